@@ -2,12 +2,15 @@
 """bench.py -- env-steps/s of the batched Capture-the-Flag tick on MI355X (BASELINE.json metric).
 
     python bench.py [--gpus N] [--steps K] [--warmup W] [--workload small16384|tiny4096|blox4096] [--obs float32|bfloat16|uint8]
+                    [--dump-outputs DIR]
     python -m torch.distributed.run --nnodes=1 --nproc-per-node N --master-addr 127.0.0.1 --master-port P bench.py --gpus N ...
 
 A "step" is one pass of the hot path over one batch: one gymPacMan tick (4 agent sub-steps, rewards, termination,
 4 observation tensors, auto-reset) of every env on the rank's GPU.  Inputs (the action stream) are resident in HBM
 before the timed region.  Envs are independent, so N GPUs hold N disjoint shards ("weak" scaling, no data-path
 collective); the timed region is bracketed by barrier + synchronize and the reported time is the max over ranks.
+`--steps` is the number of timed steps and `ms_per_step` the time of one.  `--dump-outputs DIR` writes what the last timed
+step returned to DIR/*.npy (dump_outputs()), after the timed region.
 
 The JSON line also carries
   roofline      the observation-expansion kernel (>95 % of the bytes): algorithmic bytes per launch / its average
@@ -40,6 +43,8 @@ WORKLOADS = {
 }
 HBM_PEAK_GBS = 8000.0   # MI355X_MICROARCH.md: 8 TB/s spec (6.3 TB/s measured copy ceiling)
 ROOFLINE_MIN_LAUNCHES = 500
+DUMP_BYTES = 60 << 20     # --dump-outputs: all arrays together stay under 64 MB
+DUMP_SEED = 0
 ELEM = {"float32": 4, "bfloat16": 2, "uint8": 1}
 
 
@@ -57,6 +62,28 @@ def reference_ratio(layname):
             return json.load(f)["layouts"][layname]["ratio_port_over_reference_1core"]
     except (OSError, KeyError, ValueError):
         return None
+
+
+def dump_outputs(out_dir, step_out, n_envs):
+    """Writes what the last timed env.step returned -- obs, reward, done and the info tensors -- as float32 / float64 .npy files,
+    so that two builds run with the same arguments can be compared output for output (the action stream and the env seed are
+    fixed, so the inputs are too).  Every array keeps its leading env axis; when all envs would exceed DUMP_BYTES, the same fixed,
+    seeded sample of envs is taken from each array and its indices are written as env_index.npy."""
+    obs, reward, done, info = step_out
+    arrays = {"obs": obs, "reward": reward, "done": done, **info}
+    wide = {"reward", "agent"}                                   # float64: values that float32 would round
+    per_env = sum((8 if n in wide else 4) * t[0].numel() for n, t in arrays.items())
+    k = min(n_envs, DUMP_BYTES // (per_env + 8))
+    idx = np.arange(n_envs) if k == n_envs else np.sort(np.random.RandomState(DUMP_SEED).choice(n_envs, k, replace=False))
+    sel = torch.from_numpy(idx).to(obs.device)
+    os.makedirs(out_dir, exist_ok=True)
+    files = {"env_index": idx.astype(np.float64)}
+    for n, t in arrays.items():
+        files[n] = t.index_select(0, sel).to(torch.float64 if n in wide else torch.float32).cpu().numpy()
+    for n, a in files.items():
+        np.save(os.path.join(out_dir, n + ".npy"), a)
+    return {"dir": os.path.abspath(out_dir), "envs": int(k), "of_envs": n_envs, "seed": DUMP_SEED,
+            "arrays": {n: [list(a.shape), str(a.dtype)] for n, a in files.items()}}
 
 
 def cpu_baseline(layout_rows, length, seconds=12.0, layname=None):
@@ -309,7 +336,11 @@ def main():
     ap.add_argument("--fixed-sweep", action="store_true",
                     help="run EVERY pass with the sweep direction fixed (all bytes to HBM): for profiler runs, so that the trace's average "
                          "duration of the expansion kernel is the one `roofline` is quoted on")
+    ap.add_argument("--dump-outputs", metavar="DIR", default="",
+                    help="write what the last timed step returned (rank 0's shard) to DIR/<name>.npy: see dump_outputs()")
     args = ap.parse_args()
+    if args.steps < 1 or args.warmup < 0:
+        ap.error("--steps must be at least 1 and --warmup at least 0")
     # stdout carries exactly ONE line, the JSON: whatever libraries print on file descriptor 1 meanwhile (RCCL's version banner at
     # communicator creation, MIOpen's notes) goes to stderr
     sys.stdout.flush()
@@ -367,7 +398,7 @@ def main():
     barrier()
     t0 = time.perf_counter()
     for k in range(args.steps):
-        env.step(actions[k % n_act])
+        last = env.step(actions[k % n_act])
     torch.cuda.synchronize(dev)
     if dist is not None:
         dist.barrier()
@@ -377,6 +408,7 @@ def main():
         tmax = torch.tensor([dt], dtype=torch.float64, device=dev)
         dist.all_reduce(tmax, op=dist.ReduceOp.MAX)
         dt = float(tmax.item())
+    dumped = dump_outputs(args.dump_outputs, last, n_envs) if args.dump_outputs and rank == 0 else None
     checksum = int(env.obs.sum(dtype=torch.float64).item()) if args.obs != "uint8" else int(env.obs.sum().item())
 
     # roofline pass: start/stop HIP events attached to each kernel dispatch (pmx_profile_begin/end), over AT LEAST 500 launches
@@ -507,6 +539,8 @@ def main():
         }
         if emit is not None:
             line["roofline_emit_team"] = emit
+        if dumped is not None:
+            line["dump_outputs"] = dumped
         if not args.no_cpu_baseline and world == 1:
             _progress("cpu_baseline")
             line["cpu_baseline"] = cpu_baseline(lay[0].text if isinstance(lay, list) else lay.text, length, layname=layname)
