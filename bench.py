@@ -2,7 +2,7 @@
 """bench.py -- env-steps/s of the batched Capture-the-Flag tick on MI355X (BASELINE.json metric).
 
     python bench.py [--gpus N] [--steps K] [--warmup W] [--workload small16384|tiny4096|blox4096] [--obs float32|bfloat16|uint8]
-                    [--dump-outputs DIR]
+                    [--dump-outputs DIR] [--full]
     python -m torch.distributed.run --nnodes=1 --nproc-per-node N --master-addr 127.0.0.1 --master-port P bench.py --gpus N ...
 
 A "step" is one pass of the hot path over one batch: one gymPacMan tick (4 agent sub-steps, rewards, termination,
@@ -12,7 +12,8 @@ collective); the timed region is bracketed by barrier + synchronize and the repo
 `--steps` is the number of timed steps and `ms_per_step` the time of one.  `--dump-outputs DIR` writes what the last timed
 step returned to DIR/*.npy (dump_outputs()), after the timed region.
 
-The JSON line also carries
+A plain run does only that: set up, warm up, time the steps, dump if asked, print the line.  With --full the JSON line
+also carries
   roofline      the observation-expansion kernel (>95 % of the bytes): algorithmic bytes per launch / its average
                 duration from start/stop HIP events attached to each dispatch on the launch stream (pmx_profile_begin/end) vs the 8 TB/s HBM peak
   roofline_emit_team  the same for pmx_emit_team_obs on byte planes, the observation kernel the training loop runs
@@ -131,6 +132,106 @@ def cpu_baseline(layout_rows, length, seconds=12.0, layname=None):
             "multi_thread": {"value": mt, "unit": "env-steps/s", "cores": n_thr, "sample": f"{n} envs per thread, 5 s"},
             "sample": f"{n} envs x {ticks} ticks of the same layout, float32 planes, auto-reset, uniform random actions "
                       f"({dt:.1f} s on 1 of {os.cpu_count()} host cores)"}
+
+
+def recorded_traffic(workload, kind, n_envs):
+    """The per-launch L2 <-> fabric bytes a PMC pass recorded in profiles/traffic.json for `workload:kind`, or None.  The passes
+    were taken at the workload's own env count, so another count gets None."""
+    if n_envs != WORKLOADS[workload][1]:
+        return None
+    try:
+        with open(os.path.join(ROOT, "profiles", "traffic.json")) as f:
+            return json.load(f).get(f"{workload}:{kind}", {}).get("expand_hbm_bytes_per_launch")
+    except Exception:
+        return None
+
+
+def roofline_probe(env, actions, args, n_envs, H, W, dev):
+    """The expansion kernel (pmx_expand_kernel) against the HBM peak, on the env the timed loop left behind: its average
+    duration from start/stop events on each dispatch with the sweep direction fixed, the library's default path in this loop
+    (`cache_assisted`), the default path with a consumer between ticks, and a same-device fill_ of as many bytes."""
+    n_act = actions.shape[0]
+    # roofline pass: start/stop HIP events attached to each kernel dispatch (pmx_profile_begin/end), over AT LEAST 500 launches
+    # whatever --steps is (a 20-launch average moved by 10 % from run to run), in segments whose spread is reported
+    k_roof, seg = max(args.steps, ROOFLINE_MIN_LAUNCHES), 125
+    seg_us, exp_ms, exp_n, rule_ms, rule_n = [], 0.0, 0, 0.0, 0
+    done = 0
+    while done < k_roof:
+        n = min(seg, k_roof - done)
+        env.profile_begin(n + 8)
+        for k in range(n):
+            env.step(actions[(done + k) % n_act])
+        pr = env.profile_end()
+        seg_us.append(pr["expand_ms"] * 1e3 / max(pr["expand_launches"], 1))
+        exp_ms += pr["expand_ms"]; exp_n += pr["expand_launches"]; rule_ms += pr["rule_ms"]; rule_n += pr["rule_launches"]
+        done += n
+    prof_uni = {"expand_ms": exp_ms, "expand_launches": exp_n, "rule_ms": rule_ms, "rule_launches": rule_n}
+    # the library's default path in this loop (alternating sweep): reported as `cache_assisted`, never as `value`
+    k_alt = min(max(args.steps, 100), 500)
+    env.set_tuning("expand_alt", 0 if args.fixed_sweep else -1)
+    for k in range(20):
+        env.step(actions[k % n_act])
+    torch.cuda.synchronize(dev)
+    t_alt0 = time.perf_counter()
+    for k in range(k_alt):
+        env.step(actions[k % n_act])
+    torch.cuda.synchronize(dev)
+    tick_alt_s = (time.perf_counter() - t_alt0) / k_alt
+    env.profile_begin(k_alt + 8)
+    for k in range(k_alt):
+        env.step(actions[k % n_act])
+    prof = env.profile_end()
+    # the default sweep with a CONSUMER between ticks that reads the planes and writes a rollout slot (what a training loop
+    # does first with every tick's observations): the cache holds the consumer's traffic then
+    prof_cons = None
+    if not args.no_unidirectional:
+        slots = torch.empty((4,) + tuple(env.obs.shape), dtype=env.obs.dtype, device=dev)
+        k_c = min(args.steps, 200)
+        for k in range(10):
+            env.step(actions[k % n_act]); slots[k % 4].copy_(env.obs)
+        env.profile_begin(k_c + 8)
+        for k in range(k_c):
+            env.step(actions[k % n_act]); slots[k % 4].copy_(env.obs)
+        prof_cons = env.profile_end()
+        del slots
+    expand_bytes = n_envs * 4 * 8 * H * W * ELEM[args.obs]          # algorithmic bytes of one expansion launch
+    expand_alt_s = prof["expand_ms"] / 1e3 / max(prof["expand_launches"], 1)
+    expand_s = prof_uni["expand_ms"] / 1e3 / max(prof_uni["expand_launches"], 1)
+    rule_s = prof_uni["rule_ms"] / 1e3 / max(prof_uni["rule_launches"], 1)
+    achieved = expand_bytes / expand_s / 1e9
+    # same-process, same-device calibration: a pure streaming write of the same number of bytes (torch fill_)
+    cal = torch.empty(expand_bytes // 4, dtype=torch.float32, device=dev)
+    for _ in range(5):
+        cal.fill_(1.0)
+    c0, c1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+    c0.record()
+    for _ in range(20):
+        cal.fill_(1.0)
+    c1.record()
+    torch.cuda.synchronize(dev)
+    write_ceiling = expand_bytes / (c0.elapsed_time(c1) / 20 / 1e3) / 1e9
+    del cal
+    return {"bound": "hbm", "kernel": "pmx_expand_kernel", "achieved": achieved, "peak": HBM_PEAK_GBS,
+            "unit": "GB/s", "frac": achieved / HBM_PEAK_GBS, "traffic": recorded_traffic(args.workload, args.obs, n_envs),
+            "measured_with": "sweep direction fixed (pmx_set_tuning expand_alt 0): every byte of the planes reaches HBM",
+            "traffic_scope": "PMC TCC FETCH_SIZE/WRITE_SIZE = L2 <-> fabric requests; the Infinity Cache sits behind them",
+            "algorithmic_bytes_per_launch": expand_bytes, "avg_launch_us": expand_s * 1e6,
+            "launches": prof_uni["expand_launches"], "rule_kernel_avg_us": rule_s * 1e6,
+            "segment_avg_us_min_max": [min(seg_us), max(seg_us)],
+            "frac_min_max": [expand_bytes / (max(seg_us) * 1e-6) / 1e9 / HBM_PEAK_GBS,
+                             expand_bytes / (min(seg_us) * 1e-6) / 1e9 / HBM_PEAK_GBS],
+            "same_device_fill_GBps": write_ceiling,
+            "cache_assisted": {
+                "avg_launch_us": expand_alt_s * 1e6, "GBps": expand_bytes / expand_alt_s / 1e9,
+                "us_per_tick": tick_alt_s * 1e6, "env_steps_per_s": n_envs / tick_alt_s,
+                "note": "the library's default path in THIS loop (same buffer re-stepped, nothing in between): the sweep "
+                        "direction alternates and tick t+1 overwrites the tail of tick t while it is still in the 256 MiB "
+                        "Infinity Cache; algorithmic bytes / time, NOT an HBM rate, and not what `value` is quoted on"},
+            "with_consumer": None if prof_cons is None else {
+                "avg_launch_us": prof_cons["expand_ms"] * 1e3 / max(prof_cons["expand_launches"], 1),
+                "GBps": expand_bytes / (prof_cons["expand_ms"] / 1e3 / max(prof_cons["expand_launches"], 1)) / 1e9,
+                "note": "default path with a copy of the planes into a rollout slot between ticks (reads them, writes as "
+                        "many bytes elsewhere)"}}
 
 
 def emit_team_probe(lay, n_envs, length, dev, rank, actions, launches=ROOFLINE_MIN_LAUNCHES):
@@ -324,23 +425,28 @@ def main():
     ap.add_argument("--workload", default="small16384", choices=sorted(WORKLOADS))
     ap.add_argument("--envs", type=int, default=0, help="override envs per GPU")
     ap.add_argument("--obs", default="float32", choices=sorted(ELEM))
+    ap.add_argument("--full", action="store_true",
+                    help="after the timed steps also run every other measurement: roofline and emit passes, CPU baseline, the MAPPO "
+                         "probes (the --no-* options below skip single ones)")
     ap.add_argument("--no-cpu-baseline", action="store_true")
     ap.add_argument("--no-unidirectional", action="store_true", help="skip the pass with a consumer between ticks (for profiler runs)")
     ap.add_argument("--no-ppo", action="store_true", help="skip the short MAPPO rollout/update probe")
     ap.add_argument("--no-dp-rehearsal", action="store_true", help="skip the one-rank RCCL rehearsal of the data-parallel optimizer step")
     ap.add_argument("--no-emit", action="store_true", help="skip the pmx_emit_team_obs (training-loop observation kernel) pass")
-    ap.add_argument("--no-config5", action="store_true", help="skip the 20x20 generated-maze MAPPO / IPPO probe of the default run")
+    ap.add_argument("--no-config5", action="store_true", help="skip the 20x20 generated-maze MAPPO / IPPO probe of the --full run")
     ap.add_argument("--float32-e2e", action="store_true",
-                    help="add the float32 / library-op end-to-end figure (ppo.float32_end_to_end); not in the default run: MIOpen's "
+                    help="with --full, add the float32 / library-op end-to-end figure (ppo.float32_end_to_end); not by default: MIOpen's "
                          "solver search for the float32 convolutions can take minutes on a fresh box")
     ap.add_argument("--fixed-sweep", action="store_true",
-                    help="run EVERY pass with the sweep direction fixed (all bytes to HBM): for profiler runs, so that the trace's average "
-                         "duration of the expansion kernel is the one `roofline` is quoted on")
+                    help="with --full, run EVERY pass with the sweep direction fixed (all bytes to HBM): for profiler runs, so that the "
+                         "trace's average duration of the expansion kernel is the one `roofline` is quoted on")
     ap.add_argument("--dump-outputs", metavar="DIR", default="",
                     help="write what the last timed step returned (rank 0's shard) to DIR/<name>.npy: see dump_outputs()")
     args = ap.parse_args()
     if args.steps < 1 or args.warmup < 0:
         ap.error("--steps must be at least 1 and --warmup at least 0")
+    if not args.full and (args.float32_e2e or args.fixed_sweep):
+        ap.error("--float32-e2e and --fixed-sweep change passes that only --full runs")
     # stdout carries exactly ONE line, the JSON: whatever libraries print on file descriptor 1 meanwhile (RCCL's version banner at
     # communicator creation, MIOpen's notes) goes to stderr
     sys.stdout.flush()
@@ -411,91 +517,18 @@ def main():
     dumped = dump_outputs(args.dump_outputs, last, n_envs) if args.dump_outputs and rank == 0 else None
     checksum = int(env.obs.sum(dtype=torch.float64).item()) if args.obs != "uint8" else int(env.obs.sum().item())
 
-    # roofline pass: start/stop HIP events attached to each kernel dispatch (pmx_profile_begin/end), over AT LEAST 500 launches
-    # whatever --steps is (a 20-launch average moved by 10 % from run to run), in segments whose spread is reported
-    k_roof, seg = max(args.steps, ROOFLINE_MIN_LAUNCHES), 125
-    seg_us, exp_ms, exp_n, rule_ms, rule_n = [], 0.0, 0, 0.0, 0
-    done = 0
-    while done < k_roof:
-        n = min(seg, k_roof - done)
-        env.profile_begin(n + 8)
-        for k in range(n):
-            env.step(actions[(done + k) % n_act])
-        pr = env.profile_end()
-        seg_us.append(pr["expand_ms"] * 1e3 / max(pr["expand_launches"], 1))
-        exp_ms += pr["expand_ms"]; exp_n += pr["expand_launches"]; rule_ms += pr["rule_ms"]; rule_n += pr["rule_launches"]
-        done += n
-    prof_uni = {"expand_ms": exp_ms, "expand_launches": exp_n, "rule_ms": rule_ms, "rule_launches": rule_n}
-    # the library's default path in this loop (alternating sweep): reported as `cache_assisted`, never as `value`
-    k_alt = min(max(args.steps, 100), 500)
-    env.set_tuning("expand_alt", 0 if args.fixed_sweep else -1)
-    for k in range(20):
-        env.step(actions[k % n_act])
-    torch.cuda.synchronize(dev)
-    t_alt0 = time.perf_counter()
-    for k in range(k_alt):
-        env.step(actions[k % n_act])
-    torch.cuda.synchronize(dev)
-    tick_alt_s = (time.perf_counter() - t_alt0) / k_alt
-    env.profile_begin(k_alt + 8)
-    for k in range(k_alt):
-        env.step(actions[k % n_act])
-    prof = env.profile_end()
-    # the default sweep with a CONSUMER between ticks that reads the planes and writes a rollout slot (what a training loop
-    # does first with every tick's observations): the cache holds the consumer's traffic then
-    prof_cons = None
-    if not args.no_unidirectional:
-        slots = torch.empty((4,) + tuple(env.obs.shape), dtype=env.obs.dtype, device=dev)
-        k_c = min(args.steps, 200)
-        for k in range(10):
-            env.step(actions[k % n_act]); slots[k % 4].copy_(env.obs)
-        env.profile_begin(k_c + 8)
-        for k in range(k_c):
-            env.step(actions[k % n_act]); slots[k % 4].copy_(env.obs)
-        prof_cons = env.profile_end()
-        del slots
-    e = ELEM[args.obs]
-    expand_bytes = n_envs * 4 * 8 * H * W * e                      # algorithmic bytes of one expansion launch
-    expand_alt_s = prof["expand_ms"] / 1e3 / max(prof["expand_launches"], 1)
-    expand_s = prof_uni["expand_ms"] / 1e3 / max(prof_uni["expand_launches"], 1)
-    rule_s = prof_uni["rule_ms"] / 1e3 / max(prof_uni["rule_launches"], 1)
-    achieved = expand_bytes / expand_s / 1e9
-    # same-process, same-device calibration: a pure streaming write of the same number of bytes (torch fill_)
-    cal = torch.empty(expand_bytes // 4, dtype=torch.float32, device=dev)
-    for _ in range(5):
-        cal.fill_(1.0)
-    c0, c1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-    c0.record()
-    for _ in range(20):
-        cal.fill_(1.0)
-    c1.record()
-    torch.cuda.synchronize(dev)
-    write_ceiling = expand_bytes / (c0.elapsed_time(c1) / 20 / 1e3) / 1e9
-    del cal
-    traffic = None
-    tpath = os.path.join(ROOT, "profiles", "traffic.json")
-    if os.path.exists(tpath):
-        try:
-            tj = json.load(open(tpath))
-            key = f"{args.workload}:{args.obs}"
-            if n_envs == WORKLOADS[args.workload][1]:           # the PMC passes were taken at the workload's own env count
-                traffic = tj.get(key, {}).get("expand_hbm_bytes_per_launch")
-        except Exception:
-            traffic = None
+    roofline =roofline_probe(env, actions, args, n_envs, H, W, dev) if args.full else None
     # the observation kernel of the TRAINING loop: pmx_emit_team_obs on byte planes (two learners' canonicalised planes + the
     # merged critic input per env-tick, written straight into the rollout buffers); the four-agent expansion above is the
     # reference-dtype parity path and is not launched by the trainer at all
     emit = None
-    if not args.no_emit:
+    if args.full and not args.no_emit:
         _progress("emit_team_probe")
         emit = emit_team_probe(lay, n_envs, length, dev, rank, actions)
-        try:
-            if n_envs == WORKLOADS[args.workload][1]:
-                emit["traffic"] = json.load(open(tpath)).get(f"{args.workload}:emit_uint8", {}).get("expand_hbm_bytes_per_launch")
-        except Exception:
-            pass
+        emit["traffic"] = recorded_traffic(args.workload, "emit_uint8", n_envs)
 
     if rank == 0:
+        e = ELEM[args.obs]
         B = algorithmic_bytes(H, W, e)
         value = world * n_envs * args.steps / dt
         line = {
@@ -514,39 +547,20 @@ def main():
                                       "frac_of_peak": n_envs * B / (dt / args.steps) / 1e9 / HBM_PEAK_GBS,
                                       "note": "whole tick (rule + expansion kernels, host launch path) with the sweep direction fixed: "
                                               "the loop `value` and `ms_per_step` are taken from"},
-            "roofline": {"bound": "hbm", "kernel": "pmx_expand_kernel", "achieved": achieved, "peak": HBM_PEAK_GBS,
-                         "unit": "GB/s", "frac": achieved / HBM_PEAK_GBS, "traffic": traffic,
-                         "measured_with": "sweep direction fixed (pmx_set_tuning expand_alt 0): every byte of the planes reaches HBM",
-                         "traffic_scope": "PMC TCC FETCH_SIZE/WRITE_SIZE = L2 <-> fabric requests; the Infinity Cache sits behind them",
-                         "algorithmic_bytes_per_launch": expand_bytes, "avg_launch_us": expand_s * 1e6,
-                         "launches": prof_uni["expand_launches"], "rule_kernel_avg_us": rule_s * 1e6,
-                         "segment_avg_us_min_max": [min(seg_us), max(seg_us)],
-                         "frac_min_max": [expand_bytes / (max(seg_us) * 1e-6) / 1e9 / HBM_PEAK_GBS,
-                                          expand_bytes / (min(seg_us) * 1e-6) / 1e9 / HBM_PEAK_GBS],
-                         "same_device_fill_GBps": write_ceiling,
-                         "cache_assisted": {
-                             "avg_launch_us": expand_alt_s * 1e6, "GBps": expand_bytes / expand_alt_s / 1e9,
-                             "us_per_tick": tick_alt_s * 1e6, "env_steps_per_s": n_envs / tick_alt_s,
-                             "note": "the library's default path in THIS loop (same buffer re-stepped, nothing in between): the sweep "
-                                     "direction alternates and tick t+1 overwrites the tail of tick t while it is still in the 256 MiB "
-                                     "Infinity Cache; algorithmic bytes / time, NOT an HBM rate, and not what `value` is quoted on"},
-                         "with_consumer": None if prof_cons is None else {
-                             "avg_launch_us": prof_cons["expand_ms"] * 1e3 / max(prof_cons["expand_launches"], 1),
-                             "GBps": expand_bytes / (prof_cons["expand_ms"] / 1e3 / max(prof_cons["expand_launches"], 1)) / 1e9,
-                             "note": "default path with a copy of the planes into a rollout slot between ticks (reads them, writes as "
-                                     "many bytes elsewhere)"}},
             "obs_checksum": checksum,
         }
+        if roofline is not None:
+            line["roofline"] = roofline
         if emit is not None:
             line["roofline_emit_team"] = emit
         if dumped is not None:
             line["dump_outputs"] = dumped
-        if not args.no_cpu_baseline and world == 1:
+        if args.full and not args.no_cpu_baseline and world == 1:
             _progress("cpu_baseline")
             line["cpu_baseline"] = cpu_baseline(lay[0].text if isinstance(lay, list) else lay.text, length, layname=layname)
     env.close()
     ppo = cfg5 = None
-    if not args.no_ppo:
+    if args.full and not args.no_ppo:
         rehearsal_dist = None
         if world == 1 and dist is None and not args.no_dp_rehearsal:
             try:            # a one-rank RCCL group for the data-parallel rehearsal of the optimizer step

@@ -1,4 +1,4 @@
-"""bench.py: the SURVEY 8(d) byte formula on CPU, and the one-JSON-line contract on the GPU."""
+"""bench.py: the SURVEY 8(d) byte formula on CPU, and the one-JSON-line contract of the plain and the --full run on the GPU."""
 import json
 import os
 import subprocess
@@ -22,10 +22,33 @@ def test_algorithmic_bytes_formula():
     assert r is None or r > 10                                                # port / reference speed ratio, if the file is present
 
 
+@pytest.mark.parametrize("flag", ["--float32-e2e", "--fixed-sweep"])
+def test_options_of_full_only_passes_are_refused_without_full(flag):
+    out = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), flag], capture_output=True, text=True, timeout=300, cwd=ROOT)
+    assert out.returncode == 2 and "--full" in out.stderr and not out.stdout.strip()
+
+
+FULL_ONLY = ("roofline", "roofline_emit_team", "cpu_baseline", "ppo", "ppo_config5")
+
+
+@pytest.mark.gpu
+def test_plain_bench_run_prints_the_headline_and_nothing_of_full():
+    out = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--steps", "30", "--warmup", "5", "--workload", "tiny4096"],
+                         capture_output=True, text=True, timeout=600, cwd=ROOT)
+    assert out.returncode == 0, out.stderr[-2000:]
+    lines = [l for l in out.stdout.splitlines() if l.strip()]
+    assert len(lines) == 1
+    d = json.loads(lines[0])
+    assert d["metric"] == "env-steps/s (4-agent tinyCapture)" and d["unit"] == "env-steps/s" and d["higher_is_better"] is True
+    assert d["dtype"] == "u32" and d["steps"] == 30 and d["warmup"] == 5 and d["n_gpus"] == 1
+    assert abs(d["value"] - 4096 / (d["ms_per_step"] / 1e3)) <= 1e-6 * d["value"]
+    assert not [k for k in FULL_ONLY if k in d]
+
+
 @pytest.mark.gpu
 def test_bench_prints_one_json_line_with_the_contract_keys():
     out = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--steps", "30", "--warmup", "5", "--workload", "tiny4096",
-                          "--no-ppo", "--no-cpu-baseline"], capture_output=True, text=True, timeout=600, cwd=ROOT)
+                          "--full", "--no-ppo", "--no-cpu-baseline"], capture_output=True, text=True, timeout=600, cwd=ROOT)
     assert out.returncode == 0, out.stderr[-2000:]
     lines = [l for l in out.stdout.splitlines() if l.strip().startswith("{")]
     assert len(lines) == 1
@@ -42,6 +65,7 @@ def test_bench_prints_one_json_line_with_the_contract_keys():
     # this loop is reported beside it and can only be faster
     assert "expand_alt 0" in r["measured_with"] and r["cache_assisted"]["GBps"] > 0 and "workload" in d["config"]
     assert d["tick_all_bytes_to_hbm"]["us_per_tick"] > 0
+    assert d["roofline_emit_team"]["bound"] == "hbm" and "cpu_baseline" not in d and "ppo" not in d      # the --no-* options hold
 
 
 def _fake_step(n, h, w, obs_dtype):

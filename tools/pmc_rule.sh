@@ -6,7 +6,7 @@ mkdir -p $ROOT/gpurun_out
 cd /tmp
 for grp in "SQ_WAVE_CYCLES SQ_WAIT_ANY SQ_WAIT_INST_ANY SQ_ACTIVE_INST_ANY" "SQ_IFETCH SQ_IFETCH_LEVEL SQ_WAIT_INST_LDS SQ_INST_LEVEL_VMEM" "SQ_ACTIVE_INST_VALU SQ_ACTIVE_INST_SCA SQ_ACTIVE_INST_LDS SQ_ACTIVE_INST_VMEM" "SQ_INST_LEVEL_LDS SQ_INST_LEVEL_SMEM SQ_INSTS_SMEM SQ_BUSY_CYCLES"; do
   tag=$(echo $grp | tr ' ' '_' | cut -c1-40)
-  rocprofv3 --pmc $grp --kernel-trace --output-format csv -d /tmp/pmcr_$tag -- python3 $ROOT/bench.py --steps 40 --warmup 10 --no-cpu-baseline --no-ppo --no-unidirectional > /tmp/pmcr_$tag.log 2>&1
+  rocprofv3 --pmc $grp --kernel-trace --output-format csv -d /tmp/pmcr_$tag -- python3 $ROOT/bench.py --full --steps 40 --warmup 10 --no-cpu-baseline --no-ppo --no-unidirectional > /tmp/pmcr_$tag.log 2>&1
 done
 python3 - <<'PY' > $ROOT/gpurun_out/pmc_rule.txt
 import csv, glob, collections

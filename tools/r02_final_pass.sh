@@ -8,11 +8,11 @@ O=gpurun_out/r2final
 mkdir -p $O
 python -c "import __graft_entry__ as g; g.smoke()" > $O/smoke.log 2>&1; tail -1 $O/smoke.log
 timeout -k 10 900 python -m pytest tests -m gpu -q > $O/pytest_gpu.log 2>&1; tail -1 $O/pytest_gpu.log
-timeout -k 10 600 python bench.py > $O/bench_default.json 2> $O/bench_default.err; echo bench default rc=$?
-for w in tiny4096 blox4096 mazes4096; do timeout -k 10 300 python bench.py --workload $w --no-ppo > $O/bench_$w.json 2>/dev/null; done
-timeout -k 10 300 python bench.py --obs bfloat16 --no-ppo > $O/bench_small_bfloat16.json 2>/dev/null
-timeout -k 10 300 python bench.py --obs uint8 --no-ppo > $O/bench_small_uint8.json 2>/dev/null
-timeout -k 10 300 python bench.py --envs 65536 --no-ppo > $O/bench_small65536.json 2>/dev/null
+timeout -k 10 600 python bench.py --full > $O/bench_default.json 2> $O/bench_default.err; echo bench default rc=$?
+for w in tiny4096 blox4096 mazes4096; do timeout -k 10 300 python bench.py --full --workload $w --no-ppo > $O/bench_$w.json 2>/dev/null; done
+timeout -k 10 300 python bench.py --full --obs bfloat16 --no-ppo > $O/bench_small_bfloat16.json 2>/dev/null
+timeout -k 10 300 python bench.py --full --obs uint8 --no-ppo > $O/bench_small_uint8.json 2>/dev/null
+timeout -k 10 300 python bench.py --full --envs 65536 --no-ppo > $O/bench_small65536.json 2>/dev/null
 echo benches done
 bash tools/tick_prof.sh $O
 cd /tmp

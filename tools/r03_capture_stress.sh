@@ -6,7 +6,7 @@ ROOT=${GRAFT_REPO_ROOT:-$(pwd)}
 cd $ROOT
 O=gpurun_out/r3lines; mkdir -p $O
 for i in 1 2 3 4 5; do
-  timeout -k 10 300 python bench.py --workload tiny4096 --no-cpu-baseline --no-emit --steps 100 --warmup 10 > $O/bench_tiny4096.json 2> $O/bench_tiny4096.err; echo "tiny run $i rc=$?"
+  timeout -k 10 300 python bench.py --full --workload tiny4096 --no-cpu-baseline --no-emit --steps 100 --warmup 10 > $O/bench_tiny4096.json 2> $O/bench_tiny4096.err; echo "tiny run $i rc=$?"
 done
 python - <<'PY'
 import json

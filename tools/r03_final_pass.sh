@@ -7,12 +7,12 @@ O=gpurun_out/r3final
 mkdir -p $O
 python -c "import __graft_entry__ as g; g.smoke()" > $O/smoke.log 2>&1; tail -1 $O/smoke.log
 timeout -k 10 900 python -m pytest tests -m gpu -q > $O/pytest_gpu.log 2>&1; tail -1 $O/pytest_gpu.log
-timeout -k 10 900 python bench.py > $O/bench_default.json 2> $O/bench_default.err; echo "bench default rc=$?"
-timeout -k 10 600 python bench.py --steps 20 --warmup 5 > $O/bench_driver_command.json 2>/dev/null; echo "bench driver command rc=$?"
-for w in blox4096 mazes8192; do timeout -k 10 900 python bench.py --workload $w --no-cpu-baseline > $O/bench_$w.json 2>/dev/null; echo "bench $w rc=$?"; done
-timeout -k 10 300 python bench.py --workload tiny4096 --no-ppo > $O/bench_tiny4096.json 2>/dev/null
-timeout -k 10 300 python bench.py --obs bfloat16 --no-ppo --no-emit > $O/bench_small_bfloat16.json 2>/dev/null
-timeout -k 10 300 python bench.py --obs uint8 --no-ppo --no-emit > $O/bench_small_uint8.json 2>/dev/null
+timeout -k 10 900 python bench.py --full > $O/bench_default.json 2> $O/bench_default.err; echo "bench default rc=$?"
+timeout -k 10 600 python bench.py --full --steps 20 --warmup 5 > $O/bench_driver_command.json 2>/dev/null; echo "bench driver command rc=$?"
+for w in blox4096 mazes8192; do timeout -k 10 900 python bench.py --full --workload $w --no-cpu-baseline > $O/bench_$w.json 2>/dev/null; echo "bench $w rc=$?"; done
+timeout -k 10 300 python bench.py --full --workload tiny4096 --no-ppo > $O/bench_tiny4096.json 2>/dev/null
+timeout -k 10 300 python bench.py --full --obs bfloat16 --no-ppo --no-emit > $O/bench_small_bfloat16.json 2>/dev/null
+timeout -k 10 300 python bench.py --full --obs uint8 --no-ppo --no-emit > $O/bench_small_uint8.json 2>/dev/null
 echo benches done
 bash tools/tick_prof.sh $O
 bash tools/r03_prof.sh r3final
