@@ -28,7 +28,6 @@
 #include <hip/hip_runtime.h>
 #include <hip/hip_bf16.h>
 #include <stdint.h>
-#include <stdlib.h>
 
 #include "../../include/pmx.h"
 
@@ -161,10 +160,6 @@ template <int CTRL> __device__ __forceinline__ float dpp_f(float v)
 }
 __device__ __forceinline__ float row16_sum(float v)
 {
-#ifdef PMX_ACTOR_NO_DPP         /* A/B: the ds_bpermute form */
-    v += __shfl_xor(v, 1, 64); v += __shfl_xor(v, 2, 64); v += __shfl_xor(v, 4, 64); v += __shfl_xor(v, 8, 64);
-    return v;
-#endif
     v += dpp_f<0xB1>(v);        // quad_perm [1,0,3,2]
     v += dpp_f<0x4E>(v);        // quad_perm [2,3,0,1]
     v += dpp_f<0x141>(v);       // row_half_mirror
@@ -175,14 +170,9 @@ __device__ __forceinline__ float row16_sum(float v)
 __device__ __forceinline__ float group_sum(float v)
 {
     v = row16_sum(v);
-#ifdef PMX_ACTOR_NO_DPP
-    v += __shfl_xor(v, 16, 64);
-    return v;
-#else
     float a = v, b = v;          // xor-16 step: the odd rows of a swap with the even rows of b (v_permlane16_swap, gfx950)
     asm volatile("s_nop 1\n\tv_permlane16_swap_b32 %0, %1" : "+v"(a), "+v"(b));
     return a + b;
-#endif
 }
 // sum over the 16 lanes with the same g (same channels, different positions)
 __device__ __forceinline__ float pos_sum(float v) { return row16_sum(v); }
@@ -242,25 +232,10 @@ __device__ __forceinline__ size_t dump_index(size_t sample, int NT, int t, int m
 // ---------------------------------------------------------------------------------------------------------------
 // Forward
 // ---------------------------------------------------------------------------------------------------------------
-// Forward-kernel tuning, measured on one box with tools/ab_build.sh / ab_run.sh (8 192 samples, training / inference variant):
-// RD 2 + late affine loads 605 / 615 us, RD 4 + early 625 / 650 us, RD 6 636 / 654 us -- past two tiles the registers a
-// deeper window costs (spills, each with an s_waitcnt vmcnt(0) that drains every store in flight) outweigh the latency it hides
-#ifndef PMX_ACTOR_GW_EARLY
-#define PMX_ACTOR_GW_EARLY 0                                  // 1: affine parameters loaded before the statistics instead of after
-#endif
-#ifndef PMX_ACTOR_RD
-#define PMX_ACTOR_RD 2                                        // tiles of residual in flight ahead of pass 2
-#endif
-// Development aid (-DPMX_ACTOR_TIMING, never in the shipped build): one wave's s_memtime cycles per phase, summed over its
-// layers and samples, read back with pmx_actor_ticks_read (tools/actor_ticks.py)
-#ifdef PMX_ACTOR_TIMING
-__device__ unsigned long long pmx_actor_ticks[16];
-#define PMX_TICK(var) const unsigned long long var = __builtin_amdgcn_s_memtime()
-#define PMX_TICK_ADD(i, a, b) tick_sum[i] += (b) - (a)
-#else
-#define PMX_TICK(var)
-#define PMX_TICK_ADD(i, a, b)
-#endif
+// Forward-kernel tuning, measured on one box (8 192 samples, training / inference variant): 2 tiles of residual in flight
+// ahead of pass 2 + affine parameters loaded after the statistics 605 / 615 us, 4 tiles + loaded before them 625 / 650 us,
+// 6 tiles 636 / 654 us -- past two tiles the registers a deeper window costs (spills, each with an s_waitcnt vmcnt(0) that
+// drains every store in flight) outweigh the latency it hides
 template <int NT, typename IN_T, bool SAVE>
 __global__ __launch_bounds__(256, 2) void pmx_actor_fwd_kernel(const IN_T *__restrict__ obs, const char *__restrict__ pack,
                                                               uint2 *__restrict__ feat, uint2 *__restrict__ hsave,
@@ -296,11 +271,7 @@ __global__ __launch_bounds__(256, 2) void pmx_actor_fwd_kernel(const IN_T *__res
     const float *gnbp = reinterpret_cast<const float *>(pack + PACK_GNB);
     const float inv_n = 1.0f / (float)(8 * G.HW);
 
-#ifdef PMX_ACTOR_TIMING
-    unsigned long long tick_sum[4] = {0, 0, 0, 0};
-#endif
     for (int s = blockIdx.x * 4 + wave; s < B; s += gridDim.x * 4) {
-        PMX_TICK(tk_s);
         wave_lds_fence();
         load_obs<IN_T>(obs + (size_t)s * 8 * G.HW, map, G, lane);
         wave_lds_fence();
@@ -336,8 +307,6 @@ __global__ __launch_bounds__(256, 2) void pmx_actor_fwd_kernel(const IN_T *__res
             for (int m = 0; m < 2; ++m)
 #pragma unroll
                 for (int r = 0; r < 4; ++r) bias[m][r] = biasp[l * 32 + 16 * m + 4 * g + r];
-            PMX_TICK(tk0);
-            if (li == 0) PMX_TICK_ADD(3, tk_s, tk0);
             uint2 hp[NT][2];                               // bf16-rounded convolution output (+ bias), packed
             float s1[2] = {0.f, 0.f}, s2[2] = {0.f, 0.f};
             const char *rbase = map + pq * 64 + g * 16;    // the lane's part of every operand read address
@@ -363,22 +332,14 @@ __global__ __launch_bounds__(256, 2) void pmx_actor_fwd_kernel(const IN_T *__res
                 }
                 __builtin_amdgcn_sched_barrier(0);         // one tile at a time: bounds the registers the scheduler spends on overlap
             }
-            PMX_TICK(tk1);
-            PMX_TICK_ADD(0, tk0, tk1);
             // the map has been read for the last time in this layer: the next layer's weights can start to arrive
             load_frags(A, fws + (size_t)(l + 1 < NLAYER ? l + 1 : l) * FRAG_PER_LAYER, lane);
             // ... and so can everything pass 2 reads from global memory: the affine parameters and the whole residual (the block
             // input of two layers back), RD tiles ahead of their use.  Issued here, the latency hides behind the statistics;
             // loaded tile by tile inside pass 2 each of the 2 NT reads was a full round trip the wave sat out (half the
             // kernel's time at two waves per SIMD).
-            constexpr int RD = PMX_ACTOR_RD;
+            constexpr int RD = 2;                          // tiles of residual in flight ahead of pass 2
             float gw[2][4], gb[2][4];
-#if PMX_ACTOR_GW_EARLY
-#pragma unroll
-            for (int m = 0; m < 2; ++m)
-#pragma unroll
-                for (int r = 0; r < 4; ++r) gw[m][r] = gnwp[l * 32 + 16 * m + 4 * g + r], gb[m][r] = gnbp[l * 32 + 16 * m + 4 * g + r];
-#endif
             uint2 rres[NT][2];
 #pragma unroll
             for (int t = 0; t < NT; ++t) rres[t][0] = rres[t][1] = uint2{0u, 0u};
@@ -402,15 +363,11 @@ __global__ __launch_bounds__(256, 2) void pmx_actor_fwd_kernel(const IN_T *__res
                     st[0] = mean[m], st[1] = rstd[m];
                 }
             }
-#if !PMX_ACTOR_GW_EARLY
 #pragma unroll
             for (int m = 0; m < 2; ++m)
 #pragma unroll
                 for (int r = 0; r < 4; ++r) gw[m][r] = gnwp[l * 32 + 16 * m + 4 * g + r], gb[m][r] = gnbp[l * 32 + 16 * m + 4 * g + r];
-#endif
             wave_lds_fence();
-            PMX_TICK(tk2);
-            PMX_TICK_ADD(1, tk1, tk2);
 #pragma unroll
             for (int t = 0; t < NT; ++t) {
                 const float vm = ((vmk >> t) & 1) ? 1.0f : 0.0f;
@@ -431,14 +388,8 @@ __global__ __launch_bounds__(256, 2) void pmx_actor_fwd_kernel(const IN_T *__res
                 }
             }
             wave_lds_fence();
-            PMX_TICK(tk3);
-            PMX_TICK_ADD(2, tk2, tk3);
         }
     }
-#ifdef PMX_ACTOR_TIMING
-    if (blockIdx.x == 5 && wave == 1 && lane == 0)
-        for (int i = 0; i < 4; ++i) pmx_actor_ticks[(SAVE ? 4 : 0) + i] += tick_sum[i];
-#endif
 }
 
 // ---------------------------------------------------------------------------------------------------------------
@@ -1556,28 +1507,14 @@ int grid_for(int64_t B, int blocks_per_cu)
     return (int)(want < cap ? want : cap);
 }
 
-// batches up to this size take the four-waves-per-sample kernels (PMX_ACTOR_SPLIT_MAX overrides, 0 = never; read once)
-int64_t split_max_batch()
-{
-    static const int64_t v = [] { const char *e = getenv("PMX_ACTOR_SPLIT_MAX"); return e ? (int64_t)atoll(e) : (int64_t)1536; }();
-    return v;
-}
-
-int64_t split_bwd_max_batch()      // the data-gradient kernel splits samples over waves up to this batch (PMX_ACTOR_SPLIT_BWD_MAX, read once)
-{
-    static const int64_t v = [] { const char *e = getenv("PMX_ACTOR_SPLIT_BWD_MAX"); return e ? (int64_t)atoll(e) : (int64_t)512; }();
-    return v;
-}
+constexpr int64_t SPLIT_MAX_BATCH = 1536;       // batches up to this size take the several-waves-per-sample forward kernels
+constexpr int64_t SPLIT_BWD_MAX_BATCH = 512;    // ... and the data-gradient kernel splits samples over waves up to this batch
+constexpr int64_t BWD_TWO_WAVE_MIN = 4096;      // from this batch on, the data gradient runs two waves per sample at two per SIMD
 
 // waves per sample of the small-batch forward kernel: four while every sample's block is resident at once (two blocks of ~190
 // registers per CU: 512 samples), two beyond (measured at 1 024 samples: one wave per sample 112 us, two 85 us, four 103 us -- at
-// four the blocks no longer fit in one round).  PMX_ACTOR_SPLIT_WAVES = 2 / 4 forces one (read once).
-int split_waves(int64_t B)
-{
-    static const int forced = [] { const char *e = getenv("PMX_ACTOR_SPLIT_WAVES"); return e ? atoi(e) : 0; }();
-    if (forced == 2 || forced == 4) return forced;
-    return B <= 512 ? 4 : 2;
-}
+// four the blocks no longer fit in one round)
+constexpr int split_waves(int64_t B) { return B <= 512 ? 4 : 2; }
 
 template <int NT, typename IN_T>
 int launch_fwd(const void *obs, const void *pack, void *feat, void *save, void *scratch, int64_t B, int H, int W, hipStream_t st)
@@ -1587,7 +1524,7 @@ int launch_fwd(const void *obs, const void *pack, void *feat, void *save, void *
     float *stt = hs ? reinterpret_cast<float *>(ys + 8 * B * dump) : nullptr;
     uint2 *rtmp = reinterpret_cast<uint2 *>(scratch);
     if (!save && !rtmp) return PMX_ERR_INVALID;
-    if (large_board(NT) || B <= split_max_batch()) {
+    if (large_board(NT) || B <= SPLIT_MAX_BATCH) {
         // several waves per sample (pmx_actor_fwd_split_kernel): small batches, and every batch of a large board (its
         // pre-activations do not fit one wave's registers); 2 048 skip slots exist in the scratch area
         const int ws = large_board(NT) ? 4 : split_waves(B);
@@ -1643,10 +1580,8 @@ int launch_bwd(const void *obs, const void *pack, const void *save, const void *
     float *accpart = reinterpret_cast<float *>(sk + (size_t)2048 * dump);       // then the data kernel's per-block partial sums
     int rc;
     int grid_d = grid_for(B, 2);
-    // from this batch on, two waves per sample at two waves per SIMD (PMX_ACTOR_BWD_TWO_WAVE_MIN, read once; 0 = never)
-    static const int64_t two_wave_min = [] { const char *e = getenv("PMX_ACTOR_BWD_TWO_WAVE_MIN"); return e ? (int64_t)atoll(e) : (int64_t)4096; }();
-    const bool two_wave = two_wave_min > 0 && B >= two_wave_min;
-    if (large_board(NT) || two_wave || (B <= split_max_batch() && B <= split_bwd_max_batch())) {
+    const bool two_wave = B >= BWD_TWO_WAVE_MIN;
+    if (large_board(NT) || two_wave || B <= SPLIT_BWD_MAX_BATCH) {
         // several waves per sample (pmx_actor_bwd_data_split_kernel): every batch of a large board; small batches otherwise
         // (four waves: 256 samples 56 us, 512 samples 69 us against 118 us for one wave per sample) and LARGE ones (two waves per
         // sample: the one-wave kernel holds a sample's 44 + 44 registers of gradient and pre-activation and runs one wave per
@@ -1727,9 +1662,6 @@ extern "C" int pmx_actor_forward(const void *obs_dev, int32_t obs_dtype, const v
     if (!pmx_actor_supported(H, W)) return PMX_ERR_UNSUPPORTED;
     hipStream_t st = reinterpret_cast<hipStream_t>(stream);
     const int nt = tiles_for(H, W);
-#ifdef PMX_ACTOR_EXP      /* compile-time experiments: one instantiation only */
-#define PMX_FWD(NT) return launch_fwd<11, __hip_bfloat16>(obs_dev, pack_dev, feat_dev, save_dev, scratch_dev, B, H, W, st);
-#else
 #define PMX_FWD(NT)                                                                                                      \
     switch (obs_dtype) {                                                                                                 \
     case PMX_OBS_F32: return launch_fwd<NT, float>(obs_dev, pack_dev, feat_dev, save_dev, scratch_dev, B, H, W, st);                  \
@@ -1737,7 +1669,6 @@ extern "C" int pmx_actor_forward(const void *obs_dev, int32_t obs_dtype, const v
     case PMX_OBS_U8: return launch_fwd<NT, uint8_t>(obs_dev, pack_dev, feat_dev, save_dev, scratch_dev, B, H, W, st);                 \
     default: return PMX_ERR_INVALID;                                                                                     \
     }
-#endif
     if (nt == 10) { PMX_FWD(10) }
     if (nt == 28) { PMX_FWD(28) }
     PMX_FWD(11)
@@ -1754,9 +1685,6 @@ extern "C" int pmx_actor_backward(const void *obs_dev, int32_t obs_dtype, const 
     if (B == 0) return hipMemsetAsync(grad_dev, 0, sizeof(float) * GRAD_FLOATS, st) == hipSuccess ? PMX_OK : PMX_ERR_HIP;
     // (no memset otherwise: the two row-sum kernels write every word of the gradient)
     const int nt = tiles_for(H, W);
-#ifdef PMX_ACTOR_EXP
-#define PMX_BWD(NT) return launch_bwd<11, __hip_bfloat16>(obs_dev, pack_dev, save_dev, dfeat_dev, scratch_dev, grad_dev, B, H, W, st);
-#else
 #define PMX_BWD(NT)                                                                                                                  \
     switch (obs_dtype) {                                                                                                             \
     case PMX_OBS_F32: return launch_bwd<NT, float>(obs_dev, pack_dev, save_dev, dfeat_dev, scratch_dev, grad_dev, B, H, W, st);      \
@@ -1764,7 +1692,6 @@ extern "C" int pmx_actor_backward(const void *obs_dev, int32_t obs_dtype, const 
     case PMX_OBS_U8: return launch_bwd<NT, uint8_t>(obs_dev, pack_dev, save_dev, dfeat_dev, scratch_dev, grad_dev, B, H, W, st);     \
     default: return PMX_ERR_INVALID;                                                                                                 \
     }
-#endif
     if (nt == 10) { PMX_BWD(10) }
     if (nt == 28) { PMX_BWD(28) }
     PMX_BWD(11)
@@ -2059,15 +1986,3 @@ extern "C" int pmx_proj_backward(const void *obs_dev, int32_t obs_dtype, const v
     PMX_PB(11)
 #undef PMX_PB
 }
-
-#ifdef PMX_ACTOR_TIMING
-extern "C" int pmx_actor_ticks_read(unsigned long long *out, int reset)
-{
-    if (hipMemcpyFromSymbol(out, HIP_SYMBOL(pmx_actor_ticks), sizeof(unsigned long long) * 16) != hipSuccess) return -1;
-    if (reset) {
-        unsigned long long z[16] = {0};
-        if (hipMemcpyToSymbol(HIP_SYMBOL(pmx_actor_ticks), z, sizeof(z)) != hipSuccess) return -1;
-    }
-    return 0;
-}
-#endif

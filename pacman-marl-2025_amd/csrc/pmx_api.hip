@@ -14,8 +14,7 @@ extern "C" hipError_t pmx_launch_rule_agent(const PmxTickParams *p, int H, int a
 extern "C" hipError_t pmx_launch_reset(const PmxTickParams *p, int H, hipStream_t st);
 extern "C" hipError_t pmx_launch_successor(const PmxTickParams *p, int H, int agent, hipStream_t st);
 extern "C" hipError_t pmx_launch_emit_team(const PmxEmitParams *p, int dtype, hipStream_t st, hipEvent_t ev0, hipEvent_t ev1);
-extern "C" hipError_t pmx_launch_expand(const PmxExpandParams *p, const PmxExpandTuning *tune, int dtype, hipStream_t st, hipEvent_t ev0,
-                                         hipEvent_t ev1);
+extern "C" hipError_t pmx_launch_expand(const PmxExpandParams *p, int dtype, hipStream_t st, hipEvent_t ev0, hipEvent_t ev1);
 extern "C" hipError_t pmx_launch_maze(const PmxLayoutDev *lay_dev, const int16_t *cell_index_dev, int n_cells,
                                       const int8_t *cells_dev, uint8_t *dist_dev, hipStream_t st);
 
@@ -44,7 +43,7 @@ struct pmx_env {
     // optional per-kernel timing (pmx_profile_begin/end): pairs of events around each launch
     bool profiling;
     uint64_t expand_launches = 0;   // parity selects the direction of the expansion sweep
-    PmxExpandTuning tune;           // launch tuning, read from the environment once at pmx_create
+    PmxExpandTuning tune;           // launch tuning (pmx_set_tuning)
     bool snaps_valid = false;       // the three sub-step snapshots belong to the current state (set by pmx_step)
     std::vector<hipEvent_t> ev_rule, ev_expand;
     size_t ev_rule_used, ev_expand_used;
@@ -167,7 +166,7 @@ int launch_expand(pmx_env *env, void *obs, bool from_snapshots, int single_agent
         if (env->tune.alt != 0) x.reverse = (int32_t)(env->expand_launches++ & 1);
     }
     hipEvent_t *ev = prof_pair(env, true);       // profiling: the dispatch's own start / stop timestamps
-    HIP_TRY(pmx_launch_expand(&x, &env->tune, env->cfg.obs_dtype, st, ev ? ev[0] : nullptr, ev ? ev[1] : nullptr));
+    HIP_TRY(pmx_launch_expand(&x, env->cfg.obs_dtype, st, ev ? ev[0] : nullptr, ev ? ev[1] : nullptr));
     return PMX_OK;
 }
 
@@ -274,14 +273,6 @@ int pmx_create(const pmx_config *cfg, pmx_env **out)
     if (cfg->enable_bots && dist_bytes > ((size_t)1 << 31)) { delete env; return fail(PMX_ERR_UNSUPPORTED, "enable_bots: the layouts' distance matrices exceed 2 GiB"); }
     const bool with_bots = cfg->enable_bots != 0;
     env->cfg = *cfg;
-    {   // experiment overrides of the expansion launch, read HERE once, not on the tick path
-        auto env_int = [](const char *name) { const char *o = getenv(name); return o ? atoi(o) : -1; };
-        env->tune.alt = env_int("PMX_EXPAND_ALT");
-        env->tune.nt = env_int("PMX_EXPAND_NT");
-        env->tune.lds_pad = env_int("PMX_EXPAND_LDS_PAD");
-        env->tune.lut = env_int("PMX_EXPAND_LUT");
-        env->tune.per_env = env_int("PMX_EXPAND_PER_ENV");
-    }
     env->cfg.wall_rows = env->cfg.food_rows = env->cfg.cap_rows = nullptr;
     env->cfg.starts = nullptr;
     env->cfg.layout_index = nullptr;
@@ -464,16 +455,11 @@ int pmx_observe(pmx_env *env, void *obs_dev, uint8_t *legal_dev, void *stream)
 }
 
 // ---- per-kernel timing for bench.py (not part of the reference surface) -----------------------------------------
-// Launch tuning of the expansion kernel for A/B measurements: key "expand_alt" | "expand_nt" | "expand_lds_pad" | "expand_lut",
-// value -1 = built-in choice.
+// Launch tuning of the expansion kernel: key "expand_alt", value -1 = built-in choice.
 int pmx_set_tuning(pmx_env *env, const char *key, int32_t value)
 {
     if (!env || !key) return fail(PMX_ERR_INVALID, "pmx_set_tuning: null argument");
     if (!strcmp(key, "expand_alt")) env->tune.alt = value;
-    else if (!strcmp(key, "expand_nt")) env->tune.nt = value;
-    else if (!strcmp(key, "expand_lds_pad")) env->tune.lds_pad = value;
-    else if (!strcmp(key, "expand_lut")) env->tune.lut = value;
-    else if (!strcmp(key, "expand_wave_per_env")) env->tune.per_env = value;
     else return fail(PMX_ERR_INVALID, "pmx_set_tuning: unknown key %s", key);
     return PMX_OK;
 }

@@ -62,7 +62,6 @@ __device__ __forceinline__ bf16x8 frag_of(uint32_t a, uint32_t b, uint32_t c, ui
 // Cross-lane sums without the LDS pipeline (ds_bpermute): v_permlane16_swap / v_permlane32_swap (gfx950) exchange the odd rows
 // / upper half of one register with the even rows / lower half of another, so `a = b = v; swap(a, b); a + b` is the xor-16 /
 // xor-32 all-reduce step; within a 16-lane row DPP quad permutes and mirrors do the same as modifiers of the add.
-#ifndef PMX_CRITIC_NO_DPP
 __device__ __forceinline__ float xor16_sum(float v)
 {
     float a = v, b = v;
@@ -90,22 +89,6 @@ __device__ __forceinline__ float tile_sum(float v)
     v += dpp_f<0x140>(v);       // row_mirror
     return v;
 }
-#else
-__device__ __forceinline__ float token_sum(float v)
-{
-    v += __shfl_xor(v, 16, 64);
-    v += __shfl_xor(v, 32, 64);
-    return v;
-}
-__device__ __forceinline__ float tile_sum(float v)
-{
-    v += __shfl_xor(v, 1, 64);
-    v += __shfl_xor(v, 2, 64);
-    v += __shfl_xor(v, 4, 64);
-    v += __shfl_xor(v, 8, 64);
-    return v;
-}
-#endif
 
 struct Weights {
     bf16x8 A1[8];        // W1 forward

@@ -4,9 +4,7 @@
 #include <stdint.h>
 
 #define PMX_BLOCK 256            // expansion kernel: 4 wavefronts of 64
-#ifndef PMX_RULE_BLOCK
 #define PMX_RULE_BLOCK 64        // rule kernels: one wavefront per block, so that N/64 blocks spread over all CUs
-#endif
 #define PMX_SCARED_TIME 40       // capture.py:75
 #define PMX_MIN_FOOD 2           // capture.py:70
 
@@ -98,12 +96,7 @@ struct PmxEmitParams {
     int32_t lay_H, lay_W;
 };
 
-// Host-side launch tuning of the expansion kernel: -1 = the built-in choice.  Filled once per handle at pmx_create (from the
-// PMX_EXPAND_* environment variables, for experiments) and changed through pmx_set_tuning; never read at launch time.
+// Host-side launch tuning of the expansion kernel, changed through pmx_set_tuning: -1 = the built-in choice.
 struct PmxExpandTuning {
-    int32_t alt = -1;            // alternate the sweep direction from tick to tick
-    int32_t nt = -1;             // non-temporal stores
-    int32_t lds_pad = -1;        // dynamic-LDS reservation per block (occupancy cap), bytes
-    int32_t lut = -1;            // LDS look-up-table expansion
-    int32_t per_env = -1;        // one wave per env (pmx_expand4_kernel) instead of one per (env, agent)
+    int32_t alt = -1;            // alternate the sweep direction from tick to tick (0: always the same direction)
 };

@@ -448,7 +448,7 @@ __device__ __forceinline__ void store_snapshot(const Env &e, const Ctx &c, uint3
     st[(size_t)PMX_W_CAPS(c.H, 1) * N + env] = e.capw[1];
 }
 // The same words with 16-byte stores: a dword store per word and lane is 22 (snapshot) or 25 (state) store instructions of
-// 256 bytes each, and on a kernel that runs ONE wave per CU their issue time is on the critical path (s_memtime: a sub-step
+// 256 bytes each, and on a kernel that runs ONE wave per CU their issue time is on the critical path (shader clock: a sub-step
 // with its snapshot took 2 250-2 700 ticks, one without 1 200).  The SoA rows of 64 consecutive envs are 256 contiguous
 // bytes, and the food rows already sit in LDS as [row][lane]: lane L of instruction k reads row 4k + (L >> 4), envs
 // 4 (L & 15) .. + 3 with one ds_read_b128 and stores them with one global_store_dwordx4 -- 3 + 3 instructions per snapshot
@@ -628,23 +628,11 @@ __device__ __forceinline__ Ctx make_ctx(const PmxTickParams &p, uint32_t *lds)
 
 }  // namespace
 
-// Development aid (-DPMX_RULE_TIMING, never in the shipped build): s_memtime stamps of the phases of the wave of block 0, summed
-// over launches in pmx_rule_ticks[] (start->ctx, ->state unpacked, four sub-steps with their snapshot stores, finish, state store)
-#ifdef PMX_RULE_TIMING
-__device__ unsigned long long pmx_rule_ticks[16];
-#define PMX_RTICK(i) do { const unsigned long long now_ = __builtin_amdgcn_s_memtime(); if (blockIdx.x == 0 && threadIdx.x == 0) pmx_rule_ticks[i] += now_ - last_; last_ = now_; } while (0)
-#else
-#define PMX_RTICK(i) do { } while (0)
-#endif
-
 // dynamic LDS: 32 wall rows + 3 x H rows x PMX_RULE_BLOCK lanes (food, bots' scratch copy, dump_food's blocked-cell rows)
 template <bool BOTS, int HB>
 __global__ __launch_bounds__(PMX_RULE_BLOCK) void pmx_rule_kernel(PmxTickParams p)
 {
     extern __shared__ uint32_t lds[];
-#ifdef PMX_RULE_TIMING
-    unsigned long long last_ = __builtin_amdgcn_s_memtime();
-#endif
     const int env = blockIdx.x * PMX_RULE_BLOCK + threadIdx.x;
     const bool live = env < p.N;
     RawEnv raw;
@@ -655,33 +643,22 @@ __global__ __launch_bounds__(PMX_RULE_BLOCK) void pmx_rule_kernel(PmxTickParams 
         av = reinterpret_cast<const uint32_t *>(p.actions)[env];   // 4 int8 actions
     }
     Ctx c = make_ctx(p, lds);
-    PMX_RTICK(0);
     if (!live) return;
     Env e;
     load_env_commit<HB>(e, c, raw, rows);
-    PMX_RTICK(1);
     Acc a = { 0.0, 0.0, 0, 0, 0, 0, 0 };
     count_food<HB>(a, c, rows);
     const size_t snap_sz = (size_t)PMX_SNAP_WORDS(c.H) * p.N;
     const bool wide = (p.N & (PMX_RULE_BLOCK - 1)) == 0;          // every wave is full: the 16-byte store path (store_words_wide)
     tick_substep<0, BOTS>(e, a, c, (int)(int8_t)(av & 0xFF));
     if (wide) store_snapshot_wide<HB>(e, c, p.snap, p.N); else store_snapshot<HB>(e, c, p.snap, p.N, env);
-    PMX_RTICK(2);
     tick_substep<1, BOTS>(e, a, c, (int)(int8_t)((av >> 8) & 0xFF));
     if (wide) store_snapshot_wide<HB>(e, c, p.snap + snap_sz, p.N); else store_snapshot<HB>(e, c, p.snap + snap_sz, p.N, env);
-    PMX_RTICK(3);
     tick_substep<2, BOTS>(e, a, c, (int)(int8_t)((av >> 16) & 0xFF));
     if (wide) store_snapshot_wide<HB>(e, c, p.snap + 2 * snap_sz, p.N); else store_snapshot<HB>(e, c, p.snap + 2 * snap_sz, p.N, env);
-    PMX_RTICK(4);
     tick_substep<3, BOTS>(e, a, c, (int)(int8_t)((av >> 24) & 0xFF));
-    PMX_RTICK(5);
     tick_finish<HB>(e, a, c, p, env, true);
-    PMX_RTICK(6);
     if (wide) store_env_wide<HB>(e, c, p.state, p.N); else store_env<HB>(e, c, p.state, p.N, env);
-    PMX_RTICK(7);
-#ifdef PMX_RULE_TIMING
-    if (blockIdx.x == 0 && threadIdx.x == 0) pmx_rule_ticks[15] += 1;
-#endif
 }
 
 // pmx_step_agent: one sub-step; the accumulators of the open tick travel through the state words.
@@ -851,18 +828,18 @@ __device__ __forceinline__ void stream_or_row(uint32_t *T, uint32_t off, uint32_
 //      store: the wave writes 1 KiB of consecutive addresses per instruction.  LDS operations of one wavefront
 //      execute in order, so the waves need no barrier after the one that publishes the look-up table.
 // ---------------------------------------------------------------------------------------------------------------
-// LUT: the 16 output bytes of a lane come from a block-shared lookup table indexed by its stream bits (float32: 16 entries
+// The 16 output bytes of a lane come from a block-shared lookup table indexed by its stream bits (float32: 16 entries
 // of 16 bytes, every entry in its own four LDS banks, so any mix of indices is conflict free; bfloat16: 256 entries; uint8: two
 // 8-bit look-ups of 8 bytes) instead of being computed: with the observation buffer partly resident in the Infinity Cache the
 // float32 kernel had become instruction bound (~1.8 T elements/s whatever the footprint), and the expansion arithmetic was most
 // of its ~35 instructions per 16 bytes.
-template <int DT, bool NT, bool LUT>
+template <int DT, bool NT>
 __global__ __launch_bounds__(PMX_BLOCK) void pmx_expand_kernel(PmxExpandParams p)
 {
     constexpr int VEC = ObsVec<DT>::VEC;
     __shared__ uint32_t tab[4][8 * 32 * 32 / 32 + 8];
-    __shared__ __align__(16) uint32_t lut[LUT ? (DT == 0 ? 16 * 4 : (DT == 1 ? 256 * 4 : 256 * 2)) : 4];
-    if (LUT) {
+    __shared__ __align__(16) uint32_t lut[DT == 0 ? 16 * 4 : (DT == 1 ? 256 * 4 : 256 * 2)];
+    {
         const uint32_t i = threadIdx.x;
         if (DT == 0) {
             if (i < 16) *reinterpret_cast<uint4 *>(&lut[4 * i]) = pack_obs<0>(i);
@@ -939,16 +916,12 @@ __global__ __launch_bounds__(PMX_BLOCK) void pmx_expand_kernel(PmxExpandParams p
         const uint32_t e0 = (uint32_t)k * VEC;
         const uint32_t bits = T[e0 >> 5] >> (e0 & 31);
         uint4 v;
-        if (LUT) {
-            if (DT == 0) v = *reinterpret_cast<const uint4 *>(&lut[(bits & 15u) * 4]);
-            else if (DT == 1) v = *reinterpret_cast<const uint4 *>(&lut[(bits & 255u) * 4]);
-            else {
-                const uint2 lo = *reinterpret_cast<const uint2 *>(&lut[(bits & 255u) * 2]);
-                const uint2 hi = *reinterpret_cast<const uint2 *>(&lut[((bits >> 8) & 255u) * 2]);
-                v = make_uint4(lo.x, lo.y, hi.x, hi.y);
-            }
-        } else {
-            v = pack_obs<DT>(bits);
+        if (DT == 0) v = *reinterpret_cast<const uint4 *>(&lut[(bits & 15u) * 4]);
+        else if (DT == 1) v = *reinterpret_cast<const uint4 *>(&lut[(bits & 255u) * 4]);
+        else {
+            const uint2 lo = *reinterpret_cast<const uint2 *>(&lut[(bits & 255u) * 2]);
+            const uint2 hi = *reinterpret_cast<const uint2 *>(&lut[((bits >> 8) & 255u) * 2]);
+            v = make_uint4(lo.x, lo.y, hi.x, hi.y);
         }
         const uint32_t d = (uint32_t)(fself - (int)e0);
         if (d < (uint32_t)VEC) patch_self<DT>(v, (int)d, carry);
@@ -962,18 +935,16 @@ __global__ __launch_bounds__(PMX_BLOCK) void pmx_expand_kernel(PmxExpandParams p
 }
 
 // ---------------------------------------------------------------------------------------------------------------
-// The same expansion with ONE wavefront per ENV for the narrow element types: at 1 or 2 bytes per element an (env, agent)
-// block is 1.2 - 2.5 KB, i.e. one or two store instructions per lane behind a fixed ~2 us of snapshot-load latency and table
-// set-up -- pmx_expand_kernel is issue / latency bound there (0.39 of the HBM peak for uint8).  Here a wave issues the snapshot
-// loads of all four agents together, builds the four bit streams side by side in LDS and then streams the env's whole
-// [4][8][H][W] block (4.9 KB of uint8 for smallCapture, contiguous: whole 128-byte lines except at the two ends, where
-// pmx_expand_kernel's 1 232-byte agent blocks split a line each).
+// The same expansion with ONE wavefront per ENV for uint8 planes: at 1 byte per element an (env, agent) block is 1.2 KB, i.e.
+// one or two store instructions per lane behind a fixed ~2 us of snapshot-load latency and table set-up -- pmx_expand_kernel is
+// issue / latency bound there (0.39 of the HBM peak).  Here a wave issues the snapshot loads of all four agents together, builds
+// the four bit streams side by side in LDS and then streams the env's whole [4][8][H][W] block (4.9 KB for smallCapture,
+// contiguous: whole 128-byte lines except at the two ends, where pmx_expand_kernel's 1 232-byte agent blocks split a line each).
 // ---------------------------------------------------------------------------------------------------------------
-// EPW envs per wave, consecutive, with the NEXT env's snapshot words loaded while the current env's planes are streamed.
-// Measured and NOT used (EPW = 1 is what is launched): s_memtime (tools/rule_ticks.py, uint8) shows a wave spending ~7 k of its
-// ~14 k ticks on the snapshot loads, which queue behind the other waves' plane stores, yet two envs per wave with the prefetch ran
-// 20.4 us against 18.5 us -- as did a variant with 16 envs per block and cooperative, fully coalesced snapshot loads (24.9 us):
-// with half the waves the chip has fewer store streams in flight, and that costs more than the hidden latency gains.
+// One env per wave.  Measured and not kept: two envs per wave, the second env's snapshot words loaded while the first env's
+// planes are streamed (a wave spent ~7 k of its ~14 k shader-clock ticks on the snapshot loads, which queue behind the other
+// waves' plane stores), ran 20.4 us against 18.5 us -- as did 16 envs per block with cooperative, fully coalesced snapshot
+// loads (24.9 us): with half the waves the chip has fewer store streams in flight, and that costs more than the hidden latency.
 struct SnapWords { uint32_t food[4], pt[4], a_self[4], b_self[4]; };
 __device__ __forceinline__ void load_snap_words(SnapWords &s, const PmxExpandParams &p, long env, int lane, int H)
 {
@@ -990,148 +961,116 @@ __device__ __forceinline__ void load_snap_words(SnapWords &s, const PmxExpandPar
     }
 }
 
-template <int DT, bool NT, int EPW>
+template <bool NT>
 __global__ __launch_bounds__(PMX_BLOCK) void pmx_expand4_kernel(PmxExpandParams p)
 {
-    constexpr int VEC = ObsVec<DT>::VEC;
+    constexpr int DT = 2, VEC = ObsVec<DT>::VEC;
     constexpr int TW = 8 * 32 * 32 / 32 + 8;
     __shared__ uint32_t tab[4][4][TW];                        // [wave][agent][stream words]
-    __shared__ __align__(16) uint32_t lut[DT == 0 ? 16 * 4 : (DT == 1 ? 256 * 4 : 256 * 2)];
+    __shared__ __align__(16) uint32_t lut[256 * 2];           // 8 stream bits -> 8 bytes
     {
         const uint32_t i = threadIdx.x;
-        if (DT == 0) {
-            if (i < 16) *reinterpret_cast<uint4 *>(&lut[4 * i]) = pack_obs<0>(i);
-        } else if (DT == 1) {
-            *reinterpret_cast<uint4 *>(&lut[4 * i]) = pack_obs<1>(i);
-        } else {
-            lut[2 * i] = ((i & 15u) * 0x00204081u) & 0x01010101u;
-            lut[2 * i + 1] = ((i >> 4) * 0x00204081u) & 0x01010101u;
-        }
+        lut[2 * i] = ((i & 15u) * 0x00204081u) & 0x01010101u;
+        lut[2 * i + 1] = ((i >> 4) * 0x00204081u) & 0x01010101u;
         __syncthreads();
     }
     const int wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
     const int lane = threadIdx.x & 63;
     const int W = p.lay_W, H = p.lay_H, HW = H * W;
     long blk = p.reverse ? (long)gridDim.x - 1 - (long)blockIdx.x : (long)blockIdx.x;
-    if ((p.N & (128 * EPW - 1)) == 0 && EPW <= 4) {
+    if ((p.N & 127) == 0) {
         // XCD-aware order (blocks b, b + 8, .. share an XCD): the 16 envs whose SoA snapshot words share a 64-byte line are
-        // 4 / EPW consecutive blocks; send them to one XCD
-        constexpr int G = 4 / EPW;                            // blocks per line of 16 envs
-        const long r = blk & (8 * G - 1);
-        blk = (blk & ~(long)(8 * G - 1)) + (r & 7) * G + (r >> 3);
+        // 4 consecutive blocks; send them to one XCD
+        const long r = blk & 31;
+        blk = (blk & ~31L) + (r & 7) * 4 + (r >> 3);
     }
-    const long env_first = (blk * 4 + wave) * EPW;
-    if (env_first >= p.N) return;
-#ifdef PMX_RULE_TIMING
-    unsigned long long last_ = __builtin_amdgcn_s_memtime();
-    const bool rec_ = (blockIdx.x == 0 || blockIdx.x == gridDim.x / 2 || blockIdx.x == gridDim.x - 1) && threadIdx.x == 0;
-#define PMX_XTICK(i) do { const unsigned long long now_ = __builtin_amdgcn_s_memtime(); if (rec_) atomicAdd(&pmx_rule_ticks[8 + i], now_ - last_); last_ = now_; } while (0)
-#else
-#define PMX_XTICK(i) do { } while (0)
-#endif
+    const long env = blk * 4 + wave;
+    if (env >= p.N) return;
     const int n_words = (8 * HW + 31) >> 5;
     const int wall_words = (HW + 31) >> 5;
     const int n_vec = 8 * HW / VEC;
     SnapWords cur;
-    load_snap_words(cur, p, env_first, lane, H);              // all four agents' snapshot words in flight together
-#pragma unroll 1
-    for (int q = 0; q < EPW; ++q) {
-        const long env = env_first + q;
-        if (env >= p.N) break;
-        const PmxLayoutDev *L = p.lay + (p.layout_idx ? p.layout_idx[env] : 0);
+    load_snap_words(cur, p, env, lane, H);                    // all four agents' snapshot words in flight together
+    const PmxLayoutDev *L = p.lay + (p.layout_idx ? p.layout_idx[env] : 0);
 #pragma unroll
-        for (int a = 0; a < 4; ++a)
-            for (int k = lane; k < n_words + 1; k += 64) tab[wave][a][k] = k < wall_words ? L->wall_stream[k] : 0u;
-        const uint32_t hi_mask = L->hi_mask, lo_mask = L->lo_mask;
-        __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
-        __builtin_amdgcn_wave_barrier();
-        PMX_XTICK(0);
-        int fself[4];
-        uint32_t carry[4];
+    for (int a = 0; a < 4; ++a)
+        for (int k = lane; k < n_words + 1; k += 64) tab[wave][a][k] = k < wall_words ? L->wall_stream[k] : 0u;
+    const uint32_t hi_mask = L->hi_mask, lo_mask = L->lo_mask;
+    __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
+    __builtin_amdgcn_wave_barrier();
+    int fself[4];
+    uint32_t carry[4];
 #pragma unroll
-        for (int a = 0; a < 4; ++a) {
-            uint32_t *T = tab[wave][a];
-            if (lane < H) {
-                stream_or_row(T, (uint32_t)((6 * H + lane) * W), cur.food[a] & hi_mask, W);
-                stream_or_row(T, (uint32_t)((7 * H + lane) * W), cur.food[a] & lo_mask, W);
-            }
-            if (lane < 4) {
-                const int x = cur.pt[a] & 0xFF, y = (cur.pt[a] >> 8) & 0xFF;
-                const int plane = lane == a ? 1 : (((lane ^ a) == 2) ? 4 : 5);
+    for (int a = 0; a < 4; ++a) {
+        uint32_t *T = tab[wave][a];
+        if (lane < H) {
+            stream_or_row(T, (uint32_t)((6 * H + lane) * W), cur.food[a] & hi_mask, W);
+            stream_or_row(T, (uint32_t)((7 * H + lane) * W), cur.food[a] & lo_mask, W);
+        }
+        if (lane < 4) {
+            const int x = cur.pt[a] & 0xFF, y = (cur.pt[a] >> 8) & 0xFF;
+            const int plane = lane == a ? 1 : (((lane ^ a) == 2) ? 4 : 5);
+            const uint32_t off = (uint32_t)((plane * H + y) * W + x);
+            atomicOr(&T[off >> 5], 1u << (off & 31));
+        } else if (lane < 8) {
+            const uint32_t cxy = (cur.pt[a] >> (16 * ((lane - 4) & 1))) & 0xFFFFu;
+            if (cxy != 0xFFFFu) {
+                const int x = cxy & 0xFF, y = cxy >> 8;
+                const int plane = (2 * x > W) ? 2 : 3;
                 const uint32_t off = (uint32_t)((plane * H + y) * W + x);
                 atomicOr(&T[off >> 5], 1u << (off & 31));
-            } else if (lane < 8) {
-                const uint32_t cxy = (cur.pt[a] >> (16 * ((lane - 4) & 1))) & 0xFFFFu;
-                if (cxy != 0xFFFFu) {
-                    const int x = cxy & 0xFF, y = cxy >> 8;
-                    const int plane = (2 * x > W) ? 2 : 3;
-                    const uint32_t off = (uint32_t)((plane * H + y) * W + x);
-                    atomicOr(&T[off >> 5], 1u << (off & 31));
-                }
-            }
-            carry[a] = (cur.b_self[a] >> 8) & 0xFFF;
-            fself[a] = (H + (int)((cur.a_self[a] >> 8) & 0xFF)) * W + (int)(cur.a_self[a] & 0xFF);
-        }
-        if (EPW > 1 && q + 1 < EPW && env + 1 < p.N) load_snap_words(cur, p, env + 1, lane, H);   // in flight behind the stores below
-        __builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "wavefront");
-        __builtin_amdgcn_wave_barrier();
-        PMX_XTICK(1);
-
-        uint4 *out = reinterpret_cast<uint4 *>(p.obs) + (size_t)env * 4 * n_vec;
-        // U iterations of the store loop at a time: all their stream words are read first, then all look-up-table entries,
-        // then the stores are issued -- one LDS round trip per group instead of two per 16 bytes (a wave spent 1.2 k ticks per
-        // store instruction on these dependent reads)
-        constexpr int U = 5;
-        for (int base = 0; base < 4 * n_vec; base += 64 * U) {
-            uint32_t bits[U];
-            int ag[U];
-            uint32_t e0s[U];
-#pragma unroll
-            for (int u = 0; u < U; ++u) {
-                const int kk = base + 64 * u + lane;
-                const int a = (kk >= n_vec) + (kk >= 2 * n_vec) + (kk >= 3 * n_vec);
-                const int a_c = kk < 4 * n_vec ? a : 0;
-                const int k = kk < 4 * n_vec ? kk - a * n_vec : 0;
-                ag[u] = a_c;
-                e0s[u] = (uint32_t)k * VEC;
-                bits[u] = tab[wave][a_c][e0s[u] >> 5] >> (e0s[u] & 31);
-            }
-            uint4 v[U];
-#pragma unroll
-            for (int u = 0; u < U; ++u) {
-                if (DT == 0) v[u] = *reinterpret_cast<const uint4 *>(&lut[(bits[u] & 15u) * 4]);
-                else if (DT == 1) v[u] = *reinterpret_cast<const uint4 *>(&lut[(bits[u] & 255u) * 4]);
-                else {
-                    const uint2 lo = *reinterpret_cast<const uint2 *>(&lut[(bits[u] & 255u) * 2]);
-                    const uint2 hi = *reinterpret_cast<const uint2 *>(&lut[((bits[u] >> 8) & 255u) * 2]);
-                    v[u] = make_uint4(lo.x, lo.y, hi.x, hi.y);
-                }
-            }
-#pragma unroll
-            for (int u = 0; u < U; ++u) {
-                const int kk = base + 64 * u + lane;
-                const int a = ag[u];
-                const int fs = a == 0 ? fself[0] : (a == 1 ? fself[1] : (a == 2 ? fself[2] : fself[3]));
-                const uint32_t cr = a == 0 ? carry[0] : (a == 1 ? carry[1] : (a == 2 ? carry[2] : carry[3]));
-                const uint32_t d = (uint32_t)(fs - (int)e0s[u]);
-                if (d < (uint32_t)VEC) patch_self<DT>(v[u], (int)d, cr);
-                if (kk < 4 * n_vec) {
-                    if (NT) {
-                        __builtin_nontemporal_store(v[u].x, &out[kk].x); __builtin_nontemporal_store(v[u].y, &out[kk].y);
-                        __builtin_nontemporal_store(v[u].z, &out[kk].z); __builtin_nontemporal_store(v[u].w, &out[kk].w);
-                    } else {
-                        out[kk] = v[u];
-                    }
-                }
             }
         }
-        __builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "wavefront");      // the tables are rebuilt for the next env
-        __builtin_amdgcn_wave_barrier();
-        PMX_XTICK(2);
+        carry[a] = (cur.b_self[a] >> 8) & 0xFFF;
+        fself[a] = (H + (int)((cur.a_self[a] >> 8) & 0xFF)) * W + (int)(cur.a_self[a] & 0xFF);
     }
-#ifdef PMX_RULE_TIMING
-    if (rec_) atomicAdd(&pmx_rule_ticks[14], 1ull);
-#endif
+    __builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "wavefront");
+    __builtin_amdgcn_wave_barrier();
+
+    uint4 *out = reinterpret_cast<uint4 *>(p.obs) + (size_t)env * 4 * n_vec;
+    // U iterations of the store loop at a time: all their stream words are read first, then all look-up-table entries,
+    // then the stores are issued -- one LDS round trip per group instead of two per 16 bytes (a wave spent 1.2 k ticks per
+    // store instruction on these dependent reads)
+    constexpr int U = 5;
+    for (int base = 0; base < 4 * n_vec; base += 64 * U) {
+        uint32_t bits[U];
+        int ag[U];
+        uint32_t e0s[U];
+#pragma unroll
+        for (int u = 0; u < U; ++u) {
+            const int kk = base + 64 * u + lane;
+            const int a = (kk >= n_vec) + (kk >= 2 * n_vec) + (kk >= 3 * n_vec);
+            const int a_c = kk < 4 * n_vec ? a : 0;
+            const int k = kk < 4 * n_vec ? kk - a * n_vec : 0;
+            ag[u] = a_c;
+            e0s[u] = (uint32_t)k * VEC;
+            bits[u] = tab[wave][a_c][e0s[u] >> 5] >> (e0s[u] & 31);
+        }
+        uint4 v[U];
+#pragma unroll
+        for (int u = 0; u < U; ++u) {
+            const uint2 lo = *reinterpret_cast<const uint2 *>(&lut[(bits[u] & 255u) * 2]);
+            const uint2 hi = *reinterpret_cast<const uint2 *>(&lut[((bits[u] >> 8) & 255u) * 2]);
+            v[u] = make_uint4(lo.x, lo.y, hi.x, hi.y);
+        }
+#pragma unroll
+        for (int u = 0; u < U; ++u) {
+            const int kk = base + 64 * u + lane;
+            const int a = ag[u];
+            const int fs = a == 0 ? fself[0] : (a == 1 ? fself[1] : (a == 2 ? fself[2] : fself[3]));
+            const uint32_t cr = a == 0 ? carry[0] : (a == 1 ? carry[1] : (a == 2 ? carry[2] : carry[3]));
+            const uint32_t d = (uint32_t)(fs - (int)e0s[u]);
+            if (d < (uint32_t)VEC) patch_self<DT>(v[u], (int)d, cr);
+            if (kk < 4 * n_vec) {
+                if (NT) {
+                    __builtin_nontemporal_store(v[u].x, &out[kk].x); __builtin_nontemporal_store(v[u].y, &out[kk].y);
+                    __builtin_nontemporal_store(v[u].z, &out[kk].z); __builtin_nontemporal_store(v[u].w, &out[kk].w);
+                } else {
+                    out[kk] = v[u];
+                }
+            }
+        }
+    }
 }
 
 // ---------------------------------------------------------------------------------------------------------------
@@ -1361,12 +1300,11 @@ extern "C" hipError_t pmx_launch_reset(const PmxTickParams *p, int H, hipStream_
     return hipGetLastError();
 }
 
-extern "C" hipError_t pmx_launch_expand(const PmxExpandParams *p, const PmxExpandTuning *tune, int dtype, hipStream_t st, hipEvent_t ev0,
-                                         hipEvent_t ev1)
+extern "C" hipError_t pmx_launch_expand(const PmxExpandParams *p, int dtype, hipStream_t st, hipEvent_t ev0, hipEvent_t ev1)
 {
     const long waves = (long)p->N * p->n_emit;
     const unsigned blocks = (unsigned)((waves + 3) / 4);
-    // Store policy, measured in one process with tools/ab_expand.py (us per launch):
+    // Store policy, measured in one process (us per launch):
     //   f32   323 MB  ordinary 53.7 | nt 64.9 | nt + 3 blocks/CU 60.0
     //         646 MB  ordinary 114.6 | nt 126.1 | nt + 3 blocks/CU 107.2
     //        1.29 GB  ordinary 262 | nt 246 | nt + 4 blocks/CU 227 | nt + 3 blocks/CU 207.8 | nt + 2 blocks/CU 278
@@ -1387,70 +1325,36 @@ extern "C" hipError_t pmx_launch_expand(const PmxExpandParams *p, const PmxExpan
     // It needs ordinary (cache-allocating) stores, so float32 planes up to 900 MB now use them; p->reverse carries the parity.
     const size_t elem = dtype == 0 ? 4 : (dtype == 1 ? 2 : 1);
     const size_t bytes = (size_t)waves * 8 * p->lay_H * p->lay_W * elem;
-    bool nt = elem == 1 || (elem == 2 && bytes > ((size_t)512 << 20)) || (elem == 4 && bytes > ((size_t)900 << 20));
-    if (tune && tune->nt >= 0) nt = tune->nt != 0;                        // experiment override (pmx_set_tuning)
-    size_t lds_pad = (nt && elem == 4) ? 40000 : 0;
-    if (tune && tune->lds_pad >= 0) lds_pad = (size_t)tune->lds_pad;      // experiment override
+    // uint8 planes always take streaming stores (and so never the alternating sweep); float32 and bfloat16 by size
+    const bool nt = elem == 1 || (elem == 2 && bytes > ((size_t)512 << 20)) || (elem == 4 && bytes > ((size_t)900 << 20));
+    const size_t lds_pad = (nt && elem == 4) ? 40000 : 0;
     PmxExpandParams q = *p;
     if (nt) q.reverse = 0;
-    p = &q;
-    bool use_lut = true;
-    if (tune && tune->lut >= 0) use_lut = tune->lut != 0;                 // experiment override
     // uint8 planes with all four agents emitted: one wave per env (pmx_expand4_kernel; measured at 16 384 envs of smallCapture:
-    // 25.8 -> 22.4 us for uint8, but 26.7 -> 28.3 us for bfloat16, which therefore keeps the wave per (env, agent));
-    // pmx_set_tuning("expand_wave_per_env", 0/1) overrides
-    bool per_env = dtype == 2 && p->n_emit == 4 && p->single_agent < 0;
-    if (tune && tune->per_env >= 0) per_env = tune->per_env != 0 && p->n_emit == 4 && p->single_agent < 0;
-    if (per_env) {
-        constexpr int epw = 1;                                 // envs per wave (see pmx_expand4_kernel)
-        const unsigned b4 = (unsigned)((p->N + 4 * epw - 1) / (4 * epw));
-#define PMX_EXPAND4(DT, NTV)                                                                                              \
+    // 25.8 -> 22.4 us for uint8, but 26.7 -> 28.3 us for bfloat16, which therefore keeps the wave per (env, agent))
+    if (dtype == 2 && p->n_emit == 4 && p->single_agent < 0) {
+        const unsigned b4 = (unsigned)((p->N + 3) / 4);
+        // this kernel's planes fit the Infinity Cache up to a few hundred MB: ordinary stores there, streaming beyond
+        const bool nt4 = bytes > ((size_t)200 << 20);
+#define PMX_EXPAND4(NTV)                                                                                                  \
     do {                                                                                                                  \
-        if (ev0) hipExtLaunchKernelGGL((pmx_expand4_kernel<DT, NTV, epw>), dim3(b4), dim3(PMX_BLOCK), 0, st, ev0, ev1, 0, *p); \
-        else hipLaunchKernelGGL((pmx_expand4_kernel<DT, NTV, epw>), dim3(b4), dim3(PMX_BLOCK), 0, st, *p);                 \
+        if (ev0) hipExtLaunchKernelGGL((pmx_expand4_kernel<NTV>), dim3(b4), dim3(PMX_BLOCK), 0, st, ev0, ev1, 0, q);      \
+        else hipLaunchKernelGGL((pmx_expand4_kernel<NTV>), dim3(b4), dim3(PMX_BLOCK), 0, st, q);                          \
     } while (0)
-        // the planes of these types fit the Infinity Cache up to a few hundred MB: ordinary stores there, streaming beyond
-        const bool nt4 = (tune && tune->nt >= 0) ? tune->nt != 0 : bytes > ((size_t)200 << 20);
-        PmxExpandParams q4 = *p;
-        if (nt4) q4.reverse = 0;
-        p = &q4;
-        switch (dtype) {
-        case 0: if (nt4) PMX_EXPAND4(0, true); else PMX_EXPAND4(0, false); break;
-        case 1: if (nt4) PMX_EXPAND4(1, true); else PMX_EXPAND4(1, false); break;
-        default: if (nt4) PMX_EXPAND4(2, true); else PMX_EXPAND4(2, false); break;
-        }
+        if (nt4) PMX_EXPAND4(true); else PMX_EXPAND4(false);
 #undef PMX_EXPAND4
         return hipGetLastError();
     }
-#define PMX_EXPAND_LAUNCH2(DT, NTV, LUTV)                                                                               \
+#define PMX_EXPAND(DT, NTV)                                                                                             \
     do {                                                                                                                \
-        if (ev0) hipExtLaunchKernelGGL((pmx_expand_kernel<DT, NTV, LUTV>), dim3(blocks), dim3(PMX_BLOCK), (uint32_t)lds_pad, st, ev0, ev1, 0, *p); \
-        else hipLaunchKernelGGL((pmx_expand_kernel<DT, NTV, LUTV>), dim3(blocks), dim3(PMX_BLOCK), lds_pad, st, *p);      \
-    } while (0)
-#define PMX_EXPAND_LAUNCH1(DT, NTV)                                                                                     \
-    do {                                                                                                                \
-        if (use_lut) PMX_EXPAND_LAUNCH2(DT, NTV, true); else PMX_EXPAND_LAUNCH2(DT, NTV, false);                        \
-    } while (0)
-#define PMX_EXPAND_LAUNCH(DT)                                                                                           \
-    do {                                                                                                                \
-        if (nt) PMX_EXPAND_LAUNCH1(DT, true); else PMX_EXPAND_LAUNCH1(DT, false);                                       \
+        if (ev0) hipExtLaunchKernelGGL((pmx_expand_kernel<DT, NTV>), dim3(blocks), dim3(PMX_BLOCK), (uint32_t)lds_pad, st, ev0, ev1, 0, q); \
+        else hipLaunchKernelGGL((pmx_expand_kernel<DT, NTV>), dim3(blocks), dim3(PMX_BLOCK), lds_pad, st, q);          \
     } while (0)
     switch (dtype) {
-    case 0: PMX_EXPAND_LAUNCH(0); break;
-    case 1: PMX_EXPAND_LAUNCH(1); break;
-    default: PMX_EXPAND_LAUNCH(2); break;
+    case 0: if (nt) PMX_EXPAND(0, true); else PMX_EXPAND(0, false); break;
+    case 1: if (nt) PMX_EXPAND(1, true); else PMX_EXPAND(1, false); break;
+    default: PMX_EXPAND(2, true); break;
     }
+#undef PMX_EXPAND
     return hipGetLastError();
 }
-
-#ifdef PMX_RULE_TIMING
-extern "C" int pmx_rule_ticks_read(unsigned long long *out, int reset)
-{
-    if (hipMemcpyFromSymbol(out, HIP_SYMBOL(pmx_rule_ticks), sizeof(unsigned long long) * 16) != hipSuccess) return -1;
-    if (reset) {
-        unsigned long long z[16] = {0};
-        if (hipMemcpyToSymbol(HIP_SYMBOL(pmx_rule_ticks), z, sizeof(z)) != hipSuccess) return -1;
-    }
-    return 0;
-}
-#endif

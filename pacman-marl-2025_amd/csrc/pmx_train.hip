@@ -597,7 +597,6 @@ extern "C" int pmx_gn8_gelu_backward(const void *h, const void *res, const void 
 // written as [S][B][E], so no head split / merge copies exist.
 //   S^T tile = K_tile . Q_tile^T      v_mfma_f32_16x16x32_bf16, head_dim 8 zero-padded to the K = 32 of the instruction;
 //                                     the accumulator holds S^T[key = 4*(lane>>4)+reg][query = lane&15]
-//   online softmax per query column   (max / sum over the 8 keys a lane holds, then over the four lane groups: 2 shuffles)
 //   O^T += V^T . P^T                  the exp'd accumulators of two key tiles ARE the B fragment of the next MFMA: the
 //                                     contraction index (keys) may be enumerated in any order as long as the A operand
 //                                     (V^T, staged transposed in LDS) uses the same one -- no LDS round trip for P.
@@ -611,115 +610,6 @@ __device__ __forceinline__ short pmx_f2bf(float f)
 {
     const __hip_bfloat16 h = __float2bfloat16(f);
     return *reinterpret_cast<const short *>(&h);
-}
-
-__global__ __launch_bounds__(512) void pmx_attn8_fwd_kernel(const __hip_bfloat16 *__restrict__ qkv, __hip_bfloat16 *__restrict__ out,
-                                                            float *__restrict__ lse, int S, int B, float scale, int bm)
-{
-    constexpr int D = 8, HEADS = 4, E = 32;
-    extern __shared__ __align__(16) unsigned char smem[];
-    const int wave = threadIdx.x >> 6, lane = threadIdx.x & 63;
-    const int b = blockIdx.x, h = wave & 3, role = wave >> 2;        // two wavefronts per head: they split the query tiles
-    const int S_pad = (S + 31) & ~31;
-    // per head: K [S_pad][8] bf16, then V^T [8][S_pad] bf16
-    short *Ks = reinterpret_cast<short *>(smem) + (size_t)h * 2 * S_pad * D;
-    short *Vt = Ks + (size_t)S_pad * D;
-    const short *base = reinterpret_cast<const short *>(qkv);
-    // elements between consecutive sequence positions: sequence-major [S][B][.] (nn.MultiheadAttention's batch_first=False) or
-    // batch-major [B][S][.] (bm: a sample's rows are one contiguous 192 S bytes)
-    const size_t row_stride = bm ? (size_t)3 * E : (size_t)B * 3 * E;
-    const size_t head_off = (size_t)b * 3 * E * (bm ? S : 1) + (size_t)h * D;
-    const size_t out_row = bm ? (size_t)E : (size_t)B * E, out_off = (size_t)b * E * (bm ? S : 1) + (size_t)h * D;
-    for (int s = lane + 64 * role; s < S_pad; s += 128) {
-        uint4 kv = make_uint4(0, 0, 0, 0), vv = make_uint4(0, 0, 0, 0);
-        if (s < S) {
-            kv = *reinterpret_cast<const uint4 *>(base + (size_t)s * row_stride + head_off + E);
-            vv = *reinterpret_cast<const uint4 *>(base + (size_t)s * row_stride + head_off + 2 * E);
-        }
-        *reinterpret_cast<uint4 *>(Ks + (size_t)s * D) = kv;
-        const short *vs = reinterpret_cast<const short *>(&vv);
-#pragma unroll
-        for (int d = 0; d < D; ++d) Vt[(size_t)d * S_pad + s] = vs[d];
-    }
-    __syncthreads();
-
-    const int g = lane >> 4, c = lane & 15;
-    const pmx_bf16x8 zero8 = { 0, 0, 0, 0, 0, 0, 0, 0 };
-    const int n_qt = (S + 15) >> 4, n_kp = S_pad >> 5;
-    for (int qt = role; qt < n_qt; qt += 2) {
-        const int q_row = qt * 16 + c;
-        pmx_bf16x8 qf = zero8;
-        if (g == 0 && q_row < S) qf = *reinterpret_cast<const pmx_bf16x8 *>(base + (size_t)q_row * row_stride + head_off);
-        // Scores stay in the raw (unscaled) domain; c2 = scale * log2(e) turns them into base-2 exponents with ONE fma per
-        // element (exp2(s * c2 - m)), the running maximum m and the stored log-sum-exp are kept in that base-2 domain.
-        float m = -1e30f, l = 0.f;
-        pmx_f32x4 o = { 0.f, 0.f, 0.f, 0.f };
-        const float c2 = scale * 1.44269504088896341f;
-        auto tile = [&](int kp, bool last) {
-            pmx_bf16x8 k0 = zero8, k1 = zero8;
-            if (g == 0) {
-                k0 = *reinterpret_cast<const pmx_bf16x8 *>(Ks + (size_t)(kp * 32 + c) * D);
-                k1 = *reinterpret_cast<const pmx_bf16x8 *>(Ks + (size_t)(kp * 32 + 16 + c) * D);
-            }
-            const pmx_f32x4 z4 = { 0.f, 0.f, 0.f, 0.f };
-            pmx_f32x4 s0 = __builtin_amdgcn_mfma_f32_16x16x32_bf16(k0, qf, z4, 0, 0, 0);
-            pmx_f32x4 s1 = __builtin_amdgcn_mfma_f32_16x16x32_bf16(k1, qf, z4, 0, 0, 0);
-            float p[8];
-#pragma unroll
-            for (int r = 0; r < 4; ++r) { p[r] = s0[r]; p[4 + r] = s1[r]; }
-            if (last) {   // only the last key pair can hold padded keys: they must not enter the row sum
-#pragma unroll
-                for (int r = 0; r < 4; ++r) {
-                    const int key0 = kp * 32 + g * 4 + r, key1 = key0 + 16;
-                    if (key0 >= S) p[r] = -1e30f;
-                    if (key1 >= S) p[4 + r] = -1e30f;
-                }
-            }
-            float mloc = fmaxf(fmaxf(fmaxf(p[0], p[1]), fmaxf(p[2], p[3])), fmaxf(fmaxf(p[4], p[5]), fmaxf(p[6], p[7])));
-            mloc = fmaxf(mloc, __shfl_xor(mloc, 16));
-            mloc = fmaxf(mloc, __shfl_xor(mloc, 32));
-            const float mnew = fmaxf(m, mloc * c2);
-            const float alpha = __builtin_amdgcn_exp2f(m - mnew);
-            float lsum = 0.f;
-            pmx_bf16x8 pf;
-#pragma unroll
-            for (int r = 0; r < 8; ++r) {
-                const float e = __builtin_amdgcn_exp2f(__builtin_fmaf(p[r], c2, -mnew));
-                lsum += e;
-                pf[r] = pmx_f2bf(e);
-            }
-            lsum += __shfl_xor(lsum, 16);
-            lsum += __shfl_xor(lsum, 32);
-            l = l * alpha + lsum;
-            m = mnew;
-#pragma unroll
-            for (int r = 0; r < 4; ++r) o[r] *= alpha;
-            // A = V^T: row d = c (zero for d >= 8), k-slot j -> key kp*32 + 4g + j (j < 4), kp*32 + 16 + 4g + (j-4)
-            pmx_bf16x8 vf = zero8;
-            if (c < D) {
-                const short *vrow = Vt + (size_t)c * S_pad + kp * 32 + g * 4;
-                const uint2 lo = *reinterpret_cast<const uint2 *>(vrow);
-                const uint2 hi = *reinterpret_cast<const uint2 *>(vrow + 16);
-                const uint4 both = make_uint4(lo.x, lo.y, hi.x, hi.y);
-                vf = *reinterpret_cast<const pmx_bf16x8 *>(&both);
-            }
-            o = __builtin_amdgcn_mfma_f32_16x16x32_bf16(vf, pf, o, 0, 0, 0);
-        };
-        for (int kp = 0; kp < n_kp - 1; ++kp) tile(kp, false);
-        tile(n_kp - 1, true);
-        // O^T[d = 4g + r][query c]: lanes of groups 0 and 1 hold d = 0..3 and 4..7
-        if (q_row < S) {
-            const float inv = 1.0f / l;
-            if (g < 2) {
-                short w4[4];
-#pragma unroll
-                for (int r = 0; r < 4; ++r) w4[r] = pmx_f2bf(o[r] * inv);
-                *reinterpret_cast<uint2 *>(reinterpret_cast<short *>(out) + (size_t)q_row * out_row + out_off + g * 4) =
-                    *reinterpret_cast<const uint2 *>(w4);
-            }
-            if (g == 0 && lse) lse[((size_t)b * HEADS + h) * S + q_row] = (m + __log2f(l)) * 0.69314718055994531f;   // back to the natural log
-        }
-    }
 }
 
 // squared norm of eight bf16 values (one head's row of Q or K)
@@ -736,9 +626,8 @@ __device__ __forceinline__ float sq_norm8(uint4 w)
 }
 
 // ---------------------------------------------------------------------------------------------------------------
-// The forward kernel the product launches (pmx_attn8_fwd_kernel above is kept as the PMX_ATTN_FWD_V1 A/B reference).  The
-// kernel is bound by the vector ALU work of the softmax, so this version removes everything from the inner loop that is not
-// the exponential itself:
+// The forward kernel.  It is bound by the vector ALU work of the softmax, so its inner loop holds nothing that is not the
+// exponential itself:
 //   * The exponent's reference is FIXED before the loop over the keys: no running maximum, no rescaling of the output tile, no
 //     cross-lane traffic inside the loop.  It enters as the initial accumulator of the score product (s - m comes out of the
 //     matrix instruction), leaving exp2((s - m) c) = one multiply and one v_exp_f32 per score.  The reference is the
@@ -754,7 +643,8 @@ __device__ __forceinline__ float sq_norm8(uint4 w)
 //     dominates would carry that key's bf16 rounding (up to 2^-9) into every probability the backward recomputes.
 //   * Operands need no masks: lane groups 1..3 of an A operand fill k-slots 8..31, which meet the zeros of the B operand (the
 //     query row lives in group 0 only), so every lane simply reads its row (the four groups read the same 256 bytes: a broadcast).
-// Per 32 keys and lane: 8 multiplies, 8 exponentials, 4 packed conversions (the first kernel: ~75 vector instructions).
+// Per 32 keys and lane: 8 multiplies, 8 exponentials, 4 packed conversions (the first, online-softmax kernel: ~75 vector
+// instructions).
 // ---------------------------------------------------------------------------------------------------------------
 __global__ __launch_bounds__(512) void pmx_attn8_fwd2_kernel(const __hip_bfloat16 *__restrict__ qkv, __hip_bfloat16 *__restrict__ out,
                                                              float *__restrict__ lse, int S, int B, float scale, int bm)
@@ -925,35 +815,21 @@ extern "C" int pmx_attn8_forward_layout(const void *qkv_dev, void *out_dev, floa
     const int S_pad = (S + 31) & ~31;
     int cur_dev = 0;
     if (hipGetDevice(&cur_dev) != hipSuccess || cur_dev < 0 || cur_dev >= 64) return PMX_ERR_HIP;
-    static const bool v1 = getenv("PMX_ATTN_FWD_V1") != nullptr;                    // A/B switch, read once
-    if (!v1) {
-        const size_t lds2 = (size_t)4 * (8 + 9) * S_pad * sizeof(short) + 16 * sizeof(float);
-        static bool attr2_dev[64] = {};
-        if (lds2 > 65536 && !attr2_dev[cur_dev]) {
-            if (hipFuncSetAttribute(reinterpret_cast<const void *>(pmx_attn8_fwd2_kernel), hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024) != hipSuccess)
-                return PMX_ERR_HIP;
-            attr2_dev[cur_dev] = true;
-        }
-        hipLaunchKernelGGL(pmx_attn8_fwd2_kernel, dim3(B), dim3(512), lds2, st, (const __hip_bfloat16 *)qkv_dev, (__hip_bfloat16 *)out_dev, lse_dev, S, B,
-                           0.35355339059327379f /* 1/sqrt(8) */, batch_major ? 1 : 0);
-        return hipGetLastError() == hipSuccess ? PMX_OK : PMX_ERR_HIP;
-    }
-    const size_t lds = (size_t)4 * 2 * S_pad * 8 * sizeof(short);
+    const size_t lds = (size_t)4 * (8 + 9) * S_pad * sizeof(short) + 16 * sizeof(float);
     static bool attr_set_dev[64] = {};          // the attribute belongs to the function ON THE CURRENT DEVICE
-    bool &attr_set = attr_set_dev[cur_dev];
-    if (lds > 65536 && !attr_set) {
-        if (hipFuncSetAttribute(reinterpret_cast<const void *>(pmx_attn8_fwd_kernel), hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024) != hipSuccess)
+    if (lds > 65536 && !attr_set_dev[cur_dev]) {
+        if (hipFuncSetAttribute(reinterpret_cast<const void *>(pmx_attn8_fwd2_kernel), hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024) != hipSuccess)
             return PMX_ERR_HIP;
-        attr_set = true;
+        attr_set_dev[cur_dev] = true;
     }
-    hipLaunchKernelGGL(pmx_attn8_fwd_kernel, dim3(B), dim3(512), lds, st, (const __hip_bfloat16 *)qkv_dev, (__hip_bfloat16 *)out_dev, lse_dev, S, B,
+    hipLaunchKernelGGL(pmx_attn8_fwd2_kernel, dim3(B), dim3(512), lds, st, (const __hip_bfloat16 *)qkv_dev, (__hip_bfloat16 *)out_dev, lse_dev, S, B,
                        0.35355339059327379f /* 1/sqrt(8) */, batch_major ? 1 : 0);
     return hipGetLastError() == hipSuccess ? PMX_OK : PMX_ERR_HIP;
 }
 
 
 // ---------------------------------------------------------------------------------------------------------------
-// Backward of the small-sequence attention (same shapes as pmx_attn8_fwd_kernel), recomputing the probabilities from
+// Backward of the small-sequence attention (same shapes as pmx_attn8_fwd2_kernel), recomputing the probabilities from
 // the saved log-sum-exp.  One wavefront per (sample, head), two passes, every product on v_mfma_f32_16x16x32_bf16:
 //   pass A (per 16-query tile, lanes = queries):  S^T, dP^T tiles over key pairs -> dS^T = P^T o (dP^T - Delta_q)
 //                                                 dQ^T += K^T . dS^T          (the accumulators are the B fragment)
@@ -963,10 +839,6 @@ extern "C" int pmx_attn8_forward_layout(const void *qkv_dev, void *out_dev, floa
 // the row-major operands of the score products are read straight from global memory (16 bytes per lane, L1-resident).
 // Gradients are written in the packed [S][B][96] layout of the in-projection output.
 // ---------------------------------------------------------------------------------------------------------------
-// NPF > 0: the sequence has exactly NPF pairs of 16-row tiles and each wave keeps ITS row operands (K and V rows for the dQ
-// pass, Q and dO rows for the dK/dV pass) in registers for all of its tiles instead of re-reading them from global memory
-// once per tile (10x for S = 154): 16 NPF registers, loaded once.
-template <int NPF>
 __global__ __launch_bounds__(512) void pmx_attn8_bwd_kernel(const __hip_bfloat16 *__restrict__ qkv, const __hip_bfloat16 *__restrict__ outp,
                                                             const __hip_bfloat16 *__restrict__ dout, const float *__restrict__ lse,
                                                             __hip_bfloat16 *__restrict__ dqkv, int S, int B, float scale, int bm)
@@ -1037,44 +909,7 @@ __global__ __launch_bounds__(512) void pmx_attn8_bwd_kernel(const __hip_bfloat16
     };
 
     // ---- pass A: dQ
-    if (NPF > 0 && role == 0) {
-        pmx_bf16x8 kr[NPF > 0 ? 2 * NPF : 1], vr[NPF > 0 ? 2 * NPF : 1];
-#pragma unroll
-        for (int t = 0; t < 2 * NPF; ++t) {
-            kr[t] = row8(base, row_stride, head_off + E, t * 16 + c);
-            vr[t] = row8(base, row_stride, head_off + 2 * E, t * 16 + c);
-        }
-        for (int qt = 0; qt < n_t; ++qt) {
-            const int q_row = qt * 16 + c;
-            const pmx_bf16x8 qf = row8(base, row_stride, head_off, q_row);
-            const pmx_bf16x8 dof = row8(dobase, orow, ohead, q_row);
-            const float ls = fmaxf(lse_s[q_row < S_pad ? q_row : 0], -120.f), dl = delta_s[q_row < S_pad ? q_row : 0];
-            pmx_f32x4 dq = z4;
-#pragma unroll
-            for (int kp = 0; kp < NPF; ++kp) {
-                const pmx_f32x4 s0 = __builtin_amdgcn_mfma_f32_16x16x32_bf16(kr[2 * kp], qf, z4, 0, 0, 0);
-                const pmx_f32x4 s1 = __builtin_amdgcn_mfma_f32_16x16x32_bf16(kr[2 * kp + 1], qf, z4, 0, 0, 0);
-                const pmx_f32x4 p0 = __builtin_amdgcn_mfma_f32_16x16x32_bf16(vr[2 * kp], dof, z4, 0, 0, 0);
-                const pmx_f32x4 p1 = __builtin_amdgcn_mfma_f32_16x16x32_bf16(vr[2 * kp + 1], dof, z4, 0, 0, 0);
-                pmx_bf16x8 dsf;
-#pragma unroll
-                for (int r = 0; r < 4; ++r) {
-                    const float e0 = __builtin_amdgcn_exp2f(__builtin_fmaf(s0[r], c2, -ls));
-                    const float e1 = __builtin_amdgcn_exp2f(__builtin_fmaf(s1[r], c2, -ls));
-                    dsf[r] = pmx_f2bf(e0 * (p0[r] - dl));
-                    dsf[4 + r] = pmx_f2bf(e1 * (p1[r] - dl));
-                }
-                dq = __builtin_amdgcn_mfma_f32_16x16x32_bf16(tfrag(Kt, kp), dsf, dq, 0, 0, 0);
-            }
-            if (q_row < S && g < 2) {
-                short w4[4];
-#pragma unroll
-                for (int r = 0; r < 4; ++r) w4[r] = pmx_f2bf(dq[r] * scale);
-                *reinterpret_cast<uint2 *>(dbase + (size_t)q_row * row_stride + head_off + g * 4) = *reinterpret_cast<const uint2 *>(w4);
-            }
-        }
-    }
-    if (NPF == 0 && role == 0)
+    if (role == 0)
     for (int qt = 0; qt < n_t; ++qt) {
         const int q_row = qt * 16 + c;
         const pmx_bf16x8 qf = row8(base, row_stride, head_off, q_row);
@@ -1115,47 +950,7 @@ __global__ __launch_bounds__(512) void pmx_attn8_bwd_kernel(const __hip_bfloat16
         }
     }
     // ---- pass B: dK, dV
-    if (NPF > 0 && role == 1) {
-        pmx_bf16x8 qr[NPF > 0 ? 2 * NPF : 1], dr[NPF > 0 ? 2 * NPF : 1];
-#pragma unroll
-        for (int t = 0; t < 2 * NPF; ++t) {
-            qr[t] = row8(base, row_stride, head_off, t * 16 + c);
-            dr[t] = row8(dobase, orow, ohead, t * 16 + c);
-        }
-        for (int kt = 0; kt < n_t; ++kt) {
-            const int k_row = kt * 16 + c;
-            const pmx_bf16x8 kf = row8(base, row_stride, head_off + E, k_row);
-            const pmx_bf16x8 vf = row8(base, row_stride, head_off + 2 * E, k_row);
-            pmx_f32x4 dk = z4, dv = z4;
-#pragma unroll
-            for (int qp = 0; qp < NPF; ++qp) {
-                const pmx_f32x4 s0 = __builtin_amdgcn_mfma_f32_16x16x32_bf16(qr[2 * qp], kf, z4, 0, 0, 0);
-                const pmx_f32x4 s1 = __builtin_amdgcn_mfma_f32_16x16x32_bf16(qr[2 * qp + 1], kf, z4, 0, 0, 0);
-                const pmx_f32x4 p0 = __builtin_amdgcn_mfma_f32_16x16x32_bf16(dr[2 * qp], vf, z4, 0, 0, 0);
-                const pmx_f32x4 p1 = __builtin_amdgcn_mfma_f32_16x16x32_bf16(dr[2 * qp + 1], vf, z4, 0, 0, 0);
-                pmx_bf16x8 pf, dsf;
-#pragma unroll
-                for (int r = 0; r < 4; ++r) {
-                    const int qa = qp * 32 + g * 4 + r, qb = qa + 16;
-                    const float e0 = __builtin_amdgcn_exp2f(__builtin_fmaf(s0[r], c2, -lse_s[qa]));
-                    const float e1 = __builtin_amdgcn_exp2f(__builtin_fmaf(s1[r], c2, -lse_s[qb]));
-                    pf[r] = pmx_f2bf(e0); pf[4 + r] = pmx_f2bf(e1);
-                    dsf[r] = pmx_f2bf(e0 * (p0[r] - delta_s[qa]));
-                    dsf[4 + r] = pmx_f2bf(e1 * (p1[r] - delta_s[qb]));
-                }
-                dv = __builtin_amdgcn_mfma_f32_16x16x32_bf16(tfrag(dOt, qp), pf, dv, 0, 0, 0);
-                dk = __builtin_amdgcn_mfma_f32_16x16x32_bf16(tfrag(Qt, qp), dsf, dk, 0, 0, 0);
-            }
-            if (k_row < S && g < 2) {
-                short wk[4], wv[4];
-#pragma unroll
-                for (int r = 0; r < 4; ++r) { wk[r] = pmx_f2bf(dk[r] * scale); wv[r] = pmx_f2bf(dv[r]); }
-                *reinterpret_cast<uint2 *>(dbase + (size_t)k_row * row_stride + head_off + E + g * 4) = *reinterpret_cast<const uint2 *>(wk);
-                *reinterpret_cast<uint2 *>(dbase + (size_t)k_row * row_stride + head_off + 2 * E + g * 4) = *reinterpret_cast<const uint2 *>(wv);
-            }
-        }
-    }
-    if (NPF == 0 && role == 1)
+    if (role == 1)
     for (int kt = 0; kt < n_t; ++kt) {
         const int k_row = kt * 16 + c;
         const pmx_bf16x8 kf = row8(base, row_stride, head_off + E, k_row);
@@ -1463,20 +1258,18 @@ extern "C" int pmx_attn8_backward_layout(const void *qkv_dev, const void *out_de
     if (hipGetDevice(&cur_dev) != hipSuccess || cur_dev < 0 || cur_dev >= 64) return PMX_ERR_HIP;
     bool &attr_set = attr_set_dev[cur_dev];
     if (lds > 65536 && !attr_set) {
-        if (hipFuncSetAttribute(reinterpret_cast<const void *>(pmx_attn8_bwd_kernel<0>), hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024) != hipSuccess)
+        if (hipFuncSetAttribute(reinterpret_cast<const void *>(pmx_attn8_bwd_kernel), hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024) != hipSuccess)
             return PMX_ERR_HIP;
         attr_set = true;
     }
-    static const bool generic_only = getenv("PMX_ATTN_BWD_GENERIC") != nullptr;      // A/B switch, read once
-    static const bool two_pass = getenv("PMX_ATTN_BWD_TWO_PASS") != nullptr;         // A/B switch, read once
-    if (S_pad == 160 && !generic_only && !two_pass) {
+    if (S_pad == 160) {
         // one pass, one wavefront per (sample, head): 4 x (3 x 8 x 160 x 2 + 2 x 160 x 4 + 32 x 80) = 45 KB of LDS
         constexpr size_t lds_f = (size_t)4 * ((size_t)3 * 8 * 160 * sizeof(short) + (size_t)2 * 160 * sizeof(float) + 32 * 80);
         hipLaunchKernelGGL((pmx_attn8_bwd_fused_kernel<5, 1>), dim3(B), dim3(256), lds_f, st, (const __hip_bfloat16 *)qkv_dev, (const __hip_bfloat16 *)out_dev,
                            (const __hip_bfloat16 *)dout_dev, lse_dev, (__hip_bfloat16 *)dqkv_dev, S, B, 0.35355339059327379f, batch_major ? 1 : 0);
         return hipGetLastError() == hipSuccess ? PMX_OK : PMX_ERR_HIP;
     }
-    if (S_pad == 416 && !generic_only && !two_pass) {
+    if (S_pad == 416) {
         // one pass, two wavefronts per (sample, head) splitting the query pairs (the 20 x 20 boards: 400 tokens):
         // 4 x (4 x 8 x 416 x 2 + 2 x 416 x 4 + 2 x 32 x 80 + 2 x 1 024) = 145 KB of LDS, one block of eight waves per CU
         constexpr size_t lds_f = (size_t)4 * ((size_t)4 * 8 * 416 * sizeof(short) + (size_t)2 * 416 * sizeof(float) + 2 * 32 * 80 + 2 * 1024);
@@ -1490,12 +1283,8 @@ extern "C" int pmx_attn8_backward_layout(const void *qkv_dev, const void *out_de
                            (const __hip_bfloat16 *)dout_dev, lse_dev, (__hip_bfloat16 *)dqkv_dev, S, B, 0.35355339059327379f, batch_major ? 1 : 0);
         return hipGetLastError() == hipSuccess ? PMX_OK : PMX_ERR_HIP;
     }
-    if (S_pad == 160 && !generic_only)       // tinyCapture and smallCapture (154 cells): the row operands of a wave fit in 80 registers
-        hipLaunchKernelGGL(pmx_attn8_bwd_kernel<5>, dim3(B), dim3(512), lds, st, (const __hip_bfloat16 *)qkv_dev, (const __hip_bfloat16 *)out_dev,
-                           (const __hip_bfloat16 *)dout_dev, lse_dev, (__hip_bfloat16 *)dqkv_dev, S, B, 0.35355339059327379f, batch_major ? 1 : 0);
-    else
-        hipLaunchKernelGGL(pmx_attn8_bwd_kernel<0>, dim3(B), dim3(512), lds, st, (const __hip_bfloat16 *)qkv_dev, (const __hip_bfloat16 *)out_dev,
-                           (const __hip_bfloat16 *)dout_dev, lse_dev, (__hip_bfloat16 *)dqkv_dev, S, B, 0.35355339059327379f, batch_major ? 1 : 0);
+    hipLaunchKernelGGL(pmx_attn8_bwd_kernel, dim3(B), dim3(512), lds, st, (const __hip_bfloat16 *)qkv_dev, (const __hip_bfloat16 *)out_dev,
+                       (const __hip_bfloat16 *)dout_dev, lse_dev, (__hip_bfloat16 *)dqkv_dev, S, B, 0.35355339059327379f, batch_major ? 1 : 0);
     return hipGetLastError() == hipSuccess ? PMX_OK : PMX_ERR_HIP;
 }
 

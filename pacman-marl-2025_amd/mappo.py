@@ -345,7 +345,7 @@ class _OutProjAddLN(torch.autograd.Function):
 
 
 def _fused_tokens_ok(x, *weights):
-    return (MAPPOAgent.fused_ffn and x.is_cuda and x.dtype == torch.bfloat16 and x.shape[-1] == 32
+    return (x.is_cuda and x.dtype == torch.bfloat16 and x.shape[-1] == 32
             and all(w.dtype == torch.float32 for w in weights))
 
 
@@ -372,7 +372,7 @@ def ffn_layer_norm(x, lin1, lin2, ln, pack=None):
     """The feed-forward half of the post-LN encoder layer: the fused HIP kernels for bf16 tokens of width 32 with a 128-wide
     hidden layer on the GPU, the separate ops otherwise."""
     if (x.is_cuda and x.dtype == torch.bfloat16 and x.shape[-1] == 32 and tuple(lin1.weight.shape) == (128, 32)
-            and tuple(lin2.weight.shape) == (32, 128) and lin1.weight.dtype == torch.float32 and MAPPOAgent.fused_ffn):
+            and tuple(lin2.weight.shape) == (32, 128) and lin1.weight.dtype == torch.float32):
         return _FFNLayerNorm.apply(x, lin1.weight, lin1.bias, lin2.weight, lin2.bias, ln.weight, ln.bias, ln.eps, pack)
     f = token_linear(F.relu(token_linear(x, lin1.weight, lin1.bias)), lin2.weight, lin2.bias)
     return add_layer_norm_small(x, f, ln)
@@ -439,15 +439,14 @@ class _Projector(torch.autograd.Function):
     (csrc/pmx_actor.hip): the observation planes are read as they are (bytes), no cast, no layout copy, no library convolution."""
 
     @staticmethod
-    def forward(ctx, obs, w, b, pe, pack=None):
+    def forward(ctx, obs, w, b, pe):
         import ctypes as C
         from . import _lib
         from .actor_tower import _OBS_CODE
         lib = _lib.load()
         obs = obs.contiguous()
         B, _, H, W = obs.shape
-        if pack is None:
-            pack = pack_projector(w, b)
+        pack = pack_projector(w, b)
         tok = torch.empty(B, H * W, 32, dtype=torch.bfloat16, device=obs.device)
         st = C.c_void_p(torch.cuda.current_stream(obs.device).cuda_stream)
         _lib.check(lib.pmx_proj_forward(obs.data_ptr(), _OBS_CODE[obs.dtype], pack.data_ptr(), pe.data_ptr(), tok.data_ptr(), B, H, W, st),
@@ -472,7 +471,7 @@ class _Projector(torch.autograd.Function):
         st = C.c_void_p(torch.cuda.current_stream(dev).cuda_stream)
         _lib.check(lib.pmx_proj_backward(obs.data_ptr(), _OBS_CODE[obs.dtype], dtok.data_ptr(), part.data_ptr(), dw.data_ptr(), db.data_ptr(),
                                          B, H, W, st), "pmx_proj_backward")
-        return None, dw.to(ctx.dtypes[0]), db.to(ctx.dtypes[1]), None, None
+        return None, dw.to(ctx.dtypes[0]), db.to(ctx.dtypes[1]), None
 
 
 class _ActorTail(torch.autograd.Function):
@@ -567,9 +566,6 @@ def column_sums(t):
     return t.sum(dim=tuple(range(t.dim() - 1)), dtype=torch.float32)
 
 
-_DEBUG_KEEP = None    # tools/graph_debug.py: keeps (grad_out, bias_grad, weight_grad) of every token_linear backward alive
-
-
 class _TokenLinear(torch.autograd.Function):
     """F.linear on a token tensor [S, B, in] with the weight gradient computed as S batched GEMMs of depth B followed by
     a sum over S.  hipBLASLt's choice for the flat [S*B, in]^T x [S*B, out] product (K = 630 k rows, a 32 x 128 result)
@@ -586,8 +582,6 @@ class _TokenLinear(torch.autograd.Function):
         gx = gy.matmul(weight.to(gy.dtype)) if ctx.needs_input_grad[0] else None
         gw = torch.bmm(gy.transpose(1, 2), x.to(gy.dtype)).sum(0).to(weight.dtype) if ctx.needs_input_grad[1] else None
         gb = column_sums(gy).to(weight.dtype) if ctx.needs_input_grad[2] else None
-        if _DEBUG_KEEP is not None:
-            _DEBUG_KEEP.append((gy, gb, gw))
         return gx, gw, gb
 
 
@@ -796,7 +790,6 @@ class MAPPOAgent(nn.Module):
             if m.bias is not None:
                 m.bias.data.fill_(0.0)
 
-    fused_ffn = True        # use the fused feed-forward + LayerNorm kernels of the critic's encoder layers (bf16 on the GPU)
     fused_tower = True      # use the fused actor-tower kernels where they apply (bf16 on the GPU, supported board size)
     batch_major_critic = True   # run the critic channels-last / batch-major under bf16 autocast on the GPU (no transposing copies)
     fused_loss = True       # the PPO objective and its gradient w.r.t. logits / values as one kernel on the GPU (pmx_ppo_loss)
@@ -804,7 +797,6 @@ class MAPPOAgent(nn.Module):
                             # (VecMAPPOTrainer.rollout); None = pack on every call
 
     fused_heads = True      # the small ends of the two heads as one kernel each way under bf16 autocast (csrc/pmx_heads.hip)
-    two_streams = True      # optimizer step on the GPU: the critic's forward and backward on a side stream, beside the actor's
 
     def _fused_heads_ok(self, t):
         """The head-tail kernels take bfloat16 activations under bf16 autocast on the GPU and float32 master weights of the
@@ -852,7 +844,6 @@ class MAPPOAgent(nn.Module):
         return self.actor_head(self.actor_backbone(obs))
 
     fused_projector = True  # the critic's projector + positional table as one kernel under bf16 autocast (pmx_proj_forward)
-    prepack = True          # the encoder layers' parameter packs in one launch at the top of value() instead of one in front of each use
 
     def _pe_table(self, H, W, dev):
         """The positional table [H*W, 32] float32 on `dev`, built once per board size."""
@@ -874,7 +865,7 @@ class MAPPOAgent(nn.Module):
     def value(self, merged_obs):
         """merged_obs [B,8,H,W] -> [B] (pacman_mappo_resnet.py:160-170)"""
         layers = self.critic_transformer.layers
-        bm = (self.batch_major_critic and merged_obs.is_cuda and torch.is_autocast_enabled() and self.fused_ffn
+        bm = (self.batch_major_critic and merged_obs.is_cuda and torch.is_autocast_enabled()
               and torch.get_autocast_dtype("cuda") == torch.bfloat16
               and layers[0].fused_ok(merged_obs.new_empty(0, dtype=torch.bfloat16), merged_obs.shape[2] * merged_obs.shape[3]))
         if bm:
@@ -883,16 +874,15 @@ class MAPPOAgent(nn.Module):
             B, _, H, W = merged_obs.shape
             # every parameter pack of the encoder layers in one launch (they depend on nothing but the weights; six small launches sat in
             # front of the six kernels that read them).  (Making them on a side stream instead crashes hipStreamEndCapture when that
-            # stream forks from the critic's side stream -- a fork inside a fork -- on ROCm 7.0: tools/r03_iso.sh.)
+            # stream forks from the critic's side stream -- a fork inside a fork -- on ROCm 7.0.)
             dev = merged_obs.device
             layer_tuple = tuple(layers)
             all_f32 = all(p.dtype == torch.float32 for l in layer_tuple for p in l.parameters()) and len(layer_tuple) <= 4
             fused_proj = self._fused_projector_ok(merged_obs)
-            lpacks = encoder_packs(layer_tuple) if (all_f32 and self.prepack) else None
-            ppack = None
+            lpacks = encoder_packs(layer_tuple) if all_f32 else None
             if fused_proj:
                 conv = self.critic_projector[0]
-                x = _Projector.apply(merged_obs, conv.weight, conv.bias, self._pe_table(H, W, dev), ppack)
+                x = _Projector.apply(merged_obs, conv.weight, conv.bias, self._pe_table(H, W, dev))
             else:
                 if merged_obs.dtype == torch.uint8:
                     merged_obs = merged_obs.to(torch.bfloat16)
@@ -1032,21 +1022,18 @@ def _fused_loss_ok(model, obs, act, old_logp, adv, ret):
 def ppo_loss(model, obs, merged, act, old_logp, adv, ret, clip_eps, ent_coef, vf_coef=VF_COEF):
     """The minibatch objective of pacman_mappo_resnet.py:571-585.  Returns (loss, dict of detached scalars)."""
     if _fused_loss_ok(model, obs, act, old_logp, adv, ret):
-        if MAPPOAgent.two_streams:
-            # The actor and the critic share nothing until the loss: the critic's forward runs on a side stream, so autograd
-            # runs its backward there too (a node's backward uses its forward's stream) and the two halves of the step overlap.
-            # At the reference's minibatch of 512 most kernels fill a fraction of the chip and the replayed step was one serial
-            # chain of ~80 small launches; in the captured graph the two chains become parallel branches.
-            cur = torch.cuda.current_stream(obs.device)
-            side = _side_stream(obs.device)
-            side.wait_stream(cur)
-            with torch.cuda.stream(side):
-                vals = model.value(merged).float()
-            logits = model.logits(obs)
-            cur.wait_stream(side)
-            vals.record_stream(cur)
-        else:
-            logits, vals = model.logits(obs), model.value(merged).float()
+        # The actor and the critic share nothing until the loss: the critic's forward runs on a side stream, so autograd
+        # runs its backward there too (a node's backward uses its forward's stream) and the two halves of the step overlap.
+        # At the reference's minibatch of 512 most kernels fill a fraction of the chip and the replayed step was one serial
+        # chain of ~80 small launches; in the captured graph the two chains become parallel branches.
+        cur = torch.cuda.current_stream(obs.device)
+        side = _side_stream(obs.device)
+        side.wait_stream(cur)
+        with torch.cuda.stream(side):
+            vals = model.value(merged).float()
+        logits = model.logits(obs)
+        cur.wait_stream(side)
+        vals.record_stream(cur)
         if logits.dtype not in (torch.float32, torch.bfloat16):
             logits = logits.float()
         stats = _PPOLossFn.apply(logits, vals, act, old_logp, adv, ret, clip_eps, ent_coef, vf_coef)
@@ -1071,15 +1058,6 @@ def ppo_loss(model, obs, merged, act, old_logp, adv, ret, clip_eps, ent_coef, vf
         clip_frac = ((ratio - 1).abs() > clip_eps).float().mean()
     return loss, {"pg": pg.detach(), "vl": vl.detach(), "entropy": ent_mean.detach(), "clip_frac": clip_frac,
                   "loss": loss.detach()}
-
-
-import os as _os
-if _os.environ.get("PMX_NO_PREPACK"):
-    MAPPOAgent.prepack = False
-if _os.environ.get("PMX_NO_FUSED_PROJECTOR"):
-    MAPPOAgent.fused_projector = False
-if _os.environ.get("PMX_NO_TWO_STREAMS"):
-    MAPPOAgent.two_streams = False
 
 
 class FlatBucket:
@@ -1152,18 +1130,16 @@ class PPOLearner:
 
     # the second-stage row sums of the gradient reductions folded into the gradient gather (mappo._row_sums_deferred): eight small
     # launches less on the chains of the 512-sample step.  (A first version ran them on a third stream beside the next backward kernel
-    # and LOST -- 1 380 against 1 995 steps/s: six fork / join pairs cost the captured graph more than the kernels cost the chain,
-    # tools/r03_iso2.sh.)  PMX_NO_DEFER_SUMS=1 restores a kernel per reduction.
-    defer_row_sums = not _os.environ.get("PMX_NO_DEFER_SUMS")
-    overlap_allreduce = True   # data parallel: reduce the actor's gradient slice while the critic's backward runs
-    graph_overlap_allreduce = False   # ... also in the hipGraph-replayed step (one graph per gradient group); see capture()
+    # and LOST -- 1 380 against 1 995 steps/s: six fork / join pairs cost the captured graph more than the kernels cost the chain.)
+    defer_row_sums = True
 
     def _grad_groups(self):
         """Index ranges [lo, hi) into bucket.params whose gradients are produced -- and, under data parallelism, reduced --
         together, in the order the backward pass is run: the actor's parameters (a contiguous prefix of the bucket that holds
-        97 % of its bytes: the 4928 -> 512 head), then the critic's.  One range when nothing is exchanged."""
+        97 % of its bytes: the 4928 -> 512 head), then the critic's.  Data parallel, the actor's slice is reduced while the critic's
+        backward runs.  One range when nothing is exchanged."""
         n = len(self.bucket.params)
-        if not (self.dp and self.overlap_allreduce and self._w16 is None):
+        if not (self.dp and self._w16 is None):
             return [(0, n)]
         if getattr(self, "_groups", None) is None:
             names = [k for k, p in self.model.named_parameters() if p.requires_grad]
@@ -1462,19 +1438,14 @@ class PPOLearner:
                 self._g_acc.add_(torch.stack([stats[k].float() for k in self._g_acc_keys]))
             return stats
 
-        # Data parallel: the collectives stay OUTSIDE the graphs (eager RCCL calls, exactly the ones the eager step issues), so
-        # the step is recorded as one graph per gradient group plus one for the optimizer tail (with graph_overlap_allreduce):
-        #   graph 0: forward, loss, backward of group 0 (the actor), its gradients into the bucket   | all-reduce of slice 0 starts
-        #   graph 1: backward of group 1 (the critic), its gradients into the bucket                 | ... overlaps this graph
-        #   graph 2: clip, Adam, EMA, weight copies, reports                                          | after both all-reduces
-        # The autograd graph built while graph 0 is recorded is walked again while graph 1 is recorded; all graphs share one
-        # memory pool, so what graph 0 saved for the backward pass stays where graph 1's kernels read it.
-        # Replayed steps are the launch-bound ones (small minibatches): there the actor's and the critic's backward run side by side on
-        # two streams inside one graph, which buys more than reducing the actor's slice early would (1 800 against 1 300 steps/s at 512
-        # samples on one GPU), so the replayed data-parallel step is [forward + whole backward] -> ONE all-reduce -> [optimizer tail].
-        # graph_overlap_allreduce = True restores one graph per gradient group (the eager step always reduces slice by slice).
-        groups = self._grad_groups() if (self._w16 is None and self.graph_overlap_allreduce) else [(0, len(self.bucket.params))]
-        segmented = self.dp
+        # Data parallel: the collectives stay OUTSIDE the graphs (eager RCCL calls), so the step is recorded as two graphs:
+        #   graph 0: forward, loss, whole backward, gradients into the bucket      | then ONE all-reduce of the whole bucket
+        #   graph 1: clip, Adam, EMA, weight copies, reports
+        # Both graphs share one memory pool.  Replayed steps are the launch-bound ones (small minibatches): there the actor's and the
+        # critic's backward run side by side on two streams inside one graph, which buys more than reducing the actor's slice early
+        # (one graph per gradient group: 1 800 against 1 300 steps/s at 512 samples on one GPU).  The eager step still reduces
+        # slice by slice (_backward_into_bucket).
+        n = len(self.bucket.params)
         state = {}
 
         def seg_first():
@@ -1484,20 +1455,12 @@ class PPOLearner:
                 (g16,) = torch.autograd.grad(root, (self._w16,), grad_outputs=unit)
                 self.bucket.grad.copy_(g16)
             else:
-                self._backward_group(state["loss"], *groups[0], retain=len(groups) > 1)
-
-        def seg_group(k):
-            self._backward_group(state["loss"], *groups[k], retain=k + 1 < len(groups))
+                self._backward_group(state["loss"], 0, n, retain=False)
 
         def run_eager():
             seg_first()
-            pend = [self._reduce_slice(*groups[0])] if self.dp else []
-            for k in range(1, len(groups)):
-                seg_group(k)
-                if self.dp:
-                    pend.append(self._reduce_slice(*groups[k]))
-            for fin in pend:
-                fin()
+            if self.dp:
+                self._reduce_slice(0, n)()
             return seg_tail(state["stats"])
 
         # warm up on a side stream (allocator, MIOpen solver search), restoring the optimizer state afterwards
@@ -1520,29 +1483,21 @@ class PPOLearner:
             import time as _time
             _time.sleep(0.25)
         tl = dict(capture_error_mode="thread_local")
-        if not segmented:
+        if not self.dp:
             self._graph = torch.cuda.CUDAGraph()
             self._graphs = None
             with torch.cuda.graph(self._graph, **tl):
                 seg_first()
-                for k in range(1, len(groups)):
-                    seg_group(k)
                 self._g_stats = seg_tail(state["stats"])
         else:
-            self._graphs, pool = [], None
-            for k in range(len(groups) + 1):
-                g = torch.cuda.CUDAGraph()
-                with torch.cuda.graph(g, pool=pool, **tl):
-                    if k == 0:
-                        seg_first()
-                    elif k < len(groups):
-                        seg_group(k)
-                    else:
-                        self._g_stats = seg_tail(state["stats"])
-                pool = g.pool()
-                self._graphs.append(g)
+            g0, g1 = torch.cuda.CUDAGraph(), torch.cuda.CUDAGraph()
+            with torch.cuda.graph(g0, **tl):
+                seg_first()
+            with torch.cuda.graph(g1, pool=g0.pool(), **tl):
+                self._g_stats = seg_tail(state["stats"])
+            self._graphs = [g0, g1]
             self._graph = None
-            self._g_groups = list(groups)
+            self._g_groups = [(0, n)]           # the gradient range the replayed step reduces (bench.py reports it)
         state.clear()
         for t, v in zip((self.bucket.data, self.exp_avg, self.exp_avg_sq, self.ema), saved):
             t.copy_(v)
@@ -1550,18 +1505,14 @@ class PPOLearner:
         self._g_batch = batch
 
     def _replay(self):
-        """Replays the captured step; data parallel: graph per gradient group with that group's all-reduce started behind it (on
-        RCCL's own stream, so it runs beside the next graph), then the optimizer tail."""
+        """Replays the captured step; data parallel: forward and backward, the all-reduce of the whole gradient, then the
+        optimizer tail."""
         if self._graphs is None:
             self._graph.replay()
             return
-        pend = []
-        for k, (lo, hi) in enumerate(self._g_groups):
-            self._graphs[k].replay()
-            pend.append(self._reduce_slice(lo, hi))
-        for fin in pend:
-            fin()
-        self._graphs[-1].replay()
+        self._graphs[0].replay()
+        self._reduce_slice(0, len(self.bucket.params))()
+        self._graphs[1].replay()
 
     def _graph_scalar_values(self, clip_eps, ent_coef, step):
         b1, b2 = self.betas

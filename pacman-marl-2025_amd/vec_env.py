@@ -197,7 +197,8 @@ class PmxVecEnv:
         _lib.check(self.lib.pmx_profile_begin(self.handle, int(max_launches)), "pmx_profile_begin")
 
     def set_tuning(self, key, value):
-        """Launch tuning of the expansion kernel for A/B measurements (pmx_set_tuning): "expand_alt", "expand_nt", ..."""
+        """Launch tuning of the expansion kernel for measurements (pmx_set_tuning): "expand_alt" (0 = always the same sweep
+        direction, -1 = the default alternation)."""
         _lib.check(self.lib.pmx_set_tuning(self.handle, key.encode(), int(value)), "pmx_set_tuning")
 
     def profile_end(self):

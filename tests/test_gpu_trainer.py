@@ -819,7 +819,7 @@ def test_one_launch_minibatch_gather_equals_torch_indexing():
     for bit: the tower's data-gradient kernel adds its per-channel sums with LDS float adds, whose order differs from run to run).
     FOUR optimizer steps, not the whole update: over a whole update (24 steps here) that 1e-7 noise decides, now and then, on which
     side of the clip threshold a borderline sample falls, and two runs of the SAME path then differ by a few 1e-4 in the weights and
-    ~0.05 in the averaged gradient norm (tools/r03_flaky.sh) -- a property of PPO's clipping, not of either feeding path."""
+    ~0.05 in the averaged gradient norm (repeated runs) -- a property of PPO's clipping, not of either feeding path."""
     from pmx import trainer
     res = {}
     for gather in (True, False):

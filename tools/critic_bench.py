@@ -1,6 +1,6 @@
 #!/usr/bin/env python3
-"""Times the critic (value head) forward / forward+backward with and without the fused feed-forward kernels, and the FFN
-kernels alone.   python tools/critic_bench.py [--batch 8192]"""
+"""Times the critic (value head) forward / forward+backward, and the fused feed-forward kernels alone.
+python tools/critic_bench.py [--batch 8192]"""
 import argparse, json, os, sys, time
 import torch
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
@@ -44,13 +44,7 @@ def fwd_bwd():
     torch.autograd.grad(v.float().sum(), cparams)
 
 
-res = {"batch": B}
-for fused in (True, False):
-    mappo.MAPPOAgent.fused_ffn = fused
-    k = "fused_ffn" if fused else "separate_ops"
-    res[k + "_fwd_ms"] = timeit(fwd)
-    res[k + "_fwd_bwd_ms"] = timeit(fwd_bwd)
-mappo.MAPPOAgent.fused_ffn = True
+res = {"batch": B, "fwd_ms": timeit(fwd), "fwd_bwd_ms": timeit(fwd_bwd)}
 layer = m.critic_transformer.layers[0]
 x = torch.randn(H * W, B, 32, device=dev).to(torch.bfloat16).requires_grad_(True)
 res["ffn_kernel_fwd_ms"] = timeit(lambda: mappo.ffn_layer_norm(x.detach(), layer.linear1, layer.linear2, layer.norm2))
