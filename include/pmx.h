@@ -57,6 +57,25 @@ enum { PMX_OBS_F32 = 0, PMX_OBS_BF16 = 1, PMX_OBS_U8 = 2 };
  * resident on the device, at most 2 GiB); elsewhere they act as Stop. */
 #define PMX_ACTION_BASELINE_OFFENSE (-3)
 #define PMX_ACTION_BASELINE_DEFENSE (-4)
+/* In-kernel approxQTeam opponents (agents/approxQTeam.py), understood like the two codes above (enable_bots handles, mid-tick
+ * state, any of the four agents; elsewhere Stop).
+ * OFFENSE (ApproxQLearningOffense, :49-110, :194-292, TRAINING = False): with at most two pellets left to eat the agent walks
+ * home exactly as the baseline bots do (no draw).  Otherwise Q(s, a) of every legal action is summed in float64, every product
+ * and sum rounded on its own, in the order of the reference's feature dictionary:
+ *     q = 0;  q += (1.0 / 10.0) * w_bias;  q += (g / 10.0) * w_ghosts;  if (g == 0 && the next cell holds a pellet the agent
+ *     may eat) q += (1.0 / 10.0) * w_eats;  if (such a pellet is reachable) q += ((d / (width * height)) / 10.0) * w_closest
+ * with the team file's four weights, next cell = the agent's cell plus the action vector, g = opponents that are not Pacman on
+ * that cell or on one of its four neighbours, d = maze distance from the next cell to the nearest such pellet.  The best set
+ * holds the actions whose q equals the maximum.  Three draws of the counter-based generator
+ *     h(salt) = lowbias32(seed ^ env * 0x9E3779B1 ^ ticks * 0x85EBCA77 ^ agent * 0xC2B2AE3D ^ salt):
+ *   explore iff h(0xA511E9B3) < 0x1999999A (= ceil(2^32 / 10), epsilon 0.1);
+ *   when exploring, the action PMX_ACTION_RANDOM_LEGAL would play: the floor(h(0) * n / 2^32)-th of the n legal actions;
+ *   otherwise the floor(h(0x5bd1e995) * m / 2^32)-th of the m best actions, the draw the baseline bots make
+ * (lists in the order N, S, E, W, Stop).  Distribution-equivalent to util.flipCoin(0.1) + random.choice.
+ * DEFENSE (DefensiveReflexAgent, :299-406): PMX_ACTION_BASELINE_DEFENSE, except that it walks home with at most two pellets
+ * left (:324) where baselineTeam waits for none. */
+#define PMX_ACTION_APPROXQ_OFFENSE (-5)
+#define PMX_ACTION_APPROXQ_DEFENSE (-6)
 
 typedef struct pmx_env pmx_env;
 
@@ -160,6 +179,16 @@ int pmx_step_agent(pmx_env *env, int agent, const int8_t *actions_dev, const pmx
  * hypothetical states (agents/baselineTeam.py:94-104), normally on a small scratch handle loaded with pmx_set_state.
  * score_change_dev (may be NULL) receives data.scoreChange of each successor. */
 int pmx_successor(pmx_env *env, int agent, const int8_t *actions_dev, int32_t *score_change_dev, void *stream);
+
+/* Ask an in-kernel bot for its move: for agent `agent` of every env, on the CURRENT state and without changing it, what bot
+ * `code` (PMX_ACTION_RANDOM_LEGAL .. PMX_ACTION_APPROXQ_DEFENSE) computes and what it would play if
+ * pmx_step_agent(env, agent, code) were called now (same tick counter, same draws; the tick and this query run the same device
+ * functions).  values_dev [n_envs][5] float64 indexed by action code: the q above for PMX_ACTION_APPROXQ_OFFENSE, the integer
+ * feature sum as a double for the three reflex codes, 0.0 for PMX_ACTION_RANDOM_LEGAL; NaN for illegal actions.  action_dev
+ * [n_envs] int8.  flags_dev [n_envs]: bit 0 = the agent walks home, bit 1 = it explored.  Any of the three may be NULL.
+ * PMX_ERR_UNSUPPORTED on a handle without enable_bots (except PMX_ACTION_RANDOM_LEGAL), PMX_ERR_INVALID for a bad agent or
+ * code. */
+int pmx_bot_query(pmx_env *env, int agent, int code, double *values_dev, int8_t *action_dev, uint8_t *flags_dev, void *stream);
 
 /* Observation planes / legal masks of the CURRENT state for all emitted agents (gymPacMan.get_Observation,
  * gymPacMan.py:195-229; GameState.getLegalActions, capture.py:101-105). */

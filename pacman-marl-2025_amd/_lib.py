@@ -10,6 +10,8 @@ PMX_MAX_DIM = 32
 OBS_F32, OBS_BF16, OBS_U8 = 0, 1, 2
 ACTION_RANDOM_LEGAL = -2
 ACTION_BASELINE_OFFENSE, ACTION_BASELINE_DEFENSE = -3, -4
+ACTION_APPROXQ_OFFENSE, ACTION_APPROXQ_DEFENSE = -5, -6
+BOT_FLAG_HOME, BOT_FLAG_EXPLORED = 1, 2          # pmx_bot_query flags
 COLSUM_BLOCKS = 512
 LN32_PARTIAL_ROWS = 2048
 ACTOR_PACK_BYTES = 297984
@@ -71,6 +73,7 @@ PROTOTYPES = [
     ("pmx_step", C.c_int, [_VP, _VP, C.POINTER(StepOut), _VP]),
     ("pmx_step_agent", C.c_int, [_VP, C.c_int, _VP, C.POINTER(StepOut), _VP]),
     ("pmx_successor", C.c_int, [_VP, C.c_int, _VP, _VP, _VP]),
+    ("pmx_bot_query", C.c_int, [_VP, C.c_int, C.c_int, _VP, _VP, _VP, _VP]),
     ("pmx_observe", C.c_int, [_VP, _VP, _VP, _VP]),
     ("pmx_emit_team_obs", C.c_int, [_VP, C.c_int, _VP, _VP, _VP]),
     ("pmx_get_layout_index", C.c_int, [_VP, C.POINTER(_I32), _VP]),

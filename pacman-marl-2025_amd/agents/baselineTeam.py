@@ -65,9 +65,10 @@ _ROLES = {"OffensiveReflexAgent": _forage_score, "DefensiveReflexAgent": _guard_
 
 
 class ReflexBot(CaptureAgent):
-    def __init__(self, index, score):
+    def __init__(self, index, score, home_at=0):
         CaptureAgent.__init__(self, index)
         self.score = score
+        self.home_at = home_at          # walk home once at most this many pellets are left to eat (approxQTeam's guard: 2)
 
     def registerInitialState(self, gameState):
         CaptureAgent.registerInitialState(self, gameState)
@@ -82,7 +83,7 @@ class ReflexBot(CaptureAgent):
         now = gameState._state
         names = gameState.getLegalActions(self.index)                      # reference list order: N, S, E, W, Stop
         options = gameState._engine.successors(now, self.index)            # all five successors, one GPU round trip
-        if not any(int(now.food[y]) & self.prey_mask for y in range(self.height)):
+        if sum(bin(int(now.food[y]) & self.prey_mask).count("1") for y in range(self.height)) <= self.home_at:
             best_name, best_d = None, 9999
             for name in names:
                 nxt = options[DIR_CODE[name]][0]

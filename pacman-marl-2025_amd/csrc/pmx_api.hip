@@ -13,6 +13,8 @@ extern "C" hipError_t pmx_launch_rule(const PmxTickParams *p, int H, hipStream_t
 extern "C" hipError_t pmx_launch_rule_agent(const PmxTickParams *p, int H, int agent, hipStream_t st);
 extern "C" hipError_t pmx_launch_reset(const PmxTickParams *p, int H, hipStream_t st);
 extern "C" hipError_t pmx_launch_successor(const PmxTickParams *p, int H, int agent, hipStream_t st);
+extern "C" hipError_t pmx_launch_bot_query(const PmxTickParams *p, int H, int agent, int code, double *values, int8_t *action,
+                                           uint8_t *flags, hipStream_t st);
 extern "C" hipError_t pmx_launch_emit_team(const PmxEmitParams *p, int dtype, hipStream_t st, hipEvent_t ev0, hipEvent_t ev1);
 extern "C" hipError_t pmx_launch_expand(const PmxExpandParams *p, int dtype, hipStream_t st, hipEvent_t ev0, hipEvent_t ev1);
 extern "C" hipError_t pmx_launch_maze(const PmxLayoutDev *lay_dev, const int16_t *cell_index_dev, int n_cells,
@@ -437,6 +439,20 @@ int pmx_successor(pmx_env *env, int agent, const int8_t *actions_dev, int32_t *s
     fill_tick_params(env, p, actions_dev, nullptr);
     p.score_change = score_change_dev;
     HIP_TRY(pmx_launch_successor(&p, env->lay.H, agent, as_stream(stream)));
+    return PMX_OK;
+}
+
+int pmx_bot_query(pmx_env *env, int agent, int code, double *values_dev, int8_t *action_dev, uint8_t *flags_dev, void *stream)
+{
+    if (!env) return fail(PMX_ERR_INVALID, "pmx_bot_query: null env");
+    if (agent < 0 || agent > 3) return fail(PMX_ERR_INVALID, "pmx_bot_query: agent %d out of range", agent);
+    if (code > PMX_ACTION_RANDOM_LEGAL || code < PMX_ACTION_APPROXQ_DEFENSE)
+        return fail(PMX_ERR_INVALID, "pmx_bot_query: %d is not a bot action code (-2 .. -6)", code);
+    if (code != PMX_ACTION_RANDOM_LEGAL && !env->dist_dev)
+        return fail(PMX_ERR_UNSUPPORTED, "pmx_bot_query: code %d needs a handle created with enable_bots", code);
+    PmxTickParams p;
+    fill_tick_params(env, p, nullptr, nullptr);
+    HIP_TRY(pmx_launch_bot_query(&p, env->lay.H, agent, code, values_dev, action_dev, flags_dev, as_stream(stream)));
     return PMX_OK;
 }
 

@@ -262,8 +262,60 @@ __device__ __forceinline__ int substep_core(Env &e, const Ctx &c, int action, bo
 // successor of every legal action is generated for real (on a register copy of the agents and a scratch LDS copy of the
 // food column), scored with the reference's features x weights, and one of the best actions is drawn with the
 // counter-based generator; with no food left to eat the agent walks home (:81-90).
+// The bots' draws (include/pmx.h): h(salt) = lowbias32(rng_key ^ ticks * 0x85EBCA77 ^ agent * 0xC2B2AE3D ^ salt); salt 0 is
+// random_legal's draw.
+#define PMX_SALT_BEST 0x5bd1e995u       // choice among the best actions
+#define PMX_SALT_EXPLORE 0xA511E9B3u    // approxQTeam's epsilon test
+#define PMX_BOT_HOME 1                  // flag bits returned beside the action (action | flags << 8)
+#define PMX_BOT_EXPLORED 2
+__device__ __forceinline__ uint32_t bot_hash(uint32_t key, uint32_t ticks, int agent, uint32_t salt)
+{
+    uint32_t x = key ^ (ticks * 0x85EBCA77u) ^ ((uint32_t)agent * 0xC2B2AE3Du) ^ salt;
+    x ^= x >> 16; x *= 0x7FEB352Du; x ^= x >> 15; x *= 0x846CA68Bu; x ^= x >> 16;
+    return x;
+}
+// floor(x * n / 2^32)-th set action of `mask` in the reference's list order N,S,E,W,Stop
+__device__ __forceinline__ int pick_in_order(int mask, uint32_t x)
+{
+    int kk = (int)(((uint64_t)x * (uint32_t)__popc(mask)) >> 32);
+    int pick = 4;
+    const int order[5] = { 0, 2, 1, 3, 4 };
+    for (int j = 0; j < 5; ++j) {
+        const int a = order[j];
+        if ((mask >> a) & 1) { if (kk == 0) pick = a; --kk; }
+    }
+    return pick;
+}
+
+// The walk home of the reflex bots (agents/baselineTeam.py:81-90, agents/approxQTeam.py:77-86 and :324-333): the real
+// successor of every legal action in list order, first minimum of the maze distance from the start cell, no draw.
 template <int I>
-__device__ __noinline__ int bot_action(const Env &e, const Ctx &c, bool defensive)
+__device__ __noinline__ int bot_home_walk(const Env &e, const Ctx &c, int legal)
+{
+    const int start_idx = c.cidx[(c.start_xy[I] >> 8) * 32 + (c.start_xy[I] & 0xFF)];
+    int home_best = 9999, home_act = -1;
+    const int order[5] = { 0, 2, 1, 3, 4 };
+    for (int k = 0; k < 5; ++k) {
+        const int a = order[k];
+        if (!((legal >> a) & 1)) continue;
+        Env t = e;
+        for (int y = 0; y < c.H; ++y) c.fd2[y * PMX_RULE_BLOCK] = c.fd[y * PMX_RULE_BLOCK];
+        Ctx c2 = c;
+        c2.fd = c.fd2;
+        bool rl; int dr = 0, db = 0;
+        substep_core<I>(t, c2, a, rl, dr, db);
+        const int my = c.cidx[(t.xy[I] >> 8) * 32 + (t.xy[I] & 0xFF)];
+        const int hd = c.dist[(size_t)start_idx * c.n_cells + my];
+        if (hd < home_best) { home_best = hd; home_act = a; }
+    }
+    return home_act;
+}
+
+// home_at: the agent walks home when at most that many pellets are left to eat (baselineTeam 0; approxQTeam's defender 2,
+// agents/approxQTeam.py:324).  vals (NULL inside a tick): receives the feature sum of every legal action, indexed by action
+// code (pmx_bot_query); the evaluation then runs even when the agent walks home.  Returns action | flags << 8.
+template <int I>
+__device__ __noinline__ int bot_action(const Env &e, const Ctx &c, bool defensive, int home_at, double *vals)
 {
     constexpr bool RED = (I % 2) == 0;
     constexpr int O1 = RED ? 1 : 0, O2 = O1 + 2;
@@ -271,8 +323,12 @@ __device__ __noinline__ int bot_action(const Env &e, const Ctx &c, bool defensiv
     const uint32_t enemy_mask = RED ? c.hi_mask : c.lo_mask;      // getFood: the other side's pellets
     int food_left = 0;
     for (int y = 0; y < c.H; ++y) food_left += __popc(c.fd[y * PMX_RULE_BLOCK] & enemy_mask);
-    const int start_idx = c.cidx[(c.start_xy[I] >> 8) * 32 + (c.start_xy[I] & 0xFF)];
-    int best = -(1 << 30), best_mask = 0, home_best = 9999, home_act = -1;
+    int home_act = -1;
+    if (food_left <= home_at) {
+        home_act = bot_home_walk<I>(e, c, legal) | (PMX_BOT_HOME << 8);
+        if (!vals) return home_act;
+    }
+    int best = -(1 << 30), best_mask = 0;
     const int order[5] = { 0, 2, 1, 3, 4 };
     const int rev[5] = { 2, 3, 0, 1, 4 };
     for (int k = 0; k < 5; ++k) {
@@ -308,29 +364,96 @@ __device__ __noinline__ int bot_action(const Env &e, const Ctx &c, bool defensiv
         }
         if (val > best) { best = val; best_mask = 1 << a; }
         else if (val == best) best_mask |= 1 << a;
-        const int hd = c.dist[(size_t)start_idx * c.n_cells + my];
-        if (hd < home_best) { home_best = hd; home_act = a; }
+        if (vals) vals[a] = (double)val;
     }
-    if (food_left <= 0) return home_act;
-    uint32_t x = c.rng_key ^ (e.ticks * 0x85EBCA77u) ^ ((uint32_t)I * 0xC2B2AE3Du) ^ 0x5bd1e995u;
-    x ^= x >> 16; x *= 0x7FEB352Du; x ^= x >> 15; x *= 0x846CA68Bu; x ^= x >> 16;
-    int kk = (int)(((uint64_t)x * (uint32_t)__popc(best_mask)) >> 32);
-    int pick = 4;
-    for (int j = 0; j < 5; ++j) {
-        const int a = order[j];
-        if ((best_mask >> a) & 1) { if (kk == 0) pick = a; --kk; }
-    }
-    return pick;
+    if (home_act >= 0) return home_act;
+    return pick_in_order(best_mask, bot_hash(c.rng_key, e.ticks, I, PMX_SALT_BEST));
 }
 
-// BOTS: the handle was created with pmx_config.enable_bots; only that kernel variant carries the reflex-bot code (it costs
-// registers and a stack frame for the agent state: +3 us per tick on 16 k envs even when no bot code is used)
+// agents/approxQTeam.py:49-110, 194-292 ApproxQLearningOffense evaluated in the kernel (action code -5): a linear Q function
+// of (state, action) with the team file's fixed weights, epsilon-greedy with epsilon 0.1, no learning.  Nothing is generated:
+// the features read the agent's cell plus the action vector.  The Q value is summed in float64 in the insertion order of the
+// reference's feature dictionary (bias, ghosts one step away, eats-food, closest-food), every product and sum rounded on its
+// own, so that it equals the reference's Python float bit for bit.  Three draws (include/pmx.h): explore iff
+// h(PMX_SALT_EXPLORE) < ceil(2^32 / 10); exploring plays random_legal's action; otherwise the best set is drawn from as
+// bot_action draws.  With at most two pellets left the agent walks home (:77-86).  Returns action | flags << 8.
+template <int I>
+__device__ __noinline__ int approxq_action(const Env &e, const Ctx &c, double *vals)
+{
+    constexpr bool RED = (I % 2) == 0;
+    constexpr int O1 = RED ? 1 : 0, O2 = O1 + 2;
+    const int px = (int)(e.xy[I] & 0xFF), py = (int)(e.xy[I] >> 8);
+    const int legal = legal_mask(c.wl, c.wls, px, py);
+    const uint32_t enemy_mask = RED ? c.hi_mask : c.lo_mask;      // getFood: the other side's pellets
+    int food_left = 0;
+    for (int y = 0; y < c.H; ++y) food_left += __popc(c.fd[y * PMX_RULE_BLOCK] & enemy_mask);
+    int home_act = -1;
+    if (food_left <= 2) {
+        home_act = bot_home_walk<I>(e, c, legal) | (PMX_BOT_HOME << 8);
+        if (!vals) return home_act;
+    }
+    const double w_bias = -9.280875042529367, w_ghosts = -16.6612110039328, w_eats = 11.127808437648863,
+                 w_closest = -3.099192562140742;                  // agents/approxQTeam.py:58-61
+    const double tenth = __ddiv_rn(1.0, 10.0), cells = (double)(c.W * c.H);
+    double best = 0.0;
+    int best_mask = 0;
+    const int order[5] = { 0, 2, 1, 3, 4 };
+#pragma unroll 1
+    for (int k = 0; k < 5; ++k) {
+        const int a = order[k];
+        if (!((legal >> a) & 1)) continue;
+        const int nx = px + (a == 1) - (a == 3), ny = py + (a == 0) - (a == 2);
+        // ghosts one step away: opponents that are not Pacman (scared or not) on the cell or next to it (Actions.getLegalNeighbors
+        // of the ghost's cell includes the cell itself; the next cell is open, so no wall test is left)
+        int g = 0;
+        if (!e.pac[O1]) g += (abs((int)(e.xy[O1] & 0xFF) - nx) + abs((int)(e.xy[O1] >> 8) - ny)) <= 1;
+        if (!e.pac[O2]) g += (abs((int)(e.xy[O2] & 0xFF) - nx) + abs((int)(e.xy[O2] >> 8) - ny)) <= 1;
+        const bool eats = g == 0 && (((c.fd[ny * PMX_RULE_BLOCK] & enemy_mask) >> nx) & 1u);
+        // closestFood's breadth-first search = the smallest entry of the next cell's row of the distance matrix
+        const uint8_t *drow = c.dist + (size_t)c.cidx[ny * 32 + nx] * c.n_cells;
+        int mind = 255;
+        for (int y = 0; y < c.H; ++y) {
+            uint32_t m = c.fd[y * PMX_RULE_BLOCK] & enemy_mask;
+            while (m) {
+                const int x = __ffs(m) - 1;
+                m &= m - 1;
+                const int d = drow[c.cidx[y * 32 + x]];
+                mind = d < mind ? d : mind;
+            }
+        }
+        double q = 0.0;
+        q = __dadd_rn(q, __dmul_rn(tenth, w_bias));
+        q = __dadd_rn(q, __dmul_rn(__ddiv_rn((double)g, 10.0), w_ghosts));
+        if (eats) q = __dadd_rn(q, __dmul_rn(tenth, w_eats));
+        if (mind != 255) q = __dadd_rn(q, __dmul_rn(__ddiv_rn(__ddiv_rn((double)mind, cells), 10.0), w_closest));
+        if (best_mask == 0 || q > best) { best = q; best_mask = 1 << a; }
+        else if (q == best) best_mask |= 1 << a;
+        if (vals) vals[a] = q;
+    }
+    if (home_act >= 0) return home_act;
+    if (bot_hash(c.rng_key, e.ticks, I, PMX_SALT_EXPLORE) < 0x1999999Au)
+        return random_legal(legal, c.rng_key, e.ticks, I) | (PMX_BOT_EXPLORED << 8);
+    return pick_in_order(best_mask, bot_hash(c.rng_key, e.ticks, I, PMX_SALT_BEST));
+}
+
+// what bot `code` (-2 .. -6) plays for agent I in state e, as action | flags << 8; the tick (vals NULL) and pmx_bot_query go
+// through this one function
+template <int I>
+__device__ __forceinline__ int bot_decide(const Env &e, const Ctx &c, int code, double *vals)
+{
+    if (code == -5) return approxq_action<I>(e, c, vals);
+    if (code == -3) return bot_action<I>(e, c, false, 0, vals);
+    return bot_action<I>(e, c, true, code == -6 ? 2 : 0, vals);
+}
+
+// BOTS: the handle was created with pmx_config.enable_bots; only that kernel variant carries the bot code (action codes
+// -3 .. -6; it costs registers and a stack frame for the agent state: +3 us per tick on 16 k envs even when no bot code is used)
 template <int I, bool BOTS>
 __device__ __forceinline__ int substep(Env &e, const Ctx &c, int action, bool &req_legal, int &d_red, int &d_blue)
 {
     if (action == -2) action = random_legal(legal_mask(c.wl, c.wls, (int)(e.xy[I] & 0xFF), (int)(e.xy[I] >> 8)), c.rng_key, e.ticks, I);
     if constexpr (BOTS) {
-        if ((action == -3 || action == -4) && c.dist) action = bot_action<I>(e, c, action == -4);
+        if (action <= -3 && action >= -6 && c.dist) action = bot_decide<I>(e, c, action, nullptr) & 0xFF;
     }
     return substep_core<I>(e, c, action, req_legal, d_red, d_blue);
 }
@@ -716,6 +839,42 @@ extern "C" __global__ __launch_bounds__(PMX_RULE_BLOCK) void pmx_successor_kerne
     case 1: successor_body<1>(p, lds); break;
     case 2: successor_body<2>(p, lds); break;
     default: successor_body<3>(p, lds); break;
+    }
+}
+
+// pmx_bot_query: what bot `code` computes for agent I on the current state and what it would play now; nothing is written back.
+// It calls the very device functions the tick calls (bot_decide, random_legal).
+template <int I>
+__device__ __forceinline__ void bot_query_body(const PmxTickParams &p, uint32_t *lds, int code, double *values, int8_t *action,
+                                               uint8_t *flags)
+{
+    Ctx c = make_ctx(p, lds);
+    const int env = blockIdx.x * PMX_RULE_BLOCK + threadIdx.x;
+    if (env >= p.N) return;
+    Env e;
+    load_env(e, c, p.state, p.N, env);
+    const int legal = legal_mask(c.wl, c.wls, (int)(e.xy[I] & 0xFF), (int)(e.xy[I] >> 8));
+    double v[5] = { 0.0, 0.0, 0.0, 0.0, 0.0 };
+    int r;
+    if (code == -2 || !c.dist) r = random_legal(legal, c.rng_key, e.ticks, I);      // (the host refuses other codes without bots)
+    else r = bot_decide<I>(e, c, code, v);
+    if (values) {
+#pragma unroll
+        for (int a = 0; a < 5; ++a) values[5 * (size_t)env + a] = ((legal >> a) & 1) ? v[a] : __longlong_as_double(0x7FF8000000000000LL);
+    }
+    if (action) action[env] = (int8_t)(r & 0xFF);
+    if (flags) flags[env] = (uint8_t)(r >> 8);
+}
+
+extern "C" __global__ __launch_bounds__(PMX_RULE_BLOCK) void pmx_bot_query_kernel(PmxTickParams p, int agent, int code, double *values,
+                                                                                  int8_t *action, uint8_t *flags)
+{
+    extern __shared__ uint32_t lds[];
+    switch (agent) {   // wave-uniform
+    case 0: bot_query_body<0>(p, lds, code, values, action, flags); break;
+    case 1: bot_query_body<1>(p, lds, code, values, action, flags); break;
+    case 2: bot_query_body<2>(p, lds, code, values, action, flags); break;
+    default: bot_query_body<3>(p, lds, code, values, action, flags); break;
     }
 }
 
@@ -1289,6 +1448,15 @@ extern "C" hipError_t pmx_launch_successor(const PmxTickParams *p, int H, int ag
     const int blocks = (p->N + PMX_RULE_BLOCK - 1) / PMX_RULE_BLOCK;
     const size_t lds = (p->layout_idx ? 32 + (size_t)(3 * PMX_MAX_H_LDS + 32 + 16) * PMX_RULE_BLOCK : 32 + (size_t)(3 * H + 16) * PMX_RULE_BLOCK) * sizeof(uint32_t);
     hipLaunchKernelGGL(pmx_successor_kernel, dim3(blocks), dim3(PMX_RULE_BLOCK), lds, st, *p, agent);
+    return hipGetLastError();
+}
+
+extern "C" hipError_t pmx_launch_bot_query(const PmxTickParams *p, int H, int agent, int code, double *values, int8_t *action,
+                                           uint8_t *flags, hipStream_t st)
+{
+    const int blocks = (p->N + PMX_RULE_BLOCK - 1) / PMX_RULE_BLOCK;
+    const size_t lds = (p->layout_idx ? 32 + (size_t)(3 * PMX_MAX_H_LDS + 32 + 16) * PMX_RULE_BLOCK : 32 + (size_t)(3 * H + 16) * PMX_RULE_BLOCK) * sizeof(uint32_t);
+    hipLaunchKernelGGL(pmx_bot_query_kernel, dim3(blocks), dim3(PMX_RULE_BLOCK), lds, st, *p, agent, code, values, action, flags);
     return hipGetLastError();
 }
 

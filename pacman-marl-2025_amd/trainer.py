@@ -6,9 +6,9 @@ Per update (pacman_mappo_resnet.py:385-600), with N envs in lock-step instead of
            (:241-264, :513-522), store everything in DEVICE-resident buffers (:449-455 kept them on the CPU)
   GAE      pmx_gae over the [T][2N] series (:548-553)
   update   UPDATE_EPOCHS x minibatches of the flattened [T*N*2] samples through PPOLearner (:556-595)
-Opponents: the in-kernel randomTeam and baselineTeam bots (PMX_ACTION_RANDOM_LEGAL / PMX_ACTION_BASELINE_*), the current
-network, or a frozen EMA snapshot from the opponent pool (:396-438; the A*/MCTS/approx-Q teams of the reference's
-curriculum are out of scope).
+Opponents: the in-kernel randomTeam, baselineTeam and approxQTeam bots (PMX_ACTION_RANDOM_LEGAL / PMX_ACTION_BASELINE_* /
+PMX_ACTION_APPROXQ_*), the current network, or a frozen EMA snapshot from the opponent pool (:396-438; the A* / MCTS /
+heuristic teams of the reference's curriculum are wall-clock-bounded searches and out of scope).
 """
 import copy
 import ctypes as C
@@ -39,6 +39,8 @@ def shaping_from_agent_words(prev, cur):
     return out
 
 
+BOT_TEAMS = {"baseline": (_lib.ACTION_BASELINE_OFFENSE, _lib.ACTION_BASELINE_DEFENSE),      # createTeam: first index offensive,
+             "approxq": (_lib.ACTION_APPROXQ_OFFENSE, _lib.ACTION_APPROXQ_DEFENSE)}         # second defensive
 _OBS_CODES = {torch.float32: _lib.OBS_F32, torch.bfloat16: _lib.OBS_BF16, torch.uint8: _lib.OBS_U8}
 
 
@@ -79,9 +81,14 @@ class VecMAPPOTrainer:
     def __init__(self, layout, n_envs, horizon=32, minibatch=512, epochs=UPDATE_EPOCHS, obs_dtype=None,
                  device="cuda:0", seed=0, rank=0, world_size=1, process_group=None, total_updates=2000, length=300,
                  use_autocast=True, opponent="random", use_graph=False, algorithm="mappo", paired_minibatches=True, flat_bf16=False, curriculum_scale=1.0,
-                 env=None, redraw_layouts=False, force_collectives=False):
+                 env=None, redraw_layouts=False, force_collectives=False, hard_bots=("baseline",)):
         self.device = torch.device(device)
         self.rank, self.world_size = rank, world_size
+        # hard_bots: the in-kernel teams the curriculum draws its "hard" opponent from (the reference's hard teams are
+        # baselineTeam, AstarTeam and approxQTeam, pacman_mappo_resnet.py:40-47); the default keeps the draws of earlier versions
+        self.hard_bots = tuple(hard_bots)
+        if not self.hard_bots or any(b not in BOT_TEAMS for b in self.hard_bots):
+            raise ValueError(f"hard_bots must name in-kernel teams out of {sorted(BOT_TEAMS)}, got {hard_bots!r}")
         if obs_dtype is None:
             # byte planes on the bf16 path: the values are small integers, the fused actor tower reads bytes directly and
             # the rollout buffers are half the size; float32 planes (the reference's dtype) on the float32 path
@@ -91,7 +98,7 @@ class VecMAPPOTrainer:
         # without a GPU
         self.env = env if env is not None else PmxVecEnv(
             layout, n_envs, length=length, reward_forLegalAction=True, defenceReward=True, auto_reset=True, obs_dtype=obs_dtype,
-            device=self.device, seed=seed * 1000003 + rank, bots=opponent in ("baseline", "curriculum"), redraw_layouts=redraw_layouts)
+            device=self.device, seed=seed * 1000003 + rank, bots=opponent in BOT_TEAMS or opponent == "curriculum", redraw_layouts=redraw_layouts)
         self.N, self.T = n_envs, horizon
         self.minibatch, self.epochs = minibatch, epochs
         # "mappo": centralised critic on merge_obs_for_critic of the two learners (the reference).  "ippo": the same network
@@ -132,7 +139,7 @@ class VecMAPPOTrainer:
         self.opponent_model.eval()
         self.opponent_pool = deque(maxlen=OPPONENT_POOL_SIZE)
         self.opponent_pool.append(self.learner.ema_state_dict())
-        self.opponent_mode = opponent                              # "random" | "baseline" | "self" | "pool" | "curriculum"
+        self.opponent_mode = opponent                              # "random" | "baseline" | "approxq" | "self" | "pool" | "curriculum"
         self.gen = torch.Generator(device=self.device).manual_seed(seed * 7919 + rank)   # action sampling, minibatch order: per rank
         # opponent mode / side / pool draws: the SAME stream on every rank, so that all ranks run the same kind of rollout
         # (an extra opponent forward per tick on some ranks only would make the others wait at every gradient all-reduce)
@@ -190,19 +197,26 @@ class VecMAPPOTrainer:
             v = model.value(self._net_in(merged)).float() if want_value else None
         return a.view(-1, 2), lp.view(-1, 2), v
 
+    def _hard_bot(self):
+        """The hard in-kernel team of this rollout: one extra draw, made only when there is a choice."""
+        if len(self.hard_bots) == 1:
+            return self.hard_bots[0]
+        return self.hard_bots[self.np_rng.randint(len(self.hard_bots))]
+
     def _pick_opponent(self):
         """The self-play part of the curriculum (pacman_mappo_resnet.py:396-438) with the opponents this build has."""
         mode = self.opponent_mode
         if mode == "curriculum":
-            # :396-438 with the opponents this build has on the GPU: randomTeam first, then randomTeam / baselineTeam
-            # (the reference weights its "hard" teams, baselineTeam among them, 5x), then 40 % self / 20 % pool / 40 % bots
+            # :396-438 with the opponents this build has on the GPU: randomTeam first, then randomTeam / a hard team out of
+            # hard_bots (the reference weights its "hard" teams, baselineTeam and approxQTeam among them, 5x), then 40 % self /
+            # 20 % pool / 40 % bots
             if self.update_idx <= 200 * self.curriculum_scale:
                 mode = "random"
             elif self.update_idx <= 800 * self.curriculum_scale:
-                mode = "baseline" if self.np_rng.rand() < 5.0 / 6.0 else "random"
+                mode = self._hard_bot() if self.np_rng.rand() < 5.0 / 6.0 else "random"
             else:
                 r = self.np_rng.rand()
-                mode = "self" if r < 0.40 else ("pool" if r < 0.60 else ("baseline" if self.np_rng.rand() < 5.0 / 6.0 else "random"))
+                mode = "self" if r < 0.40 else ("pool" if r < 0.60 else (self._hard_bot() if self.np_rng.rand() < 5.0 / 6.0 else "random"))
         play_as_red = False
         if mode == "self":
             play_as_red = bool(self.np_rng.rand() > 0.5)
@@ -234,9 +248,8 @@ class VecMAPPOTrainer:
             self._boot_merged = torch.empty((N,) + self.obs_shape, dtype=dt, device=self.device)
         acts = self._acts
         acts.fill_(_lib.ACTION_RANDOM_LEGAL)
-        if mode == "baseline":                                       # createTeam: first index offensive, second defensive
-            acts[:, opp_ids[0]] = _lib.ACTION_BASELINE_OFFENSE
-            acts[:, opp_ids[1]] = _lib.ACTION_BASELINE_DEFENSE
+        if mode in BOT_TEAMS:
+            acts[:, opp_ids[0]], acts[:, opp_ids[1]] = BOT_TEAMS[mode]
         mappo_alg = self.algorithm == "mappo"
         for t in range(T):
             env.emit_team_obs(red, self.obs_buf[t], self.merged_buf[t] if mappo_alg else None)
@@ -372,6 +385,7 @@ class VecMAPPOTrainer:
         torch.save({"data": self.learner.bucket.data, "ema": self.learner.ema, "exp_avg": self.learner.exp_avg,
                     "exp_avg_sq": self.learner.exp_avg_sq, "step": int(self.learner.step_count), "update": int(self.update_idx),
                     "total_updates": int(self.total_updates), "pool": list(self.opponent_pool), "gen": self.gen.get_state(),
+                    "hard_bots": list(self.hard_bots),
                     "np_rng": {"kind": str(kind), "keys": torch.from_numpy(np.asarray(keys, dtype=np.int64)), "pos": int(pos),
                                "has_gauss": int(has_gauss), "cached_gaussian": float(cached)}}, path)
 
@@ -388,6 +402,7 @@ class VecMAPPOTrainer:
         self.learner.step_count, self.update_idx = int(ck["step"]), int(ck["update"])
         self.opponent_pool = deque(ck["pool"], maxlen=OPPONENT_POOL_SIZE)
         self.gen.set_state(ck["gen"].cpu())
+        self.hard_bots = tuple(ck.get("hard_bots", ("baseline",)))       # files written before hard_bots existed: the default
         r = ck["np_rng"]
         self.np_rng.set_state((r["kind"], r["keys"].cpu().numpy().astype(np.uint32), int(r["pos"]), int(r["has_gauss"]),
                                float(r["cached_gaussian"])))
@@ -428,18 +443,18 @@ def evaluate_vs_bots(model, num_episodes=20, layout_file="bloxCapture", teams=("
 def evaluate_vectorized(model, layout="bloxCapture", n_envs=1024, opponent="baseline", length=300, device="cuda:0", seed=0,
                         autocast=True):
     """evaluate_vs_bots (pacman_mappo_resnet.py:293-337) for n_envs episodes at once: the learner plays blue with argmax
-    actions against the in-kernel randomTeam / baselineTeam, one episode per env (an env stops counting at its first done).
+    actions against the in-kernel randomTeam / baselineTeam / approxQTeam (opponent "random" / "baseline" / "approxq"), one episode per env (an env stops counting at its first done).
     Returns (mean episode return of the learner team as the reference sums it, std, win rate = share with final score < 0)."""
     dev = torch.device(device)
     env = PmxVecEnv(layout, n_envs, length=length, auto_reset=True, obs_dtype="bfloat16" if autocast else "float32", device=dev,
-                    seed=seed, bots=(opponent == "baseline"))
+                    seed=seed, bots=opponent in BOT_TEAMS)
     obs, _ = env.reset()
     was_training = model.training
     model.eval()
     alive = torch.ones(n_envs, dtype=torch.bool, device=dev)
     ret = torch.zeros(n_envs, dtype=torch.float64, device=dev)
     final = torch.zeros(n_envs, dtype=torch.int32, device=dev)
-    opp = (_lib.ACTION_BASELINE_OFFENSE, _lib.ACTION_BASELINE_DEFENSE) if opponent == "baseline" else (_lib.ACTION_RANDOM_LEGAL,) * 2
+    opp = BOT_TEAMS.get(opponent, (_lib.ACTION_RANDOM_LEGAL,) * 2)
     ctx = torch.autocast(device_type=dev.type, dtype=torch.bfloat16) if autocast else _NullCtx()
     for _ in range(length + 1):
         lo = obs[:, [1, 3]].reshape((-1,) + tuple(obs.shape[2:]))

@@ -79,7 +79,7 @@ class PmxVecEnv:
         cfg.redraw_layouts = int(bool(redraw_layouts))
         if redraw_layouts and len(L) < 2:
             raise ValueError("redraw_layouts needs a pool of at least two layouts")
-        cfg.enable_bots = int(bool(bots))          # understand ACTION_BASELINE_OFFENSE / _DEFENSE (in-kernel baselineTeam)
+        cfg.enable_bots = int(bool(bots))          # understand ACTION_BASELINE_* / ACTION_APPROXQ_* (in-kernel bot teams)
         self.handle = C.c_void_p()
         with torch.cuda.device(self.device):
             _lib.check(self.lib.pmx_create(C.byref(cfg), C.byref(self.handle)), "pmx_create")
@@ -172,6 +172,20 @@ class PmxVecEnv:
             _lib.check(self.lib.pmx_successor(self.handle, int(agent), a.data_ptr(), self.score_change.data_ptr(),
                                               self._stream()), "pmx_successor")
         return self.score_change
+
+    def bot_query(self, agent, code, want_values=True):
+        """Ask an in-kernel bot for its move (pmx_bot_query): for `agent` of every env, on the current state and without
+        changing it, what bot `code` (-2 .. -6) would play if step_agent(agent, code) were called now.  Returns (values [N,5]
+        float64 indexed by action code, NaN where illegal -- None unless want_values --, action [N] int8, flags [N] uint8:
+        bit 0 walked home, bit 1 explored); fresh tensors."""
+        N = self.n_envs
+        values = torch.empty((N, 5), dtype=torch.float64, device=self.device) if want_values else None
+        action = torch.empty((N,), dtype=torch.int8, device=self.device)
+        flags = torch.empty((N,), dtype=torch.uint8, device=self.device)
+        with torch.cuda.device(self.device):
+            _lib.check(self.lib.pmx_bot_query(self.handle, int(agent), int(code), values.data_ptr() if want_values else None,
+                                              action.data_ptr(), flags.data_ptr(), self._stream()), "pmx_bot_query")
+        return values, action, flags
 
     def observe(self, want_obs=True, want_legal=True):
         """get_Observation of the current state for every emitted agent (gymPacMan.py:195-229) and/or the legal masks."""

@@ -13,6 +13,8 @@ for bots in (False, True):
         variants["red = baselineTeam (offense, defense)"] = b
         c = a.clone(); c[:, 0] = -2; c[:, 2] = -2
         variants["red = randomTeam in-kernel"] = c
+        d = a.clone(); d[:, 0] = -5; d[:, 2] = -6
+        variants["red = approxQTeam (offense, defense)"] = d
     for name, act in variants.items():
         for _ in range(20): env.step(act)
         env.profile_begin(220)

@@ -22,7 +22,8 @@ ap.add_argument("--minibatch", type=int, default=8192, help="samples per optimiz
 ap.add_argument("--epochs", type=int, default=3)
 ap.add_argument("--updates", type=int, default=10)
 ap.add_argument("--total-updates", type=int, default=2000)
-ap.add_argument("--opponent", default="curriculum", choices=["random", "baseline", "self", "pool", "curriculum"])
+ap.add_argument("--opponent", default="curriculum", choices=["random", "baseline", "approxq", "self", "pool", "curriculum"])
+ap.add_argument("--hard-bots", default="baseline", help="comma-separated in-kernel teams the curriculum draws its hard opponent from (baseline, approxq)")
 ap.add_argument("--obs", default=None, choices=["float32", "bfloat16", "uint8"], help="observation planes; default: the trainer's choice (uint8 under bf16 autocast, float32 otherwise)")
 ap.add_argument("--algorithm", default="mappo", choices=["mappo", "ippo"])
 ap.add_argument("--eval-every", type=int, default=0)
@@ -60,7 +61,8 @@ def emit(rec):
 
 tr = trainer.VecMAPPOTrainer(layout, args.envs, horizon=args.horizon, minibatch=args.minibatch, epochs=args.epochs, redraw_layouts=args.redraw,
                              obs_dtype=args.obs, device=f"cuda:{local}", seed=args.seed, rank=rank, world_size=world,
-                             total_updates=args.total_updates, opponent=args.opponent, algorithm=args.algorithm, use_graph=args.graph, paired_minibatches=not args.unpaired, flat_bf16=args.flat_bf16, curriculum_scale=args.curriculum_scale)
+                             total_updates=args.total_updates, opponent=args.opponent, algorithm=args.algorithm, use_graph=args.graph, paired_minibatches=not args.unpaired, flat_bf16=args.flat_bf16, curriculum_scale=args.curriculum_scale,
+                             hard_bots=tuple(args.hard_bots.split(",")))
 for u in range(args.updates):
     torch.cuda.synchronize(); t0 = time.perf_counter()
     st = tr.train_update()
