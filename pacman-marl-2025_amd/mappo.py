@@ -11,11 +11,19 @@ Differences that are design, not semantics: parameters, gradients and the EMA co
 (one RCCL all-reduce per optimizer step over xGMI, one fused Adam, one lerp for the EMA); the network runs under
 bf16 autocast on the GPU (MFMA through MIOpen / hipBLASLt) with fp32 master weights; fp32 on CPU for the parity tests.
 """
+import contextlib
+import ctypes as C
 import math
+import os
+import sys
+import time
 
 import torch
 import torch.nn as nn
 import torch.nn.functional as F
+from torch.nn.utils import stateless
+
+from . import _lib, actor_tower
 
 GAMMA, GAE_LAMBDA = 0.99, 0.95                     # pacman_mappo_resnet.py:19-20
 CLIP_EPS, VF_COEF, MAX_GRAD_NORM = 0.15, 0.5, 0.5  # :21-23
@@ -75,8 +83,6 @@ def pending_rows_of(ptr):
 
 def flush_pending_rows():
     """Adds whatever partial rows are still pending with the dedicated kernel (a consumer other than the learner's gather)."""
-    import ctypes as C
-    from . import _lib
     lib = _lib.load() if _PENDING_ROWS else None
     for base, (n, floats, buf) in list(_PENDING_ROWS.items()):
         st = C.c_void_p(torch.cuda.current_stream(buf.device).cuda_stream)
@@ -89,8 +95,6 @@ class _LN32Residual(torch.autograd.Function):
 
     @staticmethod
     def forward(ctx, x, a, w, b, eps):
-        import ctypes as C
-        from . import _lib
         lib = _lib.load()
         x, a = x.contiguous(), a.contiguous()
         rows = x.numel() // 32
@@ -107,8 +111,6 @@ class _LN32Residual(torch.autograd.Function):
 
     @staticmethod
     def backward(ctx, gy):
-        import ctypes as C
-        from . import _lib
         lib = _lib.load()
         x, a, wf, mean, rstd = ctx.saved_tensors
         gy = gy.contiguous()
@@ -136,8 +138,6 @@ class _FFNLayerNorm(torch.autograd.Function):
 
     @staticmethod
     def forward(ctx, x, w1, b1, w2, b2, gamma, beta, eps, pack=None):
-        import ctypes as C
-        from . import _lib
         lib = _lib.load()
         x = x.contiguous()
         dev = x.device
@@ -153,8 +153,6 @@ class _FFNLayerNorm(torch.autograd.Function):
 
     @staticmethod
     def backward(ctx, dy):
-        import ctypes as C
-        from . import _lib
         lib = _lib.load()
         x, pack = ctx.saved_tensors
         dev = x.device
@@ -173,8 +171,6 @@ class _FFNLayerNorm(torch.autograd.Function):
 
 def pack_ffn(w1, b1, w2, b2, gamma, beta):
     """The feed-forward half's parameters in the kernels' operand layout (pmx_ffn_pack), on the current stream."""
-    import ctypes as C
-    from . import _lib
     lib = _lib.load()
     ps = [t.detach().float().contiguous() for t in (w1, b1, w2, b2, gamma, beta)]
     pack = torch.empty(_lib.FFN_PACK_BYTES, dtype=torch.uint8, device=ps[0].device)
@@ -184,8 +180,6 @@ def pack_ffn(w1, b1, w2, b2, gamma, beta):
 
 
 def pack_in_proj(w, b):
-    import ctypes as C
-    from . import _lib
     lib = _lib.load()
     wf, bf = w.detach().float().contiguous(), b.detach().float().contiguous()
     pack = torch.empty(_lib.TOK96_PACK_BYTES, dtype=torch.uint8, device=wf.device)
@@ -195,8 +189,6 @@ def pack_in_proj(w, b):
 
 
 def pack_out_proj(w, b, gamma, beta):
-    import ctypes as C
-    from . import _lib
     lib = _lib.load()
     ps = [t.detach().float().contiguous() for t in (w, b, gamma, beta)]
     pack = torch.empty(_lib.TOK32_PACK_BYTES, dtype=torch.uint8, device=ps[0].device)
@@ -208,8 +200,6 @@ def pack_out_proj(w, b, gamma, beta):
 def encoder_packs(layers):
     """The three parameter packs (in-projection, out-projection + norm1, feed-forward + norm2) of every given CriticEncoderLayer in
     ONE launch (pmx_encoder_pack) on the current stream -> [(pack_in, pack_out, pack_ffn), ...]."""
-    import ctypes as C
-    from . import _lib
     lib = _lib.load()
     n = len(layers)
     arr = (_lib.EncoderLayerParams * n)()
@@ -238,8 +228,6 @@ class _InProj96(torch.autograd.Function):
 
     @staticmethod
     def forward(ctx, a, w, b, pack=None):
-        import ctypes as C
-        from . import _lib
         lib = _lib.load()
         a = a.contiguous()
         st = C.c_void_p(torch.cuda.current_stream(a.device).cuda_stream)
@@ -253,8 +241,6 @@ class _InProj96(torch.autograd.Function):
 
     @staticmethod
     def backward(ctx, dy):
-        import ctypes as C
-        from . import _lib
         lib = _lib.load()
         a, pack = ctx.saved_tensors
         st = C.c_void_p(torch.cuda.current_stream(a.device).cuda_stream)
@@ -274,8 +260,6 @@ class _InProj96Res(torch.autograd.Function):
 
     @staticmethod
     def forward(ctx, a, w, b, pack=None):
-        import ctypes as C
-        from . import _lib
         lib = _lib.load()
         a = a.contiguous()
         st = C.c_void_p(torch.cuda.current_stream(a.device).cuda_stream)
@@ -289,8 +273,6 @@ class _InProj96Res(torch.autograd.Function):
 
     @staticmethod
     def backward(ctx, dy, dres):
-        import ctypes as C
-        from . import _lib
         lib = _lib.load()
         a, pack = ctx.saved_tensors
         st = C.c_void_p(torch.cuda.current_stream(a.device).cuda_stream)
@@ -312,8 +294,6 @@ class _OutProjAddLN(torch.autograd.Function):
 
     @staticmethod
     def forward(ctx, x, a, w, b, gamma, beta, eps, pack=None):
-        import ctypes as C
-        from . import _lib
         lib = _lib.load()
         x, a = x.contiguous(), a.contiguous()
         st = C.c_void_p(torch.cuda.current_stream(a.device).cuda_stream)
@@ -329,8 +309,6 @@ class _OutProjAddLN(torch.autograd.Function):
 
     @staticmethod
     def backward(ctx, dy):
-        import ctypes as C
-        from . import _lib
         lib = _lib.load()
         x, a, pack = ctx.saved_tensors
         st = C.c_void_p(torch.cuda.current_stream(a.device).cuda_stream)
@@ -381,8 +359,6 @@ def ffn_layer_norm(x, lin1, lin2, ln, pack=None):
 def attention8_forward(qkv, want_lse=False, batch_major=False):
     """softmax(q k^T / sqrt(8)) v for 4 heads of 8 on the matrix cores (pmx_attn8_forward_layout): qkv [S, B, 96] bfloat16 ->
     [S, B, 32] bfloat16 (+ log-sum-exp [B, 4, S] float32); with batch_major qkv is [B, S, 96] and the result [B, S, 32]."""
-    import ctypes as C
-    from . import _lib
     lib = _lib.load()
     (B, S, _) = qkv.shape if batch_major else (qkv.shape[1], qkv.shape[0], 0)
     qkv = qkv.contiguous()
@@ -406,8 +382,6 @@ class _Attention8(torch.autograd.Function):
 
     @staticmethod
     def backward(ctx, gout):
-        import ctypes as C
-        from . import _lib
         lib = _lib.load()
         qkv, out, lse = ctx.saved_tensors
         B, S = lse.shape[0], lse.shape[2]
@@ -424,8 +398,6 @@ def attention8(qkv, batch_major=False):
 
 
 def pack_projector(w, b):
-    import ctypes as C
-    from . import _lib
     lib = _lib.load()
     wf, bf = w.detach().float().contiguous(), b.detach().float().contiguous()
     pack = torch.empty(_lib.PROJ_PACK_BYTES, dtype=torch.uint8, device=wf.device)
@@ -440,16 +412,13 @@ class _Projector(torch.autograd.Function):
 
     @staticmethod
     def forward(ctx, obs, w, b, pe):
-        import ctypes as C
-        from . import _lib
-        from .actor_tower import _OBS_CODE
         lib = _lib.load()
         obs = obs.contiguous()
         B, _, H, W = obs.shape
         pack = pack_projector(w, b)
         tok = torch.empty(B, H * W, 32, dtype=torch.bfloat16, device=obs.device)
         st = C.c_void_p(torch.cuda.current_stream(obs.device).cuda_stream)
-        _lib.check(lib.pmx_proj_forward(obs.data_ptr(), _OBS_CODE[obs.dtype], pack.data_ptr(), pe.data_ptr(), tok.data_ptr(), B, H, W, st),
+        _lib.check(lib.pmx_proj_forward(obs.data_ptr(), actor_tower._OBS_CODE[obs.dtype], pack.data_ptr(), pe.data_ptr(), tok.data_ptr(), B, H, W, st),
                    "pmx_proj_forward")
         ctx.save_for_backward(obs)
         ctx.dtypes = (w.dtype, b.dtype)
@@ -457,9 +426,6 @@ class _Projector(torch.autograd.Function):
 
     @staticmethod
     def backward(ctx, dtok):
-        import ctypes as C
-        from . import _lib
-        from .actor_tower import _OBS_CODE
         lib = _lib.load()
         (obs,) = ctx.saved_tensors
         B, _, H, W = obs.shape
@@ -469,7 +435,7 @@ class _Projector(torch.autograd.Function):
         dw = torch.empty(32, 8, 3, 3, dtype=torch.float32, device=dev)
         db = torch.empty(32, dtype=torch.float32, device=dev)
         st = C.c_void_p(torch.cuda.current_stream(dev).cuda_stream)
-        _lib.check(lib.pmx_proj_backward(obs.data_ptr(), _OBS_CODE[obs.dtype], dtok.data_ptr(), part.data_ptr(), dw.data_ptr(), db.data_ptr(),
+        _lib.check(lib.pmx_proj_backward(obs.data_ptr(), actor_tower._OBS_CODE[obs.dtype], dtok.data_ptr(), part.data_ptr(), dw.data_ptr(), db.data_ptr(),
                                          B, H, W, st), "pmx_proj_backward")
         return None, dw.to(ctx.dtypes[0]), db.to(ctx.dtypes[1]), None
 
@@ -480,8 +446,6 @@ class _ActorTail(torch.autograd.Function):
 
     @staticmethod
     def forward(ctx, h, lnw, lnb, w2, b2, eps):
-        import ctypes as C
-        from . import _lib
         lib = _lib.load()
         h = h.contiguous()
         B = h.shape[0]
@@ -495,8 +459,6 @@ class _ActorTail(torch.autograd.Function):
 
     @staticmethod
     def backward(ctx, dlogits):
-        import ctypes as C
-        from . import _lib
         lib = _lib.load()
         h, stats, lnw, lnb, w2 = ctx.saved_tensors
         B = h.shape[0]
@@ -517,8 +479,6 @@ class _CriticTail(torch.autograd.Function):
 
     @staticmethod
     def forward(ctx, tokens, w1, b1, w2, b2):
-        import ctypes as C
-        from . import _lib
         lib = _lib.load()
         tokens = tokens.contiguous()
         B, S, _ = tokens.shape
@@ -533,8 +493,6 @@ class _CriticTail(torch.autograd.Function):
 
     @staticmethod
     def backward(ctx, dvalue):
-        import ctypes as C
-        from . import _lib
         lib = _lib.load()
         pooled, w1, b1, w2 = ctx.saved_tensors
         B, S, dev = pooled.shape[0], ctx.S, pooled.device
@@ -554,8 +512,6 @@ def column_sums(t):
     GPU whose last dimension is a multiple of 8 (<= 256), torch's reduction otherwise."""
     C_ = t.shape[-1]
     if t.is_cuda and t.dtype == torch.bfloat16 and t.is_contiguous() and C_ % 8 == 0 and 8 <= C_ <= 256 and t.numel() >= C_ * 4096:
-        import ctypes as C
-        from . import _lib
         lib = _lib.load()
         partial = torch.empty(_lib.COLSUM_BLOCKS, C_, dtype=torch.float32, device=t.device)
         st = C.c_void_p(torch.cuda.current_stream(t.device).cuda_stream)
@@ -655,8 +611,6 @@ class _GN8Gelu(torch.autograd.Function):
 
     @staticmethod
     def forward(ctx, h, res, w, b, groups, eps):
-        import ctypes as C
-        from . import _lib
         lib = _lib.load()
         # channels-last bf16 tensors (what MIOpen's NHWC convolutions produce) take the NHWC kernels, anything else NCHW
         cl = h.dtype == torch.bfloat16 and h.is_contiguous(memory_format=torch.channels_last) and not h.is_contiguous()
@@ -684,8 +638,6 @@ class _GN8Gelu(torch.autograd.Function):
 
     @staticmethod
     def backward(ctx, gy):
-        import ctypes as C
-        from . import _lib
         lib = _lib.load()
         h, res, wf, bf, mean, rstd = ctx.saved_tensors
         gy = gy.contiguous(memory_format=torch.channels_last if ctx.cl else torch.contiguous_format)
@@ -812,14 +764,12 @@ class MAPPOAgent(nn.Module):
             return False
         if self.actor_backbone[0].weight.dtype != torch.float32:
             return False
-        from . import actor_tower
         return actor_tower.tower_supported(obs.shape[2], obs.shape[3])
 
     def logits(self, obs):
         if self._use_fused_tower(obs):
             # one kernel for the whole convolutional tower (csrc/pmx_actor.hip); its output is channels-last, nn.Flatten's
             # order is channel-major
-            from . import actor_tower
             if self.tower_pack is not None and not torch.is_grad_enabled():
                 feat = actor_tower.tower_forward(obs, self.tower_pack)
             else:
@@ -859,7 +809,6 @@ class MAPPOAgent(nn.Module):
         if not (self.fused_projector and merged_obs.dtype in (torch.uint8, torch.bfloat16, torch.float32) and merged_obs.dim() == 4
                 and merged_obs.shape[1] == 8 and conv.weight.dtype == torch.float32 and tuple(conv.weight.shape) == (32, 8, 3, 3)):
             return False
-        from . import actor_tower
         return actor_tower.tower_supported(merged_obs.shape[2], merged_obs.shape[3])
 
     def value(self, merged_obs):
@@ -947,8 +896,6 @@ class _PPOLossFn(torch.autograd.Function):
 
     @staticmethod
     def forward(ctx, logits, values, act, old_logp, adv, ret, clip_eps, ent_coef, vf_coef):
-        import ctypes as C
-        from . import _lib
         lib = _lib.load()
         logits, values = logits.contiguous(), values.contiguous()
         B, BV = logits.shape[0], values.shape[0]
@@ -1063,22 +1010,24 @@ def ppo_loss(model, obs, merged, act, old_logp, adv, ret, clip_eps, ent_coef, vf
 class FlatBucket:
     """All parameters of a module re-homed as views into one flat fp32 buffer; same for the gradients.
     The data-parallel exchange is then ONE all-reduce of `grad` per optimizer step (2.6 M params = 10.5 MB on
-    smallCapture: latency-bound on xGMI, so one message beats many)."""
+    smallCapture: latency-bound on xGMI, so one message beats many).
+    `names` are the parameters' names in bucket order, `offsets[i]:offsets[i + 1]` is parameter i's slice of the flat buffers."""
 
     def __init__(self, module):
-        params = [p for p in module.parameters() if p.requires_grad]
-        self.numel = sum(p.numel() for p in params)
+        named = [(n, p) for n, p in module.named_parameters() if p.requires_grad]
+        self.names = [n for n, _ in named]
+        self.params = params = [p for _, p in named]
+        self.offsets = [0]
+        for p in params:
+            self.offsets.append(self.offsets[-1] + p.numel())
+        self.numel = self.offsets[-1]
         dev, dt = params[0].device, params[0].dtype
         self.data = torch.empty(self.numel, device=dev, dtype=dt)
         self.grad = torch.zeros(self.numel, device=dev, dtype=dt)
-        off = 0
-        for p in params:
-            n = p.numel()
-            self.data[off:off + n].copy_(p.data.reshape(-1))
-            p.data = self.data[off:off + n].view_as(p)
-            p.grad = self.grad[off:off + n].view_as(p)
-            off += n
-        self.params = params
+        for p, a, b in zip(params, self.offsets, self.offsets[1:]):
+            self.data[a:b].copy_(p.data.reshape(-1))
+            p.data = self.data[a:b].view_as(p)
+            p.grad = self.grad[a:b].view_as(p)
 
 
 class PPOLearner:
@@ -1101,32 +1050,19 @@ class PPOLearner:
         # collective path on a one-rank group (bench.py on a one-GPU box)
         self.dp = world_size > 1 or bool(force_collectives)
         self.autocast_dtype = autocast_dtype
-        self._w16 = None
-        self._sh16 = None
-        self._shadow_views = None
-        self._graph = self._graphs = None
-
-    def enable_bf16_flat(self):
-        """Manual mixed precision instead of autocast for the optimizer step: the network runs on ONE flat bfloat16 copy of
-        the float32 master weights (refreshed by one cast kernel per step) whose slices are the functional parameters, so
-        that autograd delivers the whole gradient as one flat bfloat16 tensor (the backward of torch.split is a single
-        concatenation).  This removes what autocast costs per step on this network: ~47 weight casts, ~46 gradient
-        casts back to float32, ~78 accumulate-into-.grad adds and the gradient memset -- about 170 of ~450 launches.  Every
-        parameter receives exactly one gradient contribution, and under autocast that contribution was computed in
-        bfloat16 as well, so storing it in bfloat16 loses nothing; master weights, Adam moments and EMA stay float32."""
-        assert self.bucket.data.is_cuda, "the flat bfloat16 path is a GPU path"
-        self._names = [n for n, p in self.model.named_parameters() if p.requires_grad]
-        self._sizes = [p.numel() for p in self.bucket.params]
-        self._shapes = [tuple(p.shape) for p in self.bucket.params]
-        self._w16 = self.bucket.data.to(torch.bfloat16).requires_grad_(True)
-        self.autocast_dtype = None
-
-    def _loss_bf16_flat(self, obs, merged, act, old_logp, adv, ret, clip_eps, ent_coef):
-        from types import SimpleNamespace
-        parts = torch.split(self._w16, self._sizes)
-        pd = {n: t.view(sh) for n, t, sh in zip(self._names, parts, self._shapes)}
-        fm = SimpleNamespace(evaluate=lambda o, m, a: torch.func.functional_call(self.model, pd, (o, m, a)))
-        return ppo_loss(fm, obs, merged, act, old_logp, adv, ret, clip_eps, ent_coef)
+        self._offsets = self.bucket.offsets
+        # the actor's parameters (a contiguous prefix of the bucket), then the critic's: see _grad_groups
+        n, n_actor = len(self.bucket.params), 0
+        while n_actor < n and self.bucket.names[n_actor].startswith("actor_"):
+            n_actor += 1
+        self._groups = [(0, n_actor), (n_actor, n)] if 0 < n_actor < n else [(0, n)]
+        # the bfloat16 copy of the bucket and what hangs on it (_shadow_context), made on the first bf16 step on the GPU
+        self._sh16 = self._shadow_slots = self._shadow_views = None
+        self._bf16_fresh = False                                         # the optimizer kernel has just written _sh16
+        self._opt_scratch = self._opt_norm = None                        # _fused_tail's buffers, made on its first call
+        # the captured step (capture): graph(s), static inputs, device scalars, the stats it returns, running report sums
+        self._graph = self._graphs = self._g_groups = None
+        self._g_in = self._g_sc = self._g_stats = self._g_acc = self._g_acc_keys = self._g_batch = None
 
     # the second-stage row sums of the gradient reductions folded into the gradient gather (mappo._row_sums_deferred): eight small
     # launches less on the chains of the 512-sample step.  (A first version ran them on a third stream beside the next backward kernel
@@ -1138,19 +1074,28 @@ class PPOLearner:
         together, in the order the backward pass is run: the actor's parameters (a contiguous prefix of the bucket that holds
         97 % of its bytes: the 4928 -> 512 head), then the critic's.  Data parallel, the actor's slice is reduced while the critic's
         backward runs.  One range when nothing is exchanged."""
-        n = len(self.bucket.params)
-        if not (self.dp and self._w16 is None):
-            return [(0, n)]
-        if getattr(self, "_groups", None) is None:
-            names = [k for k, p in self.model.named_parameters() if p.requires_grad]
-            n_actor = 0
-            while n_actor < n and names[n_actor].startswith("actor_"):
-                n_actor += 1
-            self._groups = [(0, n_actor), (n_actor, n)] if 0 < n_actor < n else [(0, n)]
-            self._offsets = [0]
-            for p in self.bucket.params:
-                self._offsets.append(self._offsets[-1] + p.numel())
-        return self._groups
+        return self._groups if self.dp else [(0, len(self.bucket.params))]
+
+    def _gather_grads(self, flat, first):
+        """pmx_flatten_sum_to_f32: the float32 / bfloat16 gradients `flat` into the float32 bucket from element `first` on, in one
+        launch; gradients that are still partial rows (mappo._row_sums_deferred) are summed on the way."""
+        lib = _lib.load()
+        n = len(flat)
+        if any(not g.is_contiguous() for g in flat):
+            flush_pending_rows()                             # (a copy would read rows that have not been added yet)
+            flat = [g.contiguous() for g in flat]
+        src = (C.c_void_p * n)(*[g.data_ptr() for g in flat])
+        isb = (C.c_uint8 * n)(*[1 if g.dtype == torch.bfloat16 else 0 for g in flat])
+        cnt = (C.c_int32 * n)(*[g.numel() for g in flat])
+        pend = [pending_rows_of(g.data_ptr()) if g.dtype == torch.float32 else (0, 0) for g in flat]
+        rows = (C.c_int32 * n)(*[r for r, _ in pend])
+        stride = (C.c_int32 * n)(*[f for _, f in pend])
+        offs, o = [], first
+        for g in flat:
+            offs.append(o); o += g.numel()
+        off = (C.c_int64 * n)(*offs)
+        st = C.c_void_p(torch.cuda.current_stream(self.bucket.grad.device).cuda_stream)
+        _lib.check(lib.pmx_flatten_sum_to_f32(n, src, isb, rows, stride, off, cnt, self.bucket.grad.data_ptr(), st), "pmx_flatten_sum_to_f32")
 
     def _backward_group(self, loss, lo, hi, retain):
         """Gradients of bucket.params[lo:hi] into their slice of the flat float32 bucket: one gathering copy instead of
@@ -1162,54 +1107,32 @@ class PPOLearner:
             for i, v in self._shadow_views.items():
                 if lo <= i < hi:
                     targets[i - lo] = v                  # the bfloat16 copy the library op multiplied by
-        dev = self.bucket.grad.device
-        flat_ok = dev.type == "cuda" and all(t.dtype in (torch.float32, torch.bfloat16) for t in targets)     # (the gather below)
-        prev, _DEFER_ROW_SUMS[0] = _DEFER_ROW_SUMS[0], bool(self.defer_row_sums and flat_ok)
+        grad = self.bucket.grad
+        # the gathering kernel applies: a float32 bucket on the GPU, gradients float32 or bfloat16 (autograd hands every gradient
+        # out in its target's type).  Only then may the backward kernels leave partial rows behind for it.
+        gather = grad.is_cuda and grad.dtype == torch.float32 and all(t.dtype in (torch.float32, torch.bfloat16) for t in targets)
+        prev, _DEFER_ROW_SUMS[0] = _DEFER_ROW_SUMS[0], bool(self.defer_row_sums and gather)
         _PENDING_ROWS.clear()                                # (nothing of an earlier, failed call may match this one's addresses)
         root, unit = loss_root(loss)
         try:
             grads = torch.autograd.grad(root, targets, grad_outputs=unit, allow_unused=True, retain_graph=retain)
         finally:
             _DEFER_ROW_SUMS[0] = prev
-        flat = [g.reshape(-1) if g is not None else torch.zeros(p.numel(), dtype=self.bucket.grad.dtype, device=dev)
+        flat = [g.reshape(-1) if g is not None else torch.zeros(p.numel(), dtype=grad.dtype, device=grad.device)
                 for g, p in zip(grads, params)]
-        first = sum(p.numel() for p in self.bucket.params[:lo])
-        if not (dev.type == "cuda" and all(g.dtype in (torch.float32, torch.bfloat16) for g in flat)):
-            flush_pending_rows()
-        if dev.type == "cuda" and all(g.dtype in (torch.float32, torch.bfloat16) for g in flat):
-            import ctypes as C
-            from . import _lib
-            lib = _lib.load()
-            n = len(flat)
-            if any(not g.is_contiguous() for g in flat):
-                flush_pending_rows()                         # (a copy would read rows that have not been added yet)
-            flat = [g.contiguous() for g in flat]
-            src = (C.c_void_p * n)(*[g.data_ptr() for g in flat])
-            isb = (C.c_uint8 * n)(*[1 if g.dtype == torch.bfloat16 else 0 for g in flat])
-            cnt = (C.c_int32 * n)(*[g.numel() for g in flat])
-            # gradients that are still partial rows (mappo._row_sums_deferred): the gather adds them
-            pend = [pending_rows_of(g.data_ptr()) if g.dtype == torch.float32 else (0, 0) for g in flat]
-            rows = (C.c_int32 * n)(*[r for r, _ in pend])
-            stride = (C.c_int32 * n)(*[f for _, f in pend])
-            offs, o = [], first
-            for g in flat:
-                offs.append(o); o += g.numel()
-            off = (C.c_int64 * n)(*offs)
-            st = C.c_void_p(torch.cuda.current_stream(dev).cuda_stream)
-            _lib.check(lib.pmx_flatten_sum_to_f32(n, src, isb, rows, stride, off, cnt, self.bucket.grad.data_ptr(), st), "pmx_flatten_sum_to_f32")
+        if gather:
+            self._gather_grads(flat, self._offsets[lo])
             _PENDING_ROWS.clear()
         else:
-            total = sum(g.numel() for g in flat)
-            torch.cat([g.to(self.bucket.grad.dtype) for g in flat], out=self.bucket.grad[first:first + total])
+            flush_pending_rows()
+            torch.cat([g.to(grad.dtype) for g in flat], out=grad[self._offsets[lo]:self._offsets[hi]])
 
     def _reduce_slice(self, lo, hi):
         """Starts the all-reduce (mean over ranks) of the gradient slice of bucket.params[lo:hi]; returns a closure that makes the
         current stream wait for it and finishes the mean.  RCCL averages in the collective; gloo (the CPU tests) sums, and the
         division follows."""
-        import torch.distributed as dist
-        self._grad_groups()
-        a, b = (self._offsets[lo], self._offsets[hi]) if getattr(self, "_offsets", None) else (0, self.bucket.numel)
-        sl = self.bucket.grad[a:b]
+        import torch.distributed as dist                     # optional
+        sl = self.bucket.grad[self._offsets[lo]:self._offsets[hi]]
         avg = self.bucket.grad.is_cuda
         h = dist.all_reduce(sl, op=dist.ReduceOp.AVG if avg else dist.ReduceOp.SUM, group=self.pg, async_op=True)
 
@@ -1222,13 +1145,6 @@ class PPOLearner:
     def _backward_into_bucket(self, loss):
         """The backward pass with the gradient ending up in the flat float32 bucket and, under data parallelism, averaged over the
         ranks: group by group, each group's all-reduce in flight while the next group's backward runs."""
-        if self._w16 is not None:
-            root, unit = loss_root(loss)
-            (g16,) = torch.autograd.grad(root, (self._w16,), grad_outputs=unit)
-            self.bucket.grad.copy_(g16)
-            if self.dp:
-                self._reduce_slice(0, len(self.bucket.params))()
-            return
         groups = self._grad_groups()
         pending = []
         for k, (lo, hi) in enumerate(groups):
@@ -1239,13 +1155,10 @@ class PPOLearner:
             fin()
 
     def _refresh_bf16(self):
-        if getattr(self, "_bf16_fresh", False):               # the optimizer kernel has just written the (one) copy
+        """The bfloat16 copy follows the float32 weights (unless the optimizer kernel has just written it)."""
+        if self._bf16_fresh:
             self._bf16_fresh = False
-            return
-        if self._w16 is not None:
-            with torch.no_grad():
-                self._w16.copy_(self.bucket.data)
-        if self._sh16 is not None:
+        elif self._sh16 is not None:
             with torch.no_grad():
                 self._sh16.copy_(self.bucket.data)
 
@@ -1268,26 +1181,28 @@ class PPOLearner:
 
     def _shadow_context(self):
         """Context manager under which the module's library-op parameters are their bfloat16 shadows (and a no-op when the
-        shadows do not apply: CPU, float32 steps, the flat-bf16 mode)."""
-        import contextlib
-        if not (self.shadow_weights and self.autocast_dtype == torch.bfloat16 and self._w16 is None and self.bucket.data.is_cuda):
+        shadows do not apply: CPU, float32 steps)."""
+        if not (self.shadow_weights and self.autocast_dtype == torch.bfloat16 and self.bucket.data.is_cuda):
             self._shadow_views = None
             return contextlib.nullcontext()
         if self._sh16 is None:
             self._sh16 = self.bucket.data.to(torch.bfloat16).requires_grad_(True)
-            names = [n for n, p in self.model.named_parameters() if p.requires_grad]
-            self._shadow_slots, off = [], 0
-            for i, (n, p) in enumerate(zip(names, self.bucket.params)):
-                if n.startswith(self._shadowed_prefixes()):
-                    self._shadow_slots.append((i, n, off, p.numel(), tuple(p.shape)))
-                off += p.numel()
+            keep = self._shadowed_prefixes()
+            self._shadow_slots = [(i, n) for i, n in enumerate(self.bucket.names) if n.startswith(keep)]
         self._shadow_views, pd = {}, {}
-        for i, n, off, k, shape in self._shadow_slots:
-            v = self._sh16[off:off + k].view(shape)
+        for i, n in self._shadow_slots:
+            v = self._sh16[self._offsets[i]:self._offsets[i + 1]].view(self.bucket.params[i].shape)
             self._shadow_views[i] = v
             pd[n] = v
-        from torch.nn.utils import stateless
         return stateless._reparametrize_module(self.model, pd)
+
+    def _loss(self, obs, merged, act, old_logp, adv, ret, clip_eps, ent_coef):
+        """ppo_loss in the learner's precision: under autocast with the bfloat16 shadow weights in place, or in plain float32."""
+        if self.autocast_dtype is None:
+            self._shadow_views = None
+            return ppo_loss(self.model, obs, merged, act, old_logp, adv, ret, clip_eps, ent_coef)
+        with self._shadow_context(), torch.autocast(device_type=self.bucket.data.device.type, dtype=self.autocast_dtype):
+            return ppo_loss(self.model, obs, merged, act, old_logp, adv, ret, clip_eps, ent_coef)
 
     def set_lr(self, lr):
         self.lr = lr
@@ -1304,18 +1219,27 @@ class PPOLearner:
         denom = (self.exp_avg_sq.sqrt() / math.sqrt(bc2)).add_(self.eps)
         p.addcdiv_(self.exp_avg, denom, value=-self.lr / bc1)
 
+    def _torch_tail(self):
+        """clip_grad_norm_(parameters, 0.5) -> Adam -> EMA as torch ops (the CPU, and what the fused tail is tested against);
+        returns the gradient norm.  The norm is the 2-norm of the per-tensor 2-norms (the reference's summation order; a single
+        fp32 reduction over the 2.6 M-element flat buffer is measurably less accurate on the CPU); the gradient is scaled by
+        max_norm / (norm + 1e-6) if that is < 1."""
+        gn = torch.linalg.vector_norm(torch.stack(torch._foreach_norm([p.grad for p in self.bucket.params])))
+        self.bucket.grad.mul_(torch.clamp(MAX_GRAD_NORM / (gn + 1e-6), max=1.0))
+        self._adam_step()
+        self.ema.mul_(EMA_DECAY).add_(self.bucket.data, alpha=1 - EMA_DECAY)
+        return gn
+
     fused_optimizer = True   # clip + Adam + EMA as two launches on the GPU (pmx_clip_adam_ema) instead of ~18 torch kernels
 
     def _fused_tail(self, scalars_dev=None, reports5=None, report_sums6=None):
         """clip_grad_norm_ -> Adam -> EMA through pmx_clip_adam_ema_tail; returns the gradient norm (a 0-dim device tensor).  With
         scalars_dev the bias-corrected step sizes are read from that device tensor (graph replay), else computed here from
         step_count, which the caller has already advanced.  The same launch refreshes the bfloat16 copy of the parameters (where
-        there is exactly one) and, given report_sums6, adds the objective's five scalars and the gradient norm to it."""
-        import ctypes as C
-        from . import _lib
+        there is one) and, given report_sums6, adds the objective's five scalars and the gradient norm to it."""
         lib = _lib.load()
         dev = self.bucket.data.device
-        if getattr(self, "_opt_scratch", None) is None:
+        if self._opt_scratch is None:
             self._opt_scratch = torch.empty(_lib.OPT_PARTIALS, dtype=torch.float64, device=dev)
             self._opt_norm = torch.zeros(1, dtype=torch.float32, device=dev)
         b1, b2 = self.betas
@@ -1325,15 +1249,13 @@ class PPOLearner:
         else:
             sp, a, b = scalars_dev.data_ptr(), 0.0, 0.0
         st = C.c_void_p(torch.cuda.current_stream(dev).cuda_stream)
-        copies = [t for t in (self._w16, self._sh16) if t is not None]
-        p16 = copies[0] if len(copies) == 1 and copies[0].is_contiguous() and copies[0].numel() == self.bucket.numel else None
         _lib.check(lib.pmx_clip_adam_ema_tail(self.bucket.grad.data_ptr(), self.bucket.data.data_ptr(), self.exp_avg.data_ptr(),
                                               self.exp_avg_sq.data_ptr(), self.ema.data_ptr(), self.bucket.numel, self._opt_scratch.data_ptr(),
                                               sp, a, b, b1, b2, self.eps, MAX_GRAD_NORM, EMA_DECAY, self._opt_norm.data_ptr(),
-                                              p16.data_ptr() if p16 is not None else None,
+                                              self._sh16.data_ptr() if self._sh16 is not None else None,
                                               reports5.data_ptr() if reports5 is not None else None,
                                               report_sums6.data_ptr() if report_sums6 is not None else None, st), "pmx_clip_adam_ema_tail")
-        self._bf16_fresh = p16 is not None
+        self._bf16_fresh = self._sh16 is not None
         return self._opt_norm[0]
 
     def _use_fused_tail(self):
@@ -1341,38 +1263,34 @@ class PPOLearner:
                 and self.bucket.grad.is_contiguous() and self.bucket.data.is_contiguous())
 
     def update_minibatch(self, obs, merged, act, old_logp, adv, ret, clip_eps=CLIP_EPS, ent_coef=ENT_COEF_START):
-        dev_type = self.bucket.data.device.type
-        if self._w16 is not None:
-            loss, stats = self._loss_bf16_flat(obs, merged, act, old_logp, adv, ret, clip_eps, ent_coef)
-        elif self.autocast_dtype is not None:
-            with self._shadow_context(), torch.autocast(device_type=dev_type, dtype=self.autocast_dtype):
-                loss, stats = ppo_loss(self.model, obs, merged, act, old_logp, adv, ret, clip_eps, ent_coef)
-        else:
-            self._shadow_views = None
-            loss, stats = ppo_loss(self.model, obs, merged, act, old_logp, adv, ret, clip_eps, ent_coef)
+        loss, stats = self._loss(obs, merged, act, old_logp, adv, ret, clip_eps, ent_coef)
         self._backward_into_bucket(loss)                  # (data parallel: includes the gradient all-reduce)
-        # clip_grad_norm_(parameters, 0.5): 2-norm of the per-tensor 2-norms (the reference's summation order; a single
-        # fp32 reduction over the 2.6 M-element flat buffer is measurably less accurate on the CPU), then scale by
-        # max_norm / (norm + 1e-6) if that is < 1
         if self._use_fused_tail():
             self.step_count += 1
             gn = self._fused_tail().clone()
         else:
-            gn = torch.linalg.vector_norm(torch.stack(torch._foreach_norm([p.grad for p in self.bucket.params])))
-            self.bucket.grad.mul_(torch.clamp(MAX_GRAD_NORM / (gn + 1e-6), max=1.0))
-            self._adam_step()
-            self.ema.mul_(EMA_DECAY).add_(self.bucket.data, alpha=1 - EMA_DECAY)
+            gn = self._torch_tail()
         self._refresh_bf16()
         stats["grad_norm"] = gn.detach()
         return stats
+
+    def snapshot(self):
+        """Copies of everything an optimizer step changes: weights, both Adam moments, the EMA, the step count."""
+        return {"data": self.bucket.data.clone(), "exp_avg": self.exp_avg.clone(), "exp_avg_sq": self.exp_avg_sq.clone(),
+                "ema": self.ema.clone(), "step": self.step_count}
+
+    def restore(self, snap):
+        """Back to a snapshot() (or to a checkpoint with the same keys); the bfloat16 copy follows the weights."""
+        for t, k in ((self.bucket.data, "data"), (self.exp_avg, "exp_avg"), (self.exp_avg_sq, "exp_avg_sq"), (self.ema, "ema")):
+            t.copy_(snap[k])
+        self.step_count = int(snap["step"])
+        self._refresh_bf16()
 
     # ---- hipGraph capture of the whole optimizer step (launch-bound at the reference's minibatch of 512) ----------
     @staticmethod
     def graph_replay_safe():
         """hipGraph replay is only trusted with ROCclr's AQL packet capture switched off, and only if the runtime can have
         read the switch: set before HIP initialised (see the package __init__, which records that at import)."""
-        import os
-        import sys
         pkg = sys.modules.get(__name__.rsplit(".", 1)[0])
         return os.environ.get("DEBUG_CLR_GRAPH_PACKET_CAPTURE") == "0" and bool(getattr(pkg, "GRAPH_REPLAY_OK", False))
 
@@ -1383,60 +1301,21 @@ class PPOLearner:
         if not self.graph_replay_safe():
             raise RuntimeError("hipGraph replay of the optimizer step needs DEBUG_CLR_GRAPH_PACKET_CAPTURE=0 in the environment "
                                "before HIP initialises (ROCm 7 graph packet-capture bug, DESIGN.md section 5)")
+        if not self._use_fused_tail():
+            raise RuntimeError("the captured optimizer step ends in the fused clip + Adam + EMA kernel (pmx_clip_adam_ema_tail): it needs "
+                               "fused_optimizer and contiguous float32 buckets on the GPU")
         dev = self.bucket.data.device
-        self._g_in = dict(obs=torch.zeros((batch,) + tuple(obs_shape), dtype=in_dtype, device=dev),
-                          merged=torch.zeros((merged_batch or batch,) + tuple(obs_shape), dtype=in_dtype, device=dev),
-                          act=torch.zeros(batch, dtype=torch.int64, device=dev),
-                          logp=torch.zeros(batch, dtype=torch.float32, device=dev),
-                          adv=torch.randn(batch, dtype=torch.float32, device=dev),
-                          ret=torch.zeros(batch, dtype=torch.float32, device=dev))
+        i = self._g_in = dict(obs=torch.zeros((batch,) + tuple(obs_shape), dtype=in_dtype, device=dev),
+                              merged=torch.zeros((merged_batch or batch,) + tuple(obs_shape), dtype=in_dtype, device=dev),
+                              act=torch.zeros(batch, dtype=torch.int64, device=dev),
+                              logp=torch.zeros(batch, dtype=torch.float32, device=dev),
+                              adv=torch.randn(batch, dtype=torch.float32, device=dev),
+                              ret=torch.zeros(batch, dtype=torch.float32, device=dev))
         # lr/bc1, 1/sqrt(bc2), clip_eps, ent_coef as device scalars
         self._g_sc = torch.zeros(4, dtype=torch.float32, device=dev)
         self._g_stats = None
         self._g_acc = torch.zeros(6, dtype=torch.float32, device=dev)       # sums of (pg, vl, entropy, clip_frac, loss, grad_norm)
-
-        def seg_loss():
-            i = self._g_in
-            if self._w16 is not None:
-                loss, stats = self._loss_bf16_flat(i["obs"], i["merged"], i["act"], i["logp"], i["adv"], i["ret"],
-                                                   self._g_sc[2], self._g_sc[3])
-            elif self.autocast_dtype is not None:
-                with self._shadow_context(), torch.autocast(device_type=dev.type, dtype=self.autocast_dtype):
-                    loss, stats = ppo_loss(self.model, i["obs"], i["merged"], i["act"], i["logp"], i["adv"], i["ret"],
-                                           self._g_sc[2], self._g_sc[3])
-            else:
-                self._shadow_views = None
-                loss, stats = ppo_loss(self.model, i["obs"], i["merged"], i["act"], i["logp"], i["adv"], i["ret"],
-                                       self._g_sc[2], self._g_sc[3])
-            return loss, stats
-
         REPORTS = ("pg", "vl", "entropy", "clip_frac", "loss")
-
-        def seg_tail(stats):
-            # the fused objective's 5-vector (ppo_loss leaves it on the loss): with it the optimizer kernel keeps the running sums
-            s5 = getattr(state.get("loss"), "_pmx_stats", None)
-            in_kernel = self._use_fused_tail() and s5 is not None and tuple(stats.keys()) == REPORTS and s5.dtype == torch.float32
-            if self._use_fused_tail():
-                gn = self._fused_tail(self._g_sc, *((s5.detach(), self._g_acc) if in_kernel else ()))
-            else:
-                self._g_norms = torch.stack(torch._foreach_norm([p.grad for p in self.bucket.params]))   # kept: per-tensor norms
-                gn = torch.linalg.vector_norm(self._g_norms)
-                self.bucket.grad.mul_(torch.clamp(MAX_GRAD_NORM / (gn + 1e-6), max=1.0))
-                b1, b2 = self.betas
-                g, p = self.bucket.grad, self.bucket.data
-                self.exp_avg.lerp_(g, 1 - b1)
-                self.exp_avg_sq.mul_(b2).addcmul_(g, g, value=1 - b2)
-                denom = (self.exp_avg_sq.sqrt() * self._g_sc[1]).add_(self.eps)
-                p.sub_(self.exp_avg / denom * self._g_sc[0])
-                self.ema.mul_(EMA_DECAY).add_(p, alpha=1 - EMA_DECAY)
-            self._refresh_bf16()
-            stats["grad_norm"] = gn
-            # running sums of the step's reports, inside the graph: a caller that averages them over an update reads ONE tensor at
-            # the end instead of launching an add per report and step
-            self._g_acc_keys = tuple(stats.keys())
-            if not in_kernel:
-                self._g_acc.add_(torch.stack([stats[k].float() for k in self._g_acc_keys]))
-            return stats
 
         # Data parallel: the collectives stay OUTSIDE the graphs (eager RCCL calls), so the step is recorded as two graphs:
         #   graph 0: forward, loss, whole backward, gradients into the bucket      | then ONE all-reduce of the whole bucket
@@ -1446,25 +1325,34 @@ class PPOLearner:
         # (one graph per gradient group: 1 800 against 1 300 steps/s at 512 samples on one GPU).  The eager step still reduces
         # slice by slice (_backward_into_bucket).
         n = len(self.bucket.params)
-        state = {}
 
         def seg_first():
-            state["loss"], state["stats"] = seg_loss()
-            if self._w16 is not None:
-                root, unit = loss_root(state["loss"])
-                (g16,) = torch.autograd.grad(root, (self._w16,), grad_outputs=unit)
-                self.bucket.grad.copy_(g16)
-            else:
-                self._backward_group(state["loss"], 0, n, retain=False)
+            loss, stats = self._loss(i["obs"], i["merged"], i["act"], i["logp"], i["adv"], i["ret"], self._g_sc[2], self._g_sc[3])
+            self._backward_group(loss, 0, n, retain=False)
+            return loss, stats
+
+        def seg_tail(loss, stats):
+            # the fused objective's 5-vector (ppo_loss leaves it on the loss): with it the optimizer kernel keeps the running sums
+            s5 = getattr(loss, "_pmx_stats", None)
+            in_kernel = s5 is not None and tuple(stats.keys()) == REPORTS and s5.dtype == torch.float32
+            gn = self._fused_tail(self._g_sc, *((s5.detach(), self._g_acc) if in_kernel else ()))
+            self._refresh_bf16()
+            stats["grad_norm"] = gn
+            # running sums of the step's reports, inside the graph: a caller that averages them over an update reads ONE tensor at
+            # the end instead of launching an add per report and step
+            self._g_acc_keys = tuple(stats.keys())
+            if not in_kernel:
+                self._g_acc.add_(torch.stack([stats[k].float() for k in self._g_acc_keys]))
+            return stats
 
         def run_eager():
-            seg_first()
+            out = seg_first()
             if self.dp:
                 self._reduce_slice(0, n)()
-            return seg_tail(state["stats"])
+            return seg_tail(*out)
 
         # warm up on a side stream (allocator, MIOpen solver search), restoring the optimizer state afterwards
-        saved = [t.clone() for t in (self.bucket.data, self.exp_avg, self.exp_avg_sq, self.ema)]
+        saved = self.snapshot()
         self._set_graph_scalars(clip_eps, ent_coef, step=1)
         s = torch.cuda.Stream(device=dev)
         s.wait_stream(torch.cuda.current_stream(dev))
@@ -1473,35 +1361,31 @@ class PPOLearner:
                 run_eager()
         torch.cuda.current_stream(dev).wait_stream(s)
         torch.cuda.synchronize(dev)
-        state.clear()
         # Capture in THREAD-LOCAL error mode: in the default (global) mode a capture in progress forbids "unsafe" runtime calls from
         # every thread of the process -- and ProcessGroupNCCL's watchdog thread polls the events of recent collectives with
         # hipEventQuery, which then fails with hipErrorStreamCaptureUnsupported and takes the process down (seen when a capture began
         # right behind the warm-up steps' all-reduces).  This thread makes no such call while it captures; other threads' launches on
         # the capturing streams (autograd's workers) are recorded either way.  The pause lets the watchdog retire what has completed.
         if self.dp:
-            import time as _time
-            _time.sleep(0.25)
+            time.sleep(0.25)
         tl = dict(capture_error_mode="thread_local")
         if not self.dp:
             self._graph = torch.cuda.CUDAGraph()
             self._graphs = None
             with torch.cuda.graph(self._graph, **tl):
-                seg_first()
-                self._g_stats = seg_tail(state["stats"])
+                out = seg_first()
+                self._g_stats = seg_tail(*out)
         else:
             g0, g1 = torch.cuda.CUDAGraph(), torch.cuda.CUDAGraph()
             with torch.cuda.graph(g0, **tl):
-                seg_first()
+                out = seg_first()
             with torch.cuda.graph(g1, pool=g0.pool(), **tl):
-                self._g_stats = seg_tail(state["stats"])
+                self._g_stats = seg_tail(*out)
             self._graphs = [g0, g1]
             self._graph = None
             self._g_groups = [(0, n)]           # the gradient range the replayed step reduces (bench.py reports it)
-        state.clear()
-        for t, v in zip((self.bucket.data, self.exp_avg, self.exp_avg_sq, self.ema), saved):
-            t.copy_(v)
-        self._refresh_bf16()
+        del out
+        self.restore(saved)
         self._g_batch = batch
 
     def _replay(self):
@@ -1520,19 +1404,20 @@ class PPOLearner:
         return tuple(float(v) for v in (self.lr / bc1, 1.0 / math.sqrt(bc2), clip_eps, ent_coef))
 
     def _set_graph_scalars(self, clip_eps, ent_coef, step):
-        vals = self._graph_scalar_values(clip_eps, ent_coef, step)
-        if self._g_sc.is_cuda:
-            # the four values travel as kernel arguments of ONE launch: stream-ordered, no host staging buffer that could be
-            # recycled while a copy is still in flight
-            import ctypes as C
-            from . import _lib
-            lib = _lib.load()
-            arr = (C.c_float * 4)(*[float(v) for v in vals])
-            st = C.c_void_p(torch.cuda.current_stream(self._g_sc.device).cuda_stream)
-            _lib.check(lib.pmx_set_floats(self._g_sc.data_ptr(), arr, 4, st), "pmx_set_floats")
-            return
-        for k, v in enumerate(vals):
-            self._g_sc[k].fill_(float(v))
+        """The four values travel as kernel arguments of ONE launch: stream-ordered, no host staging buffer that could be
+        recycled while a copy is still in flight."""
+        lib = _lib.load()
+        arr = (C.c_float * 4)(*self._graph_scalar_values(clip_eps, ent_coef, step))
+        st = C.c_void_p(torch.cuda.current_stream(self._g_sc.device).cuda_stream)
+        _lib.check(lib.pmx_set_floats(self._g_sc.data_ptr(), arr, 4, st), "pmx_set_floats")
+
+    def reset_report_sums(self):
+        """Zeroes the running sums that the replayed steps keep of their reports."""
+        self._g_acc.zero_()
+
+    def report_sums(self):
+        """{report: its sum over the replayed steps since reset_report_sums()} -- 0-dim views of one device tensor."""
+        return {k: self._g_acc[j] for j, k in enumerate(self._g_acc_keys)}
 
     def update_minibatch_graph(self, obs, merged, act, old_logp, adv, ret, clip_eps=CLIP_EPS, ent_coef=ENT_COEF_START):
         """Same step as update_minibatch, replayed from the captured graph (inputs are copied into its static buffers)."""
@@ -1549,8 +1434,6 @@ class PPOLearner:
         static inputs: sources = the flat rollout tensors {obs, merged, act, logp, adv, ret} (rows = samples; merged rows =
         env-ticks), index = int64 device indices, rows_per_index = {name: m} (2 for the per-learner tensors of a paired
         minibatch whose index names env-tick pairs).  Returns the graph's stats tensors (valid until the next replay)."""
-        import ctypes as C
-        from . import _lib
         lib = _lib.load()
         names = ("obs", "merged", "act", "logp", "adv", "ret")
         n = len(names)
@@ -1575,12 +1458,8 @@ class PPOLearner:
     def ema_state_dict(self):
         """state_dict of the EMA weights with the reference's parameter names (what :647-651 saves)."""
         sd = {k: v.clone() for k, v in self.model.state_dict().items()}
-        off = 0
-        names = [n for n, p in self.model.named_parameters() if p.requires_grad]
-        for n, p in zip(names, self.bucket.params):
-            k = p.numel()
-            sd[n] = self.ema[off:off + k].view_as(p).clone()
-            off += k
+        for n, p, a, b in zip(self.bucket.names, self.bucket.params, self._offsets, self._offsets[1:]):
+            sd[n] = self.ema[a:b].view_as(p).clone()
         return sd
 
 

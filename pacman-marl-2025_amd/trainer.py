@@ -80,7 +80,7 @@ def canonicalize_obs(o):
 class VecMAPPOTrainer:
     def __init__(self, layout, n_envs, horizon=32, minibatch=512, epochs=UPDATE_EPOCHS, obs_dtype=None,
                  device="cuda:0", seed=0, rank=0, world_size=1, process_group=None, total_updates=2000, length=300,
-                 use_autocast=True, opponent="random", use_graph=False, algorithm="mappo", paired_minibatches=True, flat_bf16=False, curriculum_scale=1.0,
+                 use_autocast=True, opponent="random", use_graph=False, algorithm="mappo", paired_minibatches=True, curriculum_scale=1.0,
                  env=None, redraw_layouts=False, force_collectives=False, hard_bots=("baseline",)):
         self.device = torch.device(device)
         self.rank, self.world_size = rank, world_size
@@ -130,10 +130,6 @@ class VecMAPPOTrainer:
             import torch.distributed as dist
             dist.broadcast(self.learner.bucket.data, src=0, group=process_group)
             self.learner.ema.copy_(self.learner.bucket.data)
-        if flat_bf16:       # optimizer step on one flat bfloat16 weight copy instead of autocast (PPOLearner.enable_bf16_flat)
-            if not use_autocast:
-                raise ValueError("flat_bf16 is the bfloat16 training path; it replaces autocast in the optimizer step")
-            self.learner.enable_bf16_flat()
         self.opponent_model = mappo.MAPPOAgent(self.obs_shape, 5, 2).to(self.device)
         self.opponent_model.load_state_dict(self.model.state_dict())
         self.opponent_model.eval()
@@ -313,8 +309,7 @@ class VecMAPPOTrainer:
         gather = bool(self.use_graph and self.graph_gather and self.paired and self.device.type == "cuda" and S % self.minibatch == 0
                       and self._net_in(obs[:1]).dtype == obs.dtype and self._net_in(merged[:1]).dtype == merged.dtype)
         if self.use_graph:      # a bad replay must not leave NaNs in the weights, the Adam moments and the EMA: keep a copy to go back to
-            L = self.learner
-            snap = [t.clone() for t in (L.bucket.data, L.exp_avg, L.exp_avg_sq, L.ema)] + [L.step_count]
+            snap = self.learner.snapshot()
         for _ in range(self.epochs):
             if self.paired:
                 pperm = torch.randperm(S // 2, device=self.device, generator=self.gen)
@@ -332,7 +327,7 @@ class VecMAPPOTrainer:
                 if gather:
                     # replayed step, paired minibatch: one gather launch into the graph's inputs, reports summed inside the graph
                     if steps == 0:
-                        self.learner._g_acc.zero_()
+                        self.learner.reset_report_sums()
                     self.learner.update_minibatch_graph_gather(
                         {"obs": obs, "merged": merged, "act": act, "logp": logp, "adv": adv, "ret": ret}, pr,
                         {"obs": 2, "merged": 1, "act": 2, "logp": 2, "adv": 2, "ret": 2}, clip_eps, ent_coef)
@@ -351,15 +346,10 @@ class VecMAPPOTrainer:
             if max_steps is not None and steps >= max_steps:
                 break
         if gather:
-            acc = self.learner._g_acc / steps
-            agg = {k: acc[i] * steps for i, k in enumerate(self.learner._g_acc_keys)}
+            agg = self.learner.report_sums()
         self.stats.update({k: v / steps for k, v in agg.items()})
         if self.use_graph and not bool(torch.isfinite(self.stats["grad_norm"]).item()):
-            L = self.learner
-            for t, v in zip((L.bucket.data, L.exp_avg, L.exp_avg_sq, L.ema), snap[:4]):
-                t.copy_(v)
-            L.step_count = snap[4]
-            L._refresh_bf16()
+            self.learner.restore(snap)
             raise RuntimeError("non-finite gradient norm from the graph-replayed optimizer step; the learner was restored to "
                                "its state before this update")
         self.stats.update(lr=lr, ent_coef=ent_coef, clip_eps=clip_eps, optimizer_steps=steps)
@@ -397,16 +387,14 @@ class VecMAPPOTrainer:
                              "checkpoints written before `total_updates` and the tensor-valued `np_rng` were added are not supported)")
         if int(ck["total_updates"]) != int(self.total_updates):
             raise ValueError(f"checkpoint was written for a schedule of {ck['total_updates']} updates, this trainer has {self.total_updates}")
-        self.learner.bucket.data.copy_(ck["data"]); self.learner.ema.copy_(ck["ema"])
-        self.learner.exp_avg.copy_(ck["exp_avg"]); self.learner.exp_avg_sq.copy_(ck["exp_avg_sq"])
-        self.learner.step_count, self.update_idx = int(ck["step"]), int(ck["update"])
+        self.learner.restore(ck)                                         # (weights, Adam moments, EMA and step count: the same keys)
+        self.update_idx = int(ck["update"])
         self.opponent_pool = deque(ck["pool"], maxlen=OPPONENT_POOL_SIZE)
         self.gen.set_state(ck["gen"].cpu())
         self.hard_bots = tuple(ck.get("hard_bots", ("baseline",)))       # files written before hard_bots existed: the default
         r = ck["np_rng"]
         self.np_rng.set_state((r["kind"], r["keys"].cpu().numpy().astype(np.uint32), int(r["pos"]), int(r["has_gauss"]),
                                float(r["cached_gaussian"])))
-        self.learner._refresh_bf16()
 
 
 def evaluate_vs_bots(model, num_episodes=20, layout_file="bloxCapture", teams=("baselineTeam", "randomTeam"), length=300,

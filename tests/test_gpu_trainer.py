@@ -214,35 +214,6 @@ def test_graph_replay_survives_larger_tower_calls_after_capture():
     assert bool(torch.isfinite(lb.bucket.data).all())
 
 
-def test_flat_bf16_step_tracks_autocast_step():
-    """PPOLearner.enable_bf16_flat (one flat bfloat16 weight copy, flat gradient) against the autocast step on the same data."""
-    from pmx import mappo
-    torch.manual_seed(2)
-    shape, B = (8, 11, 14), 256
-    a = mappo.MAPPOAgent(shape, 5, 2).cuda()
-    b = mappo.MAPPOAgent(shape, 5, 2).cuda()
-    b.load_state_dict(a.state_dict())
-    la = mappo.PPOLearner(a, autocast_dtype=torch.bfloat16)
-    lb = mappo.PPOLearner(b, autocast_dtype=torch.bfloat16)
-    lb.enable_bf16_flat()
-    g = torch.Generator(device="cuda").manual_seed(1)
-    for k in range(4):
-        obs = (torch.rand((B,) + shape, device="cuda", generator=g) < 0.2).to(torch.bfloat16)
-        mg = (torch.rand((B // 2,) + shape, device="cuda", generator=g) < 0.2).to(torch.bfloat16)
-        act = torch.randint(0, 5, (B,), device="cuda", generator=g)
-        logp = -1.6 + 0.05 * torch.randn(B, device="cuda", generator=g)
-        adv, ret = torch.randn(B, device="cuda", generator=g), torch.randn(B, device="cuda", generator=g)
-        sa = la.update_minibatch(obs, mg, act, logp, adv, ret)
-        sb = lb.update_minibatch(obs, mg, act, logp, adv, ret)
-        assert torch.allclose(sa["loss"], sb["loss"], rtol=3e-2, atol=3e-3), (k, sa["loss"], sb["loss"])
-        assert torch.allclose(sa["grad_norm"], sb["grad_norm"], rtol=0.15), (k, sa["grad_norm"], sb["grad_norm"])
-    # Adam moves every weight by about lr per step whatever the gradient scale, so compare the direction of the total update
-    da, db = la.bucket.data - la.ema, lb.bucket.data - lb.ema
-    cos = torch.nn.functional.cosine_similarity(da, db, dim=0)
-    assert float(cos) > 0.8, float(cos)
-    assert torch.equal(lb._w16.detach().float(), lb.bucket.data.to(torch.bfloat16).float())
-
-
 @pytest.mark.parametrize("rows,C", [(154 * 257, 96), (154 * 64, 32), (70000, 128), (5000, 8), (4099, 256)])
 def test_column_sum_kernel_matches_torch(rows, C):
     """pmx_colsum_bf16 (bias gradients of the token linears) against a float64 sum of the same bfloat16 values."""
@@ -881,11 +852,7 @@ def test_fused_clip_adam_ema_matches_the_torch_ops():
                 L.step_count += 1
                 norms.append(float(L._fused_tail()))
             else:
-                gn = torch.linalg.vector_norm(torch.stack(torch._foreach_norm([p.grad for p in L.bucket.params])))
-                L.bucket.grad.mul_(torch.clamp(mappo.MAX_GRAD_NORM / (gn + 1e-6), max=1.0))
-                L._adam_step()
-                L.ema.mul_(mappo.EMA_DECAY).add_(L.bucket.data, alpha=1 - mappo.EMA_DECAY)
-                norms.append(float(gn))
+                norms.append(float(L._torch_tail()))
         res[fused] = (L.bucket.data.clone(), L.exp_avg.clone(), L.exp_avg_sq.clone(), L.ema.clone(), L.bucket.grad.clone(), norms)
     for a, b, name in zip(res[True][:5], res[False][:5], ("param", "exp_avg", "exp_avg_sq", "ema", "clipped grad")):
         assert torch.allclose(a, b, rtol=2e-5, atol=1e-7), (name, float((a - b).abs().max()))
@@ -1005,6 +972,8 @@ def test_bf16_shadow_weights_give_the_autocast_step():
         for _ in range(3):
             st = L.update_minibatch(obs, merged, act, old_logp, adv, ret)
         assert (L._sh16 is not None) == shadow
+        if shadow:      # the bfloat16 copy is the float32 weights rounded, after the steps as before them
+            assert torch.equal(L._sh16.detach().float(), L.bucket.data.to(torch.bfloat16).float())
         res[shadow] = (L.bucket.grad.clone(), L.bucket.data.clone(), float(st["loss"]))
     g_rel = float((res[True][0] - res[False][0]).norm() / res[False][0].norm())
     p_rel = float((res[True][1] - res[False][1]).norm() / res[False][1].norm())

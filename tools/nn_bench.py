@@ -53,9 +53,7 @@ def run(variant):
     act = torch.randint(0, 5, (B,), device=dev)
     logp = torch.full((B,), -1.6, device=dev); adv = torch.randn(B, device=dev); ret = torch.randn(B, device=dev)
     step = learner.update_minibatch
-    if variant in ("flat", "flatgraph"):
-        learner.enable_bf16_flat()
-    if variant in ("graph", "flatgraph"):
+    if variant == "graph":
         learner.capture(B, (8, H, W), torch.bfloat16)
         step = learner.update_minibatch_graph
     for _ in range(3):
