@@ -221,7 +221,12 @@ int pmx_maze_distances_layout(pmx_env *env, int32_t layout, int8_t *cells_dev, u
  * to its rule-kernel and to its expansion-kernel dispatch on the caller's stream (hipExtLaunchKernelGGL); end
  * synchronises them and returns the summed kernel durations (milliseconds) and launch counts.  bench.py's roofline
  * figures come from here.  A pmx_emit_team_obs launch is recorded with the expansion launches (a training loop calls it in
- * place of the four-agent expansion). */
+ * place of the four-agent expansion).
+ * While a profile is open pmx_step runs the FULL expansion: outside one it stores the wall plane (plane 0, a per-layout
+ * constant) from extra blocks of the rule launch and starts the expansion kernel behind it (float32 planes up to 900 MB, no
+ * redraw_layouts).  The expansion duration reported here, which bench.py divides all plane bytes by, is therefore that of the
+ * full-plane kernel -- the one pmx_reset, pmx_observe and pmx_step_agent run -- while a timed loop of plain pmx_step calls
+ * measures the split tick.  The results of a tick are the same either way. */
 int pmx_profile_begin(pmx_env *env, int32_t max_launches);
 /* Launch tuning of the observation-expansion kernel for measurements (no reference counterpart).  The only key is "expand_alt"
  * (1 = walk the planes in alternating directions from tick to tick, the default; 0 = always the same direction, so that every

@@ -142,7 +142,8 @@ hipEvent_t *prof_pair(pmx_env *env, bool expand)
     return p;
 }
 
-int launch_expand(pmx_env *env, void *obs, bool from_snapshots, int single_agent, hipStream_t st)
+// walls_done: the rule launch of this pmx_step stored the vectors wholly inside plane 0 (split_walls)
+int launch_expand(pmx_env *env, void *obs, bool from_snapshots, int single_agent, hipStream_t st, bool walls_done = false)
 {
     PmxExpandParams x;
     std::memset(&x, 0, sizeof(x));
@@ -155,6 +156,7 @@ int launch_expand(pmx_env *env, void *obs, bool from_snapshots, int single_agent
     x.N = env->cfg.n_envs;
     x.lay_H = env->lay.H; x.lay_W = env->lay.W;
     x.single_agent = single_agent;
+    if (walls_done) x.first_vec = env->lay.H * env->lay.W * (int)sizeof(float) / 16;
     if (single_agent >= 0) {
         x.n_emit = 1;
         x.emit[0] = single_agent;
@@ -387,10 +389,22 @@ int pmx_step(pmx_env *env, const int8_t *actions_dev, const pmx_step_out *out, v
     if (env->open_agent != 0) return fail(PMX_ERR_INVALID, "pmx_step: a tick opened with pmx_step_agent is unfinished");
     PmxTickParams p;
     fill_tick_params(env, p, actions_dev, out);
+    // Plane 0 (the walls) does not depend on the rules, so the rule launch stores it in its own shadow and the expansion starts
+    // behind it.  float32 planes only, and only while the expansion uses ordinary stores: bfloat16 planes measured slower with
+    // the split, uint8 planes go through pmx_expand4_kernel, which writes whole env blocks, and beyond PMX_F32_STREAM_BYTES the
+    // split is not measured.  Not with redraw_layouts (an env's walls change at a reset inside the rule kernel) and not under
+    // a profile (pmx_profile_begin: the expansion timed there is the full-plane kernel).
+    const size_t plane_bytes = (size_t)env->cfg.n_envs * env->n_emit * 8 * env->lay.H * env->lay.W * sizeof(float);
+    const bool split_walls = out && out->obs_dev && env->cfg.obs_dtype == PMX_OBS_F32 && plane_bytes <= PMX_F32_STREAM_BYTES &&
+                             !env->cfg.redraw_layouts && !env->profiling;
+    if (split_walls) {
+        p.obs = static_cast<float *>(out->obs_dev);
+        p.n_emit = env->n_emit;
+    }
     hipEvent_t *ev = prof_pair(env, false);
     HIP_TRY(pmx_launch_rule(&p, env->lay.H, as_stream(stream), ev ? ev[0] : nullptr, ev ? ev[1] : nullptr));
     env->snaps_valid = true;
-    if (out && out->obs_dev) return launch_expand(env, out->obs_dev, true, -1, as_stream(stream));
+    if (out && out->obs_dev) return launch_expand(env, out->obs_dev, true, -1, as_stream(stream), split_walls);
     return PMX_OK;
 }
 

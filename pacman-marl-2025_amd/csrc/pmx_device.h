@@ -5,6 +5,8 @@
 
 #define PMX_BLOCK 256            // expansion kernel: 4 wavefronts of 64
 #define PMX_RULE_BLOCK 64        // rule kernels: one wavefront per block, so that N/64 blocks spread over all CUs
+#define PMX_WALL_BLOCKS 1024     // pmx_rule_kernel: one-wave blocks appended to the grid that store the wall plane (4 per CU)
+#define PMX_F32_STREAM_BYTES ((size_t)900 << 20)   // float32 planes beyond this take the streaming expansion (pmx_launch_expand)
 #define PMX_SCARED_TIME 40       // capture.py:75
 #define PMX_MIN_FOOD 2           // capture.py:70
 
@@ -71,6 +73,11 @@ struct PmxTickParams {
     uint32_t lo_mask, hi_mask;
     int32_t *layout_idx_rw;      // the same array as layout_idx when envs move to a new layout at every reset (redraw), else NULL
     int32_t n_layouts;
+    // pmx_rule_kernel only: blocks with blockIdx.x >= rule_blocks store the vectors that lie wholly inside plane 0 (the walls,
+    // a per-layout constant) of every (env, emitted agent) block of obs while the rule blocks run.  obs == NULL: no such blocks
+    float *obs;                  // [N][n_emit][8][H][W], float32 planes only
+    int32_t n_emit;
+    int32_t rule_blocks;
 };
 
 struct PmxExpandParams {
@@ -83,6 +90,8 @@ struct PmxExpandParams {
     int32_t single_agent;        // >= 0: obs is [N][8][H][W] for that agent only (pmx_step_agent)
     int32_t lay_H, lay_W;        // host-side copies of the common layout dimensions (launch sizing)
     int32_t reverse;             // 1: walk the blocks from the highest address down (alternate ticks, see pmx_launch_expand)
+    int32_t first_vec;           // pmx_expand_kernel<0, false, true>: first 16-byte vector of a block it stores.  0: the whole block; H*W*4/16:
+                                 // the vectors wholly inside plane 0 were stored by the rule launch (PmxTickParams::obs)
 };
 
 // pmx_emit_team_obs: the two observations of one team, canonicalised for a red team, + the merged critic input

@@ -5,13 +5,17 @@
 //                      rules of capture.py:448-728, the shaped reward of gymPacMan.py:231-259 and the termination
 //                      test of gymPacMan.py:261-270.  Food rows live in LDS (one column per lane, conflict free),
 //                      agents in registers.  It leaves the state after each sub-step as a coalesced SoA snapshot.
+//                      In pmx_step its grid carries extra one-wave blocks that store plane 0 (the walls, the only plane
+//                      that does not depend on the rules) of the observation while the rule waves wait on memory.
 //   pmx_expand_kernel  one WAVEFRONT per (env, agent): turns a snapshot into the 8 observation planes of
-//                      gymPacMan.get_Observation (gymPacMan.py:195-229) with 16-byte-per-lane stores (ordinary while the
+//                      gymPacMan.get_Observation (gymPacMan.py:195-229), in pmx_step from behind the wall vectors the rule
+//                      launch stored, with 16-byte-per-lane stores (ordinary while the
 //                      planes can live in the Infinity Cache, walking the blocks in alternating directions from tick to
 //                      tick; streaming with capped occupancy beyond).  This kernel moves >95 % of the bytes of the tick
 //                      and is the HBM-roofline kernel.
 // The split keeps the divergent integer rule logic at 64 envs per wave while the byte-heavy expansion gets
 // N*4 wavefronts of perfectly coalesced stores regardless of N.
+#include <algorithm>
 #include <cstdlib>
 
 #include <hip/hip_ext.h>
@@ -751,11 +755,20 @@ __device__ __forceinline__ Ctx make_ctx(const PmxTickParams &p, uint32_t *lds)
 
 }  // namespace
 
+__device__ __forceinline__ void write_walls(const PmxTickParams &p);    // defined with the observation kernels below
+
 // dynamic LDS: 32 wall rows + 3 x H rows x PMX_RULE_BLOCK lanes (food, bots' scratch copy, dump_food's blocked-cell rows)
+// Blocks rule_blocks .. gridDim.x - 1 (present when pmx_step splits the observation, see pmx_launch_rule) do not run the rules:
+// they store the wall plane of the observation, the only plane bytes that do not depend on this tick's rules, while the rule
+// blocks wait on their state loads and HBM would otherwise idle.  The branch is block-uniform; no block waits for another.
 template <bool BOTS, int HB>
 __global__ __launch_bounds__(PMX_RULE_BLOCK) void pmx_rule_kernel(PmxTickParams p)
 {
     extern __shared__ uint32_t lds[];
+    if ((int)blockIdx.x >= p.rule_blocks) {
+        write_walls(p);
+        return;
+    }
     const int env = blockIdx.x * PMX_RULE_BLOCK + threadIdx.x;
     const bool live = env < p.N;
     RawEnv raw;
@@ -940,6 +953,47 @@ __device__ __forceinline__ uint4 pack_obs(uint32_t bits)
     return make_uint4(w[0], w[1], w[2], w[3]);
 }
 
+// ---------------------------------------------------------------------------------------------------------------
+// Wall writer of the rule launch (pmx_rule_kernel, blocks behind the rule blocks).  Plane 0 of every (env, emitted agent)
+// block is the layout's wall_stream expanded to float32 (the split is used for float32 planes only, see pmx_step).  One wave
+// per block walks the (env, agent) blocks grid-stride and stores the 16-byte vectors that lie WHOLLY inside plane 0:
+// first_vec = H*W*4 / 16, rounded down.  The
+// vector that plane 0 shares with plane 1, and everything behind it, belongs to pmx_expand_kernel (PmxExpandParams::first_vec).
+// With one layout the vectors are computed once per wave and only stored again; with per-env layouts they are recomputed
+// from the env's layout record.  A lane holds vector lane + 64 j; the largest board (32 x 32) needs j < 4.
+// ---------------------------------------------------------------------------------------------------------------
+__device__ __forceinline__ void write_walls(const PmxTickParams &p)
+{
+    constexpr int VEC = ObsVec<0>::VEC;
+    constexpr int MAXJ = 32 * 32 / VEC / 64;
+    const int lane = threadIdx.x;
+    const int HW = p.lay_H * p.lay_W;
+    const int first_vec = HW / VEC;
+    const size_t n_vec = (size_t)(8 * HW / VEC);
+    const long total = (long)p.N * p.n_emit;
+    const long stride = (long)gridDim.x - p.rule_blocks;
+    uint4 v[MAXJ];
+    auto pack = [&](const PmxLayoutDev *L) {
+#pragma unroll
+        for (int j = 0; j < MAXJ; ++j) {
+            const uint32_t e0 = (uint32_t)(lane + 64 * j) * VEC;       // < 32 * 32: always inside wall_stream
+            v[j] = pack_obs<0>(L->wall_stream[e0 >> 5] >> (e0 & 31));
+        }
+    };
+    if (!p.layout_idx) pack(p.lay);
+    for (long q = (long)blockIdx.x - p.rule_blocks; q < total; q += stride) {
+        if (p.layout_idx) pack(p.lay + p.layout_idx[q / p.n_emit]);
+        uint4 *out = reinterpret_cast<uint4 *>(p.obs) + (size_t)q * n_vec;
+#pragma unroll
+        for (int j = 0; j < MAXJ; ++j)
+            if (lane + 64 * j < first_vec) {   // streaming stores (one dwordx4 nt): see the measurements at pmx_launch_rule
+                uint4 *o = &out[lane + 64 * j];
+                __builtin_nontemporal_store(v[j].x, &o->x); __builtin_nontemporal_store(v[j].y, &o->y);
+                __builtin_nontemporal_store(v[j].z, &o->z); __builtin_nontemporal_store(v[j].w, &o->w);
+            }
+    }
+}
+
 // the one element of plane 1 that is set holds 1 + numCarrying (gymPacMan.py:205): patch element d of the vector
 template <int DT>
 __device__ __forceinline__ void patch_self(uint4 &v, int d, uint32_t carry)
@@ -992,7 +1046,9 @@ __device__ __forceinline__ void stream_or_row(uint32_t *T, uint32_t off, uint32_
 // 8-bit look-ups of 8 bytes) instead of being computed: with the observation buffer partly resident in the Infinity Cache the
 // float32 kernel had become instruction bound (~1.8 T elements/s whatever the footprint), and the expansion arithmetic was most
 // of its ~35 instructions per 16 bytes.
-template <int DT, bool NT>
+// BEHIND (float32, ordinary stores): the store loop starts at p.first_vec, behind the wall vectors the rule launch stored.  A
+// template flag and not a test of first_vec, so that the full-plane instantiations are the code they were without the split.
+template <int DT, bool NT, bool BEHIND = false>
 __global__ __launch_bounds__(PMX_BLOCK) void pmx_expand_kernel(PmxExpandParams p)
 {
     constexpr int VEC = ObsVec<DT>::VEC;
@@ -1071,7 +1127,7 @@ __global__ __launch_bounds__(PMX_BLOCK) void pmx_expand_kernel(PmxExpandParams p
 
     const int n_vec = 8 * HW / VEC;
     uint4 *out = reinterpret_cast<uint4 *>(p.obs) + (size_t)q * n_vec;
-    for (int k = lane; k < n_vec; k += 64) {
+    for (int k = (BEHIND ? p.first_vec : 0) + lane; k < n_vec; k += 64) {
         const uint32_t e0 = (uint32_t)k * VEC;
         const uint32_t bits = T[e0 >> 5] >> (e0 & 31);
         uint4 v;
@@ -1414,14 +1470,24 @@ extern "C" hipError_t pmx_launch_emit_team(const PmxEmitParams *p, int dtype, hi
 // i.e. the kernel's own duration as a profiler sees it, without the dispatch gaps a hipEventRecord pair would include
 extern "C" hipError_t pmx_launch_rule(const PmxTickParams *p, int H, hipStream_t st, hipEvent_t ev0, hipEvent_t ev1)
 {
-    const int blocks = (p->N + PMX_RULE_BLOCK - 1) / PMX_RULE_BLOCK;
+    const int rule_blocks = (p->N + PMX_RULE_BLOCK - 1) / PMX_RULE_BLOCK;
     const size_t lds = (p->layout_idx ? 32 + (size_t)(3 * PMX_MAX_H_LDS + 32 + 16) * PMX_RULE_BLOCK : 32 + (size_t)(3 * H + 16) * PMX_RULE_BLOCK) * sizeof(uint32_t);
     // row loops unrolled for the board-height bucket (see load_env_issue)
     const int hb = H <= 12 ? 12 : (H <= 16 ? 16 : (H <= 20 ? 20 : 32));
+    // p->obs: the wall writer's blocks follow the rule blocks, which keep the low block ids and so are dispatched first.  A
+    // wall block is one wave and carries the same dynamic LDS reservation as a rule block (9.6 KB for smallCapture, 37 KB
+    // with per-env layouts), of which it uses nothing: PMX_WALL_BLOCKS = 4 per CU stays inside the 160 KB of a CU
+    // next to the CU's rule block in the first case, and queues behind it in the second.
+    // Block counts and store policies measured, and why float32 planes only: profiles/wall_split/README.md.
+    const long obs_blocks = (long)p->N * p->n_emit;
+    const int wall_blocks = p->obs ? (int)std::min<long>(obs_blocks, PMX_WALL_BLOCKS) : 0;
+    const int blocks = rule_blocks + wall_blocks;
+    PmxTickParams q = *p;
+    q.rule_blocks = rule_blocks;
 #define PMX_RULE_LAUNCH(B, HBV)                                                                                         \
     do {                                                                                                                \
-        if (ev0) hipExtLaunchKernelGGL((pmx_rule_kernel<B, HBV>), dim3(blocks), dim3(PMX_RULE_BLOCK), (uint32_t)lds, st, ev0, ev1, 0, *p); \
-        else hipLaunchKernelGGL((pmx_rule_kernel<B, HBV>), dim3(blocks), dim3(PMX_RULE_BLOCK), lds, st, *p);              \
+        if (ev0) hipExtLaunchKernelGGL((pmx_rule_kernel<B, HBV>), dim3(blocks), dim3(PMX_RULE_BLOCK), (uint32_t)lds, st, ev0, ev1, 0, q); \
+        else hipLaunchKernelGGL((pmx_rule_kernel<B, HBV>), dim3(blocks), dim3(PMX_RULE_BLOCK), lds, st, q);               \
     } while (0)
 #define PMX_RULE_PICK(B)                                                                      \
     switch (hb) {                                                                             \
@@ -1494,7 +1560,7 @@ extern "C" hipError_t pmx_launch_expand(const PmxExpandParams *p, int dtype, hip
     const size_t elem = dtype == 0 ? 4 : (dtype == 1 ? 2 : 1);
     const size_t bytes = (size_t)waves * 8 * p->lay_H * p->lay_W * elem;
     // uint8 planes always take streaming stores (and so never the alternating sweep); float32 and bfloat16 by size
-    const bool nt = elem == 1 || (elem == 2 && bytes > ((size_t)512 << 20)) || (elem == 4 && bytes > ((size_t)900 << 20));
+    const bool nt = elem == 1 || (elem == 2 && bytes > ((size_t)512 << 20)) || (elem == 4 && bytes > PMX_F32_STREAM_BYTES);
     const size_t lds_pad = (nt && elem == 4) ? 40000 : 0;
     PmxExpandParams q = *p;
     if (nt) q.reverse = 0;
@@ -1513,13 +1579,15 @@ extern "C" hipError_t pmx_launch_expand(const PmxExpandParams *p, int dtype, hip
 #undef PMX_EXPAND4
         return hipGetLastError();
     }
-#define PMX_EXPAND(DT, NTV)                                                                                             \
+#define PMX_EXPAND(...)                                                                                                 \
     do {                                                                                                                \
-        if (ev0) hipExtLaunchKernelGGL((pmx_expand_kernel<DT, NTV>), dim3(blocks), dim3(PMX_BLOCK), (uint32_t)lds_pad, st, ev0, ev1, 0, q); \
-        else hipLaunchKernelGGL((pmx_expand_kernel<DT, NTV>), dim3(blocks), dim3(PMX_BLOCK), lds_pad, st, q);          \
+        if (ev0) hipExtLaunchKernelGGL((pmx_expand_kernel<__VA_ARGS__>), dim3(blocks), dim3(PMX_BLOCK), (uint32_t)lds_pad, st, ev0, ev1, 0, q); \
+        else hipLaunchKernelGGL((pmx_expand_kernel<__VA_ARGS__>), dim3(blocks), dim3(PMX_BLOCK), lds_pad, st, q);       \
     } while (0)
+    // first_vec > 0 comes from pmx_step for float32 planes up to PMX_F32_STREAM_BYTES only, i.e. never with nt
+    if (q.first_vec > 0 && (dtype != 0 || nt)) return hipErrorInvalidValue;
     switch (dtype) {
-    case 0: if (nt) PMX_EXPAND(0, true); else PMX_EXPAND(0, false); break;
+    case 0: if (nt) PMX_EXPAND(0, true); else if (q.first_vec > 0) PMX_EXPAND(0, false, true); else PMX_EXPAND(0, false); break;
     case 1: if (nt) PMX_EXPAND(1, true); else PMX_EXPAND(1, false); break;
     default: PMX_EXPAND(2, true); break;
     }
