@@ -838,7 +838,21 @@ extern "C" int pmx_attn8_forward_layout(const void *qkv_dev, void *out_dev, floa
 // K^T, Q^T, dO^T are staged transposed in LDS ([8][S_pad] bf16), Delta_q = sum_d dO.O and the LSE as float32 [S_pad];
 // the row-major operands of the score products are read straight from global memory (16 bytes per lane, L1-resident).
 // Gradients are written in the packed [S][B][96] layout of the in-projection output.
+//
+// Padded keys (rows S .. S_pad - 1) have zero K rows, so their score is 0 and exp(0 - lse) overflows for a query whose
+// log-sum-exp lies below -88 nats; their K^T entries are zero too, and inf * 0 would poison dQ.  They are therefore masked, without
+// an instruction more in the loops.  This kernel masks INSIDE the score product: its contraction runs over 32 k-slots of which the head
+// dimension fills 0..7 (lane group 0 of either operand), and k-slot 8 -- element 0 of lane group 1 -- carries the key mask: every
+// query row holds 1 there, a key row 0 when the key is real and -2^100 when it lies past the sequence.  A padded key's score comes
+// out at -2^100 whatever the query's log-sum-exp, its probability and its dS are exactly 0, and a real key's score gains 1 * 0.
+// The one-pass kernels below, where a lane is one key column, add the lane's 0 / -2^100 in the multiply-add that scales the score.
+// Nothing is clamped or rescaled: the kernels take any log-sum-exp the forward kernel emits (|lse| far below 2^100), and each
+// probability exp2(c s - lse2) carries the float32 rounding of its exponent, about 1e-7 |lse| relative.  Padded QUERIES carry
+// lse = 1e30 (probability 0).
 // ---------------------------------------------------------------------------------------------------------------
+constexpr short PMX_BF16_ONE = 0x3F80, PMX_BF16_KEY_OFF = (short)0xF180;       // 1.0 and -2^100 as bf16
+constexpr float PMX_KEY_OFF = -0x1p100f;
+
 __global__ __launch_bounds__(512) void pmx_attn8_bwd_kernel(const __hip_bfloat16 *__restrict__ qkv, const __hip_bfloat16 *__restrict__ outp,
                                                             const __hip_bfloat16 *__restrict__ dout, const float *__restrict__ lse,
                                                             __hip_bfloat16 *__restrict__ dqkv, int S, int B, float scale, int bm)
@@ -897,6 +911,20 @@ __global__ __launch_bounds__(512) void pmx_attn8_bwd_kernel(const __hip_bfloat16
         if (g == 0 && r < S) v = *reinterpret_cast<const pmx_bf16x8 *>(src + (size_t)r * stride + off);
         return v;
     };
+    // the two operands of a score product, with the key mask in k-slot 8 (see above)
+    // (lane group 1 never loads: its constant does not wait for the row that group 0 requested a tile ahead)
+    auto qry8 = [&](int r) -> pmx_bf16x8 {
+        pmx_bf16x8 v = zero8;
+        if (g == 1) v[0] = PMX_BF16_ONE;
+        if (g == 0 && r < S) v = *reinterpret_cast<const pmx_bf16x8 *>(base + (size_t)r * row_stride + head_off);
+        return v;
+    };
+    auto key8 = [&](int r) -> pmx_bf16x8 {
+        pmx_bf16x8 v = zero8;
+        if (g == 1 && r >= S) v[0] = PMX_BF16_KEY_OFF;
+        if (g == 0 && r < S) v = *reinterpret_cast<const pmx_bf16x8 *>(base + (size_t)r * row_stride + head_off + E);
+        return v;
+    };
     auto tfrag = [&](const short *T, int pair) -> pmx_bf16x8 {       // A fragment [row d = c][k-slot j]: index 32*pair + 4g + j / + 16
         pmx_bf16x8 v = zero8;
         if (c < D) {
@@ -912,26 +940,25 @@ __global__ __launch_bounds__(512) void pmx_attn8_bwd_kernel(const __hip_bfloat16
     if (role == 0)
     for (int qt = 0; qt < n_t; ++qt) {
         const int q_row = qt * 16 + c;
-        const pmx_bf16x8 qf = row8(base, row_stride, head_off, q_row);
+        const pmx_bf16x8 qf = qry8(q_row);
         const pmx_bf16x8 dof = row8(dobase, orow, ohead, q_row);
-        // (the clamp only matters for the zero K rows of padded keys: exp2(-ls) must stay finite so that 0 * dS is 0 in the MFMA)
-        const float ls = fmaxf(lse_s[q_row < S_pad ? q_row : 0], -120.f), dl = delta_s[q_row < S_pad ? q_row : 0];
+        const float ls = lse_s[q_row < S_pad ? q_row : 0], dl = delta_s[q_row < S_pad ? q_row : 0];
         pmx_f32x4 dq = z4;
         // software pipeline: the row fragments of key pair kp + 1 are requested before pair kp is consumed (the loads are
         // L2 hits several hundred cycles away and the compiler does not hoist them across the loop by itself)
-        pmx_bf16x8 k0n = row8(base, row_stride, head_off + E, c), k1n = row8(base, row_stride, head_off + E, 16 + c);
+        pmx_bf16x8 k0n = key8(c), k1n = key8(16 + c);
         pmx_bf16x8 v0n = row8(base, row_stride, head_off + 2 * E, c), v1n = row8(base, row_stride, head_off + 2 * E, 16 + c);
         for (int kp = 0; kp < n_p; ++kp) {
             const pmx_bf16x8 k0 = k0n, k1 = k1n, v0 = v0n, v1 = v1n;
             if (kp + 1 < n_p) {
-                k0n = row8(base, row_stride, head_off + E, kp * 32 + 32 + c); k1n = row8(base, row_stride, head_off + E, kp * 32 + 48 + c);
+                k0n = key8(kp * 32 + 32 + c); k1n = key8(kp * 32 + 48 + c);
                 v0n = row8(base, row_stride, head_off + 2 * E, kp * 32 + 32 + c); v1n = row8(base, row_stride, head_off + 2 * E, kp * 32 + 48 + c);
             }
             const pmx_f32x4 s0 = __builtin_amdgcn_mfma_f32_16x16x32_bf16(k0, qf, z4, 0, 0, 0);
             const pmx_f32x4 s1 = __builtin_amdgcn_mfma_f32_16x16x32_bf16(k1, qf, z4, 0, 0, 0);
             const pmx_f32x4 p0 = __builtin_amdgcn_mfma_f32_16x16x32_bf16(v0, dof, z4, 0, 0, 0);
             const pmx_f32x4 p1 = __builtin_amdgcn_mfma_f32_16x16x32_bf16(v1, dof, z4, 0, 0, 0);
-            // no key mask: the K^T columns of padded keys are zero in LDS, so whatever dS holds there contributes nothing
+            // (a padded key -- accumulator row 4g + r of the last pair -- has score -2^100: e and its dS are 0)
             pmx_bf16x8 dsf;
 #pragma unroll
             for (int r = 0; r < 4; ++r) {
@@ -953,15 +980,15 @@ __global__ __launch_bounds__(512) void pmx_attn8_bwd_kernel(const __hip_bfloat16
     if (role == 1)
     for (int kt = 0; kt < n_t; ++kt) {
         const int k_row = kt * 16 + c;
-        const pmx_bf16x8 kf = row8(base, row_stride, head_off + E, k_row);
+        const pmx_bf16x8 kf = key8(k_row);
         const pmx_bf16x8 vf = row8(base, row_stride, head_off + 2 * E, k_row);
         pmx_f32x4 dk = z4, dv = z4;
-        pmx_bf16x8 q0n = row8(base, row_stride, head_off, c), q1n = row8(base, row_stride, head_off, 16 + c);
+        pmx_bf16x8 q0n = qry8(c), q1n = qry8(16 + c);
         pmx_bf16x8 d0n = row8(dobase, orow, ohead, c), d1n = row8(dobase, orow, ohead, 16 + c);
         for (int qp = 0; qp < n_p; ++qp) {
             const pmx_bf16x8 q0 = q0n, q1 = q1n, d0 = d0n, d1 = d1n;
             if (qp + 1 < n_p) {
-                q0n = row8(base, row_stride, head_off, qp * 32 + 32 + c); q1n = row8(base, row_stride, head_off, qp * 32 + 48 + c);
+                q0n = qry8(qp * 32 + 32 + c); q1n = qry8(qp * 32 + 48 + c);
                 d0n = row8(dobase, orow, ohead, qp * 32 + 32 + c); d1n = row8(dobase, orow, ohead, qp * 32 + 48 + c);
             }
             // S = Q . K^T: rows = queries (4g + r), column = key c
@@ -1058,7 +1085,8 @@ __global__ __launch_bounds__(256 * QS) void pmx_attn8_bwd_fused_kernel(const __h
         }
         if (QS > 1) *reinterpret_cast<uint4 *>(dOr + (size_t)s * D) = dov;
         // Row constants as INITIAL ACCUMULATORS of the two score products: S' = Q K^T - lse / c comes out of the matrix instruction
-        // ready for p = exp2(c S') (a multiply and the exponential), dP' = dO V^T - delta ready for dS = p dP' (one multiply).
+        // ready for p = exp2(c S' + koff) (a multiply-add and the exponential), dP' = dO V^T - delta ready for dS = p dP' (one
+        // multiply).
         lse_s[s] = -ls / (scale * 1.44269504088896341f); delta_s[s] = -delta;
     }
     for (int i = lane; i < 32 * TROW / 4; i += 64) reinterpret_cast<uint32_t *>(stg)[i] = 0u;
@@ -1113,6 +1141,9 @@ __global__ __launch_bounds__(256 * QS) void pmx_attn8_bwd_fused_kernel(const __h
     pmx_bf16x8 kf_n = row8(base, row_stride, head_off + E, c), vf_n = row8(base, row_stride, head_off + 2 * E, c);
     for (int kt = 0; kt < n_t; ++kt) {
         const int k_row = kt * 16 + c;
+        // The lane's key column.  A padded key (zero K row: S' = -lse / c, whose exponential overflows for lse < -88 nats) gets
+        // -2^100 added to every exponent by the multiply-add that scales the score: p = 0 and dS = 0 * -delta = 0 exactly.
+        const float koff = k_row < S ? 0.f : PMX_KEY_OFF;
         const pmx_bf16x8 kf = kf_n, vf = vf_n;
         if (kt + 1 < n_t) {
             kf_n = row8(base, row_stride, head_off + E, k_row + 16);
@@ -1168,8 +1199,8 @@ __global__ __launch_bounds__(256 * QS) void pmx_attn8_bwd_fused_kernel(const __h
             float e0[4], e1[4];
 #pragma unroll
             for (int r = 0; r < 4; ++r) {
-                e0[r] = __builtin_amdgcn_exp2f(cur.s0[r] * c2);
-                e1[r] = __builtin_amdgcn_exp2f(cur.s1[r] * c2);
+                e0[r] = __builtin_amdgcn_exp2f(__builtin_fmaf(cur.s0[r], c2, koff));
+                e1[r] = __builtin_amdgcn_exp2f(__builtin_fmaf(cur.s1[r], c2, koff));
             }
             // probabilities and dS as bf16 pairs: slots 0..3 = queries 4g + r of the first tile of the pair, 4..7 = of the second
             const uint4 pw = make_uint4(pack2bf(e0[0], e0[1]), pack2bf(e0[2], e0[3]), pack2bf(e1[0], e1[1]), pack2bf(e1[2], e1[3]));
@@ -1178,9 +1209,9 @@ __global__ __launch_bounds__(256 * QS) void pmx_attn8_bwd_fused_kernel(const __h
             const pmx_bf16x8 pf = *reinterpret_cast<const pmx_bf16x8 *>(&pw), dsf = *reinterpret_cast<const pmx_bf16x8 *>(&dw);
             __builtin_amdgcn_sched_barrier(0);
             // ---- dV / dK products; dS of the tile as [key c][queries 4g .. 4g+3 | 16 + 4g ..] -> staging rows 0..15 (a padded key's
-            // column holds whatever the zero K row produced; its K^T entries in `ka` are zero, so it adds nothing); the transposing
-            // reads are issued right behind the write.  Write, reads and the next pair's write are LDS operations of ONE wave on one
-            // array: the hardware runs them in program order and the compiler keeps may-aliasing accesses in order.
+            // column is exactly 0, see koff); the transposing reads are issued right behind the write.  Write, reads and the next
+            // pair's write are LDS operations of ONE wave on one array: the hardware runs them in program order and the compiler
+            // keeps may-aliasing accesses in order.
             dv = __builtin_amdgcn_mfma_f32_16x16x32_bf16(fo, pf, dv, 0, 0, 0);
             dk = __builtin_amdgcn_mfma_f32_16x16x32_bf16(fq, dsf, dk, 0, 0, 0);
             *reinterpret_cast<uint2 *>(stg + c * TROW + (4 * g) * 2) = make_uint2(dw.x, dw.y);

@@ -1,6 +1,8 @@
 """GPU tests of the training side: shaping from the compact self plane vs the oracle's observation-based restatement,
 rollout-buffer consistency, GAE on the rollout vs the oracle, PPO loss parity on the GPU (fp32, 1e-4 rtol), and a
 short end-to-end training run."""
+import functools
+
 import numpy as np
 import pytest
 import torch
@@ -403,6 +405,220 @@ def test_mfma_attention_backward_matches_torch(S, B):
     for name, sl in (("dq", slice(0, 32)), ("dk", slice(32, 64)), ("dv", slice(64, 96))):
         err = float((got[..., sl] - ref[..., sl]).abs().max())
         assert err <= 3e-2 * (float(ref[..., sl].abs().max()) + 1e-6), (name, err, float(ref[..., sl].abs().max()))
+
+
+_ATTN_PARTS = (("dq", slice(0, 32)), ("dk", slice(32, 64)), ("dv", slice(64, 96)))
+
+
+def _attn_heads(t, S, B):
+    return t.reshape(S, B, 4, 8).permute(1, 2, 0, 3)                                   # [S, B, 32] -> [B, h, S, d]
+
+
+def _attn_ref(qkv, g):
+    """torch autograd of softmax(q k^T / sqrt(8)) v in float64 from the bf16 inputs qkv [S, B, 96], g [S, B, 32]:
+    (d qkv [S, B, 96], scaled scores [B, 4, S, S], their log-sum-exp [B, 4, S]), all float64."""
+    S, B, _ = qkv.shape
+    x = qkv.double().requires_grad_(True)
+    q, k, v = (_attn_heads(t, S, B) for t in x.chunk(3, dim=-1))
+    sc = torch.matmul(q, k.transpose(-1, -2)) / 8 ** 0.5
+    out = torch.matmul(torch.softmax(sc, -1), v).permute(2, 0, 1, 3).reshape(S, B, 32)
+    out.backward(g.double())
+    sc = sc.detach()
+    return x.grad, sc, torch.logsumexp(sc, -1)
+
+
+def _attn_rounding_model(qkv, g):
+    """The same gradient in float32 with a bf16 rounding wherever the kernels' header comments place one: the probabilities that
+    multiply V and dO, the forward's output (it enters delta), dS, and the three results.  No kernel code is involved."""
+    S, B, _ = qkv.shape
+    bf = lambda t: t.to(torch.bfloat16).float()
+    q, k, v = (_attn_heads(t, S, B) for t in qkv.float().chunk(3, dim=-1))
+    do = _attn_heads(g.float(), S, B)
+    sc = torch.matmul(q, k.transpose(-1, -2)) / 8 ** 0.5
+    P = torch.exp(sc - torch.logsumexp(sc, -1, keepdim=True))
+    out = bf(torch.matmul(bf(P), v))
+    delta = (do * out).sum(-1, keepdim=True)
+    dS = bf(P * (torch.matmul(do, v.transpose(-1, -2)) - delta))
+    dq = bf(torch.matmul(dS, k) / 8 ** 0.5)
+    dk = bf(torch.matmul(dS.transpose(-1, -2), q) / 8 ** 0.5)
+    dv = bf(torch.matmul(bf(P).transpose(-1, -2), do))
+    return torch.cat([t.permute(2, 0, 1, 3).reshape(S, B, 32) for t in (dq, dk, dv)], -1)
+
+
+def _attn_rel_err(got, ref):
+    """max |got - ref| / (max |ref| + 1e-6) for dq, dk and dv separately."""
+    return {name: float((got[..., sl].double() - ref[..., sl]).abs().max()) / (float(ref[..., sl].abs().max()) + 1e-6)
+            for name, sl in _ATTN_PARTS}
+
+
+@functools.lru_cache(maxsize=None)
+def _attn_case(kind, S, B, amp=0.0, shift=0.0):
+    """Inputs (drawn on the CPU, so that the preconditions the tests assert hold for the same numbers wherever they run), the
+    float64 reference and the rounding model's error against it, computed once per case and shared read-only."""
+    if kind == "shifted":                  # the construction of test_mfma_attention_forward_with_large_and_shifted_scores
+        torch.manual_seed(77)
+        x = torch.randn(S, B, 96) * amp
+        x[:, :, 32:64] += shift * torch.sign(x[:1, :, 0:32])
+    elif kind == "dominant":               # that of test_mfma_attention_forward_rows_one_key_dominates, codes of 4.0 instead of 8.5
+        torch.manual_seed(5)
+        x = torch.randn(S, B, 96) * 0.3
+        tgt = torch.randint(0, 8, (S,))
+        code = torch.eye(8) * amp
+        for h in range(4):
+            x[:8, :, 32 + 8 * h:40 + 8 * h] += code[:, None, :]
+            x[:, :, 8 * h:8 * h + 8] += code[tgt][:, None, :]
+    else:                                  # benign: that of test_mfma_attention_backward_matches_torch
+        torch.manual_seed(S + 1)
+        x = torch.randn(S, B, 96) * 1.3
+    qkv, g = x.to(torch.bfloat16), torch.randn(S, B, 32).to(torch.bfloat16)
+    ref, sc, lse = _attn_ref(qkv, g)
+    top2 = sc.topk(min(2, S), dim=-1).values
+    case = {"qkv": qkv, "g": g, "ref": ref, "lse": lse, "gap": float((top2[..., 0] - top2[..., -1]).median())}
+    if kind != "benign":
+        case["e_model"] = _attn_rel_err(_attn_rounding_model(qkv, g), ref)
+    return case
+
+
+def _attn_backward(case, batch_major):
+    """d qkv of mappo.attention8 on the case's inputs in the given memory layout, returned as [S, B, 96] bfloat16."""
+    from pmx import mappo
+    qkv, g = case["qkv"].cuda(), case["g"].cuda()
+    if batch_major:
+        qkv, g = qkv.transpose(0, 1).contiguous(), g.transpose(0, 1).contiguous()
+    qkv.requires_grad_(True)
+    mappo.attention8(qkv, batch_major).backward(g)
+    return qkv.grad.transpose(0, 1) if batch_major else qkv.grad
+
+
+def _assert_attn_backward_within_model(case, got, what):
+    """Finite, and each of dq, dk, dv within max(3e-2, 2 e_model) of the float64 reference in the max norm, relative to the
+    reference's largest element.  3e-2 is the bound of test_mfma_attention_backward_matches_torch; e_model is what the bf16
+    roundings the kernels document cost on these very inputs, and the factor 2 covers another summation order and the hardware
+    exp2 -- not another algorithm."""
+    assert bool(torch.isfinite(got.float()).all()), (what, "non-finite gradient")
+    err = _attn_rel_err(got.cpu(), case["ref"])
+    print(what, {n: "got %.4f model %.4f" % (err[n], case["e_model"][n]) for n in err})
+    for name in err:
+        tol = max(3e-2, 2 * case["e_model"][name])
+        assert err[name] <= tol, (what, name, err[name], tol, case["e_model"][name])
+
+
+@pytest.mark.parametrize("batch_major", [False, True])
+@pytest.mark.parametrize("amp,shift", [(4.0, -25.0), (1.5, -5.0)])
+@pytest.mark.parametrize("S", [154, 400, 33, 200, 397])
+def test_mfma_attention_backward_with_large_and_shifted_scores(S, amp, shift, batch_major):
+    """The backward on the data the forward is tested on (scores of +-50 .. 300 with a common shift): every log-sum-exp the
+    forward may emit must be one the three backward kernels (S = 154: one-wave fused, 400 and 397: two-wave fused, 33 and 200:
+    two-pass) can exponentiate against.  With (4.0, -25.0) the log-sum-exp spans about -310 .. +430 nats and more than 5 % of the
+    rows lie below -88.7, where exp(-lse) of a padded key (score 0) is infinite in float32; (1.5, -5.0) is the control (|lse| < 60).
+    S = 400 is a multiple of 16, so the two-wave kernel visits no key tile with padding there; 397 makes it visit one.
+    Before the padded keys were masked: dq not finite at S = 154, 1.00 at 33 and 0.43 at 200 (all of it undersized by the -120
+    clamp of the log-sum-exp); 400 and every control case within the bound.  Measured on an MI355X, max |got - ref| / max |ref|
+    as dq / dk / dv (the rounding model's in brackets), the same in both layouts:
+      (4.0, -25.0)  S = 154: .0278 / .0077 / .0014 (.0355 / .0086 / .0014)   400: .0137 / .0079 / .0026 (.0230 / .0138 / .0026)
+                    S =  33: .0150 / .0048 / .0025 (.0211 / .0082 / .0025)   200: .0194 / .0146 / .0031 (.0411 / .0098 / .0031)
+      (1.5, -5.0)   S = 154: .0168 / .0029 / .0017 (.0303 / .0039 / .0017)   400: .0155 / .0047 / .0032 (.0164 / .0094 / .0032)
+                    S =  33: .0097 / .0041 / .0055 (.0148 / .0056 / .0055)   200: .0140 / .0038 / .0023 (.0159 / .0041 / .0023)
+    S = 397: not measured separately (rounding model .0287 / .0065 / .0024 and .0268 / .0073 / .0032)."""
+    B = 3
+    case = _attn_case("shifted", S, B, amp, shift)
+    lse = case["lse"]
+    if shift == -25.0:
+        assert float((lse < -88.7).double().mean()) >= 0.05 and float(lse.max()) > 88.7, (float(lse.min()), float(lse.max()))
+    else:
+        assert float(lse.abs().max()) < 60.0, float(lse.abs().max())
+    _assert_attn_backward_within_model(case, _attn_backward(case, batch_major), ("shifted", S, amp, shift, batch_major))
+
+
+@pytest.mark.parametrize("S", [154, 400, 33])
+def test_mfma_attention_backward_rows_one_key_dominates(S):
+    """Rows whose probability mass sits on one key.  The codes are 4.0 (the forward's test uses 8.5, where dq and dk are ~1e-7
+    and a comparison relative to their maximum means nothing): the median gap between the two largest scores is above 3.5 nats
+    and dq reaches 0.1.
+    Measured on an MI355X, max |got - ref| / max |ref| as dq / dk / dv (the rounding model's in brackets):
+      S = 154: .0049 / .0032 / .0023 (.0082 / .0065 / .0023)   400: .0053 / .0035 / .0023 (.0084 / .0055 / .0023)
+      S =  33: .0248 / .0114 / .0027 (.0256 / .0138 / .0027)"""
+    case = _attn_case("dominant", S, 3, 4.0)
+    assert case["gap"] > 3.5 and float(case["ref"][..., :32].abs().max()) > 0.1, (case["gap"], float(case["ref"][..., :32].abs().max()))
+    _assert_attn_backward_within_model(case, _attn_backward(case, False), ("dominant", S))
+
+
+@pytest.mark.parametrize("batch_major", [False, True])
+@pytest.mark.parametrize("B", [1, 3])
+@pytest.mark.parametrize("S", [1, 16, 17, 32, 128, 129, 159, 160, 161, 384, 385, 415, 416, 417, 640])
+def test_mfma_attention_backward_at_every_dispatch_edge(S, B, batch_major):
+    """pmx_attn8_backward_layout picks its kernel by the padded length: 160 (S = 129 .. 160) and 416 (S = 385 .. 416) take the
+    fused kernels, everything else up to 640 the two-pass one.  Both ends of both windows, their first neighbours outside, single
+    tiles and pairs (1, 16, 17, 32), the no-padding lengths and the largest, one sample and several, both layouts: each within the
+    bound of test_mfma_attention_backward_matches_torch of the float64 reference, bit-identical between two runs, and
+    bit-identical between the layouts (the layout only decides addresses)."""
+    case = _attn_case("benign", S, B)
+    got = _attn_backward(case, batch_major)
+    assert bool(torch.isfinite(got.float()).all())
+    err = _attn_rel_err(got.cpu(), case["ref"])
+    for name in err:
+        assert err[name] <= 3e-2, (name, err[name])
+    assert torch.equal(got, _attn_backward(case, batch_major)), "two runs of the same backward differ"
+    assert torch.equal(got, _attn_backward(case, not batch_major)), "the layouts give different gradients"
+
+
+_ATTN_CANARY = 0x7FC1                       # a bf16 NaN with a payload no arithmetic produces
+
+
+def _attn_abi_buffers(S, B, batch_major, seed):
+    """qkv, out, dout, lse of a forward call through the C ABI, and d qkv as the middle of an allocation filled with the canary."""
+    import ctypes as C
+    from pmx import _lib
+    lib = _lib.load()
+    torch.manual_seed(seed)
+    shape = (B, S) if batch_major else (S, B)
+    qkv = (torch.randn(*shape, 96, device="cuda") * 1.3).to(torch.bfloat16)
+    dout = torch.randn(*shape, 32, device="cuda").to(torch.bfloat16)
+    out = torch.zeros(*shape, 32, device="cuda", dtype=torch.bfloat16)
+    lse = torch.zeros(B, 4, S, device="cuda", dtype=torch.float32)
+    st = C.c_void_p(torch.cuda.current_stream().cuda_stream)
+    assert lib.pmx_attn8_forward_layout(qkv.data_ptr(), out.data_ptr(), lse.data_ptr(), S, B, int(batch_major), st) == 0
+    guard, n = 4096, S * B * 96
+    buf = torch.full((guard + n + guard,), _ATTN_CANARY, dtype=torch.int16, device="cuda")
+    return lib, st, qkv, out, dout, lse, buf, guard, n
+
+
+@pytest.mark.parametrize("batch_major", [False, True])
+@pytest.mark.parametrize("S", [154, 400, 33, 161])
+def test_attention_backward_writes_dqkv_in_full_and_nothing_else(S, batch_major):
+    """The entry point's contract: "dqkv_dev [S][B][96] bf16 is written in full".  d qkv sits between two guards of 4096 elements in an
+    allocation filled with a NaN pattern no kernel produces: afterwards no element of d qkv is NaN (every one was written), both
+    guards still hold the pattern, and the four inputs are what they were."""
+    B = 2
+    lib, st, qkv, out, dout, lse, buf, guard, n = _attn_abi_buffers(S, B, batch_major, S + 3)
+    before = [t.clone() for t in (qkv, out, dout, lse)]
+    dqkv = buf[guard:guard + n].view(torch.bfloat16)
+    rc = lib.pmx_attn8_backward_layout(qkv.data_ptr(), out.data_ptr(), dout.data_ptr(), lse.data_ptr(), dqkv.data_ptr(), S, B,
+                                       int(batch_major), st)
+    torch.cuda.synchronize()
+    assert rc == 0
+    canary = torch.full((guard,), _ATTN_CANARY, dtype=torch.int16, device="cuda")
+    assert torch.equal(buf[:guard], canary), "written in front of d qkv"
+    assert torch.equal(buf[guard + n:], canary), "written past the end of d qkv"
+    assert not bool(torch.isnan(dqkv.float()).any()), int(torch.isnan(dqkv.float()).sum())
+    for t, t0 in zip((qkv, out, dout, lse), before):
+        assert torch.equal(t, t0), "an input was modified"
+
+
+def test_attention_backward_entry_point_checks_its_arguments():
+    """S outside 1 .. 640 and a null pointer are PMX_ERR_INVALID, an empty batch is a success that launches nothing; none of
+    them touches d qkv."""
+    S, B = 33, 2
+    lib, st, qkv, out, dout, lse, buf, guard, n = _attn_abi_buffers(S, B, False, 11)
+    dqkv = buf[guard:guard + n]
+    PMX_ERR_INVALID = -1
+    args = lambda s, b, lse_ptr: (qkv.data_ptr(), out.data_ptr(), dout.data_ptr(), lse_ptr, dqkv.data_ptr(), s, b, 0, st)
+    assert lib.pmx_attn8_backward_layout(*args(641, B, lse.data_ptr())) == PMX_ERR_INVALID
+    assert lib.pmx_attn8_backward_layout(*args(0, B, lse.data_ptr())) == PMX_ERR_INVALID
+    assert lib.pmx_attn8_backward_layout(*args(S, 0, lse.data_ptr())) == 0
+    assert lib.pmx_attn8_backward_layout(*args(S, B, None)) == PMX_ERR_INVALID
+    torch.cuda.synchronize()
+    assert bool((buf == _ATTN_CANARY).all()), "a rejected or empty call wrote to d qkv"
 
 
 def test_evaluate_vectorized_runs_and_random_policy_loses_to_baseline():
