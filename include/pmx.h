@@ -228,11 +228,17 @@ int pmx_maze_distances_layout(pmx_env *env, int32_t layout, int8_t *cells_dev, u
  * full-plane kernel -- the one pmx_reset, pmx_observe and pmx_step_agent run -- while a timed loop of plain pmx_step calls
  * measures the split tick.  The results of a tick are the same either way. */
 int pmx_profile_begin(pmx_env *env, int32_t max_launches);
-/* Launch tuning of the observation-expansion kernel for measurements (no reference counterpart).  The only key is "expand_alt"
+/* Launch tuning of the observation-expansion kernel for measurements (no reference counterpart).  The keys are "fused_min_envs" and "expand_alt"
  * (1 = walk the planes in alternating directions from tick to tick, the default; 0 = always the same direction, so that every
  * byte reaches HBM even when the caller re-steps one buffer that partly fits the Infinity Cache); any other key is an error.
- * value -1 restores the built-in choice. */
+ * value -1 restores the built-in choice.  "fused_min_envs": see pmx_last_step_fused. */
 int pmx_set_tuning(pmx_env *env, const char *key, int32_t value);
+/* 1 when the last pmx_step ran the whole tick in one launch (pmx_tick_fused_kernel), 0 when it ran the rule and the expansion
+ * launch.  pmx_step takes the one launch for float32 planes up to 900 MB of all four agents, one shared layout, no bots, no
+ * redraw_layouts, a board of at most 20 rows, n_envs a multiple of 64 and at least "fused_min_envs", and no open profile.
+ * "fused_min_envs" is a launch threshold set with pmx_set_tuning; its default (-1) is 64 x the device's compute units, one
+ * workgroup of 64 envs per unit.  The results of a tick are the same either way. */
+int pmx_last_step_fused(const pmx_env *env);
 int pmx_profile_end(pmx_env *env, double *rule_ms, int32_t *rule_launches, double *expand_ms, int32_t *expand_launches);
 
 /* pacman_mappo_resnet.compute_gae (pacman_mappo_resnet.py:277-290) for n independent series laid out

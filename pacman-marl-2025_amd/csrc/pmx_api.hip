@@ -10,6 +10,7 @@
 #include "pmx_device.h"
 
 extern "C" hipError_t pmx_launch_rule(const PmxTickParams *p, int H, hipStream_t st, hipEvent_t ev0, hipEvent_t ev1);
+extern "C" hipError_t pmx_launch_tick_fused(const PmxTickParams *p, int reverse, hipStream_t st);
 extern "C" hipError_t pmx_launch_rule_agent(const PmxTickParams *p, int H, int agent, hipStream_t st);
 extern "C" hipError_t pmx_launch_reset(const PmxTickParams *p, int H, hipStream_t st);
 extern "C" hipError_t pmx_launch_successor(const PmxTickParams *p, int H, int agent, hipStream_t st);
@@ -47,6 +48,8 @@ struct pmx_env {
     uint64_t expand_launches = 0;   // parity selects the direction of the expansion sweep
     PmxExpandTuning tune;           // launch tuning (pmx_set_tuning)
     bool snaps_valid = false;       // the three sub-step snapshots belong to the current state (set by pmx_step)
+    int n_cus = 0;                  // compute units of the device: the default of the fused tick's env threshold
+    int last_step_fused = 0;        // the last pmx_step ran pmx_tick_fused_kernel (pmx_last_step_fused)
     std::vector<hipEvent_t> ev_rule, ev_expand;
     size_t ev_rule_used, ev_expand_used;
 };
@@ -299,6 +302,7 @@ int pmx_create(const pmx_config *cfg, pmx_env **out)
     env->profiling = false; env->ev_rule_used = env->ev_expand_used = 0;
 
     hipError_t e = hipSetDevice(cfg->device);
+    if (e == hipSuccess) e = hipDeviceGetAttribute(&env->n_cus, hipDeviceAttributeMultiprocessorCount, cfg->device);
     const size_t N = (size_t)cfg->n_envs;
     std::vector<PmxLayoutDev> recs;
     for (auto &l : env->layouts) recs.push_back(l.dev);
@@ -401,6 +405,21 @@ int pmx_step(pmx_env *env, const int8_t *actions_dev, const pmx_step_out *out, v
         p.obs = static_cast<float *>(out->obs_dev);
         p.n_emit = env->n_emit;
     }
+    // One launch for the whole tick (pmx_tick_fused_kernel) where a workgroup can own 64 envs from the state load to the last
+    // plane byte: all four agents' float32 planes, one shared layout, the non-bot rule code, a board of at most 20 rows (the
+    // rule code's registers at 16 waves per workgroup), full rule waves, and at least fused_min_envs envs -- by default one
+    // workgroup per CU, below which CUs would be left without a store stream and the two launches are faster.  A launch
+    // threshold like expand_alt, and independent of it.  Under a profile the two launches stay (see split_walls).
+    const int fused_min = env->tune.fused_min_envs >= 0 ? env->tune.fused_min_envs : PMX_RULE_BLOCK * env->n_cus;
+    const bool fused = split_walls && env->n_emit == 4 && !env->layout_idx_dev && !env->dist_dev && env->lay.H <= 20 &&
+                       env->cfg.n_envs % PMX_RULE_BLOCK == 0 && env->cfg.n_envs >= fused_min;
+    env->last_step_fused = fused;
+    if (fused) {
+        const int reverse = env->tune.alt != 0 ? (int)(env->expand_launches++ & 1) : 0;   // the sweep parity, as launch_expand
+        HIP_TRY(pmx_launch_tick_fused(&p, reverse, as_stream(stream)));
+        env->snaps_valid = true;
+        return PMX_OK;
+    }
     hipEvent_t *ev = prof_pair(env, false);
     HIP_TRY(pmx_launch_rule(&p, env->lay.H, as_stream(stream), ev ? ev[0] : nullptr, ev ? ev[1] : nullptr));
     env->snaps_valid = true;
@@ -485,11 +504,15 @@ int pmx_observe(pmx_env *env, void *obs_dev, uint8_t *legal_dev, void *stream)
 }
 
 // ---- per-kernel timing for bench.py (not part of the reference surface) -----------------------------------------
-// Launch tuning of the expansion kernel: key "expand_alt", value -1 = built-in choice.
+// which path the last pmx_step took: 1 = the one-launch tick (pmx_tick_fused_kernel), 0 = rule + expansion launch
+int pmx_last_step_fused(const pmx_env *env) { return env ? env->last_step_fused : 0; }
+
+// Launch tuning: keys "expand_alt" and "fused_min_envs", value -1 = built-in choice.
 int pmx_set_tuning(pmx_env *env, const char *key, int32_t value)
 {
     if (!env || !key) return fail(PMX_ERR_INVALID, "pmx_set_tuning: null argument");
     if (!strcmp(key, "expand_alt")) env->tune.alt = value;
+    else if (!strcmp(key, "fused_min_envs")) env->tune.fused_min_envs = value;
     else return fail(PMX_ERR_INVALID, "pmx_set_tuning: unknown key %s", key);
     return PMX_OK;
 }

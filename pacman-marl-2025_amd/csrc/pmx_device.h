@@ -105,7 +105,8 @@ struct PmxEmitParams {
     int32_t lay_H, lay_W;
 };
 
-// Host-side launch tuning of the expansion kernel, changed through pmx_set_tuning: -1 = the built-in choice.
+// Host-side launch tuning, changed through pmx_set_tuning: -1 = the built-in choice.
 struct PmxExpandTuning {
     int32_t alt = -1;            // alternate the sweep direction from tick to tick (0: always the same direction)
+    int32_t fused_min_envs = -1; // pmx_step takes the one-launch tick from this many envs on (-1: 64 x the device's CU count)
 };

@@ -1,6 +1,6 @@
 // pmx_step.hip -- the batched Capture-the-Flag tick for gfx950 (MI355X).
 //
-// Two kernels per tick:
+// Two kernels per tick (one, pmx_tick_fused_kernel below, where pmx_step can give a workgroup its 64 envs end to end):
 //   pmx_rule_kernel    one LANE per env: the four agent sub-steps of gymPacMan.step (gymPacMan.py:143-193) with the
 //                      rules of capture.py:448-728, the shaped reward of gymPacMan.py:231-259 and the termination
 //                      test of gymPacMan.py:261-270.  Food rows live in LDS (one column per lane, conflict free),
@@ -669,8 +669,9 @@ __device__ __forceinline__ void init_env(Env &e, const Ctx &c)
 }
 
 // gymPacMan.py:171-193: everything after the four sub-steps.
+// Returns true when the env finished and was reset to the fresh game (auto_reset).
 template <int HB = 0>
-__device__ __forceinline__ void tick_finish(Env &e, Acc &a, const Ctx &c_in, const PmxTickParams &p, int env, bool fused)
+__device__ __forceinline__ bool tick_finish(Env &e, Acc &a, const Ctx &c_in, const PmxTickParams &p, int env, bool fused)
 {
     Ctx c = c_in;             // a reset may move the env to another layout of the pool (redraw_layouts)
     double blue_r = a.blue_r + (double)(a.blue_sc > 0 ? a.blue_sc : 0);   // :171-172
@@ -715,40 +716,48 @@ __device__ __forceinline__ void tick_finish(Env &e, Acc &a, const Ctx &c_in, con
         for (int i = 0; i < 4; ++i) m |= (uint32_t)legal_mask(c.wl, c.wls, (int)(e.xy[i] & 0xFF), (int)(e.xy[i] >> 8)) << (8 * i);
         reinterpret_cast<uint32_t *>(p.legal)[env] = m;
     }
+    return done && p.auto_reset;
 }
 
-__device__ __forceinline__ Ctx make_ctx(const PmxTickParams &p, uint32_t *lds)
+// env0 = the env of this lane, tid = its lane in the rule wave.  The caller makes the LDS writes visible to the wave(s) that
+// read them: make_ctx with a block barrier, pmx_tick_fused_kernel (whose rule wave is one of sixteen) with a wave barrier.
+__device__ __forceinline__ Ctx make_ctx_fill(const PmxTickParams &p, uint32_t *lds, const int env0, const unsigned tid)
 {
     Ctx c;
-    const int env0 = blockIdx.x * PMX_RULE_BLOCK + threadIdx.x;
     const bool multi = p.layout_idx != nullptr;
     c.L = p.lay + ((multi && env0 < p.N) ? p.layout_idx[env0] : 0);
     c.W = p.lay_W; c.H = p.lay_H; c.half = p.lay_half; c.n_dump = p.lay_n_dump;       // identical in every layout of a handle
     c.dump = p.dump;
     c.legal_reward = p.legal_reward; c.defence_reward = p.defence_reward;
-    c.wl = multi ? lds + 32 + PMX_MAX_H_LDS * PMX_RULE_BLOCK + threadIdx.x : lds;
+    c.wl = multi ? lds + 32 + PMX_MAX_H_LDS * PMX_RULE_BLOCK + tid : lds;
     c.wls = multi ? PMX_RULE_BLOCK : 1;
-    c.fd = lds + 32 + threadIdx.x;
+    c.fd = lds + 32 + tid;
     c.rows0 = lds + 32;
     c.stg = lds + 32 + (multi ? (3 * PMX_MAX_H_LDS + 32) : 3 * c.H) * PMX_RULE_BLOCK;
-    c.fd2 = multi ? lds + 32 + 2 * PMX_MAX_H_LDS * PMX_RULE_BLOCK + threadIdx.x : lds + 32 + c.H * PMX_RULE_BLOCK + threadIdx.x;
-    c.fd3 = multi ? lds + 32 + 3 * PMX_MAX_H_LDS * PMX_RULE_BLOCK + threadIdx.x : lds + 32 + 2 * c.H * PMX_RULE_BLOCK + threadIdx.x;
+    c.fd2 = multi ? lds + 32 + 2 * PMX_MAX_H_LDS * PMX_RULE_BLOCK + tid : lds + 32 + c.H * PMX_RULE_BLOCK + tid;
+    c.fd3 = multi ? lds + 32 + 3 * PMX_MAX_H_LDS * PMX_RULE_BLOCK + tid : lds + 32 + 2 * c.H * PMX_RULE_BLOCK + tid;
     c.dist = p.dist ? p.dist + c.L->dist_off : nullptr;
     c.cidx = p.cell_index ? p.cell_index + (size_t)(c.L - p.lay) * 1024 : nullptr;
     c.n_cells = c.L->n_cells;
     c.lo_mask = p.lo_mask; c.hi_mask = p.hi_mask;
 #pragma unroll
     for (int i = 0; i < 4; ++i) c.start_xy[i] = (uint32_t)c.L->startx[i] | ((uint32_t)c.L->starty[i] << 8);
-    c.rng_key = p.seed ^ ((uint32_t)(blockIdx.x * PMX_RULE_BLOCK + threadIdx.x) * 0x9E3779B1u);
-    if (threadIdx.x < 32) lds[threadIdx.x] = threadIdx.x < (unsigned)c.H ? p.lay->walls[threadIdx.x] : 0xFFFFFFFFu;
+    c.rng_key = p.seed ^ ((uint32_t)env0 * 0x9E3779B1u);
+    if (tid < 32) lds[tid] = tid < (unsigned)c.H ? p.lay->walls[tid] : 0xFFFFFFFFu;
     if (multi) {   // per-env layouts: every lane keeps its own wall column next to its food column
-        uint32_t *w = lds + 32 + PMX_MAX_H_LDS * PMX_RULE_BLOCK + threadIdx.x;
+        uint32_t *w = lds + 32 + PMX_MAX_H_LDS * PMX_RULE_BLOCK + tid;
         uint32_t wr[32];
 #pragma unroll
         for (int y = 0; y < 32; ++y) wr[y] = y < c.H ? c.L->walls[y] : 0xFFFFFFFFu;     // all loads in flight, then the LDS writes
 #pragma unroll
         for (int y = 0; y < 32; ++y) w[y * PMX_RULE_BLOCK] = wr[y];
     }
+    return c;
+}
+
+__device__ __forceinline__ Ctx make_ctx(const PmxTickParams &p, uint32_t *lds)
+{
+    Ctx c = make_ctx_fill(p, lds, blockIdx.x * PMX_RULE_BLOCK + threadIdx.x, threadIdx.x);
     __syncthreads();
     return c;
 }
@@ -1150,6 +1159,184 @@ __global__ __launch_bounds__(PMX_BLOCK) void pmx_expand_kernel(PmxExpandParams p
 }
 
 // ---------------------------------------------------------------------------------------------------------------
+// The whole tick in ONE launch (pmx_step with float32 planes, all four agents, one layout, no bots, H <= 20, N % 64 == 0 and at
+// least one workgroup per CU: pmx_step's fused_min_envs).  Workgroup g owns envs 64 g .. 64 g + 63 from the state load to the last
+// plane byte: no workgroup reads what another one wrote in this launch, and the only synchronisation is ONE __syncthreads().
+//   phase A  wave 0 runs the rules of its 64 envs with pmx_rule_kernel's device functions and lane mapping; where that kernel
+//            stores a snapshot to global memory, this one copies the H + 10 words into the LDS area snap[4][..][64] (slot 3: the
+//            H + 13 words of the final state).  Waves 1-15 store the wall vectors of the workgroup's 256 (env, agent) blocks with
+//            streaming stores, as write_walls does.
+//   phase B  all 16 waves: the four LDS slots go to p.snap / p.state with 16-byte stores (pmx_observe, pmx_emit_team_obs,
+//            pmx_step_agent and the next tick read them there); the 256 blocks are dealt to the waves, and each is expanded as
+//            pmx_expand_kernel<0, false, true> expands it, the snapshot words coming from LDS.
+// What the two launches cost and this one does not: the end-of-kernel write-back and the second dispatch, and the snapshot
+// round trip through memory in front of every expansion wave.  No global load is issued in phase B: loads return in order
+// behind the stores in front of them, and a wave that waited for one would wait for its plane stores.
+// (That is also why the wall words of the stream tables come from an LDS copy of the layout's wall_stream.)
+// LDS (dynamic): make_ctx's area | snap | look-up table (16 x 16 bytes) | wall_stream (32 words) | 16 stream tables of
+// fused_tab_stride words.
+// ---------------------------------------------------------------------------------------------------------------
+#define PMX_FUSED_WAVES 16
+__host__ __device__ inline int fused_rule_words(int H) { return 32 + (3 * H + 16) * PMX_RULE_BLOCK; }
+__host__ __device__ inline int fused_snap_rows(int H) { return 3 * PMX_SNAP_WORDS(H) + H + 13; }
+__host__ __device__ inline int fused_tab_stride(int H, int W) { return (((8 * H * W + 31) >> 5) + 1 + 3) & ~3; }
+
+// the snapshot words of this lane's env -> column `slot` (= slot base + lane) of the LDS snapshot area; FULL: + score, steps, ticks
+template <int HB, bool FULL>
+__device__ __forceinline__ void snapshot_to_lds(const Env &e, const Ctx &c, uint32_t *slot)
+{
+    uint32_t rows[HB];
+#pragma unroll
+    for (int y = 0; y < HB; ++y) rows[y] = y < c.H ? c.fd[y * PMX_RULE_BLOCK] : 0u;
+#pragma unroll
+    for (int y = 0; y < HB; ++y)
+        if (y < c.H) slot[y * PMX_RULE_BLOCK] = rows[y];
+#pragma unroll
+    for (int i = 0; i < 4; ++i) {
+        slot[PMX_W_AGENT_A(c.H, i) * PMX_RULE_BLOCK] = pack_a(e, i);
+        slot[PMX_W_AGENT_B(c.H, i) * PMX_RULE_BLOCK] = pack_b(e, i);
+    }
+    slot[PMX_W_CAPS(c.H, 0) * PMX_RULE_BLOCK] = e.capw[0];
+    slot[PMX_W_CAPS(c.H, 1) * PMX_RULE_BLOCK] = e.capw[1];
+    if (FULL) {
+        slot[PMX_W_SCORE(c.H) * PMX_RULE_BLOCK] = (uint32_t)e.score;
+        slot[PMX_W_STEPS(c.H) * PMX_RULE_BLOCK] = (uint32_t)e.steps;
+        slot[PMX_W_TICKS(c.H) * PMX_RULE_BLOCK] = e.ticks;
+    }
+}
+
+template <int HB>
+__global__ __launch_bounds__(PMX_FUSED_WAVES * 64) void pmx_tick_fused_kernel(PmxTickParams p, int reverse)
+{
+    constexpr int VEC = ObsVec<0>::VEC, NB = 4 * PMX_RULE_BLOCK;   // (env, agent) blocks of a workgroup
+    extern __shared__ uint32_t lds[];
+    const int wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
+    const int lane = threadIdx.x & 63;
+    const int H = p.lay_H, W = p.lay_W, HW = H * W;
+    // reverse (the alternating sweep, pmx_launch_expand): the workgroups take the groups, and the waves their blocks, backwards
+    const int group = reverse ? (int)gridDim.x - 1 - (int)blockIdx.x : (int)blockIdx.x;
+    uint32_t *snapL = lds + fused_rule_words(H);
+    uint32_t *lut = snapL + fused_snap_rows(H) * PMX_RULE_BLOCK;
+    uint32_t *wstream = lut + 64;                                    // the layout's wall_stream: plane 0 of every stream table
+    uint32_t *T = wstream + 32 + wave * fused_tab_stride(H, W);
+    const int slot_words = PMX_SNAP_WORDS(H) * PMX_RULE_BLOCK;
+    const int first_vec = HW / VEC, n_vec = 8 * HW / VEC;
+    uint4 *obs = reinterpret_cast<uint4 *>(p.obs) + (size_t)group * NB * n_vec;
+
+    if (wave == 0) {
+        const int env = group * PMX_RULE_BLOCK + lane;
+        RawEnv raw;
+        uint32_t rows[HB];
+        load_env_issue<HB>(raw, rows, p.state, p.N, env, H);
+        const uint32_t av = reinterpret_cast<const uint32_t *>(p.actions)[env];   // 4 int8 actions
+        Ctx c = make_ctx_fill(p, lds, env, lane);
+        __builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "wavefront");     // the wall rows: only this wave reads them
+        __builtin_amdgcn_wave_barrier();
+        Env e;
+        load_env_commit<HB>(e, c, raw, rows);
+        Acc a = { 0.0, 0.0, 0, 0, 0, 0, 0 };
+        count_food<HB>(a, c, rows);
+        uint32_t *col = snapL + lane;
+        tick_substep<0, false>(e, a, c, (int)(int8_t)(av & 0xFF));
+        snapshot_to_lds<HB, false>(e, c, col);
+        tick_substep<1, false>(e, a, c, (int)(int8_t)((av >> 8) & 0xFF));
+        snapshot_to_lds<HB, false>(e, c, col + slot_words);
+        tick_substep<2, false>(e, a, c, (int)(int8_t)((av >> 16) & 0xFF));
+        snapshot_to_lds<HB, false>(e, c, col + 2 * slot_words);
+        tick_substep<3, false>(e, a, c, (int)(int8_t)((av >> 24) & 0xFF));
+        const bool fresh = tick_finish<HB>(e, a, c, p, env, true);
+        snapshot_to_lds<HB, true>(e, c, col + 3 * slot_words);
+        if (fresh) {   // the observations of a finished env are those of the fresh game for all four agents (tick_finish stored the
+                       // same words to p.snap; phase B stores them again)
+            for (int s = 0; s < 3; ++s) snapshot_to_lds<HB, false>(e, c, col + s * slot_words);
+        }
+    } else {
+        constexpr int MAXJ = 32 * 32 / VEC / 64;
+        if (wave == 1 && lane < 16) *reinterpret_cast<uint4 *>(&lut[4 * lane]) = pack_obs<0>(lane);
+        if (wave == 1 && lane < 32) wstream[lane] = p.lay->wall_stream[lane];
+        uint4 v[MAXJ];
+#pragma unroll
+        for (int j = 0; j < MAXJ; ++j) {
+            const uint32_t e0 = (uint32_t)(lane + 64 * j) * VEC;       // < 32 * 32: always inside wall_stream
+            v[j] = pack_obs<0>(p.lay->wall_stream[e0 >> 5] >> (e0 & 31));
+        }
+        for (int b = wave - 1; b < NB; b += PMX_FUSED_WAVES - 1) {
+            uint4 *out = obs + (size_t)(reverse ? NB - 1 - b : b) * n_vec;
+#pragma unroll
+            for (int j = 0; j < MAXJ; ++j)
+                if (lane + 64 * j < first_vec) {   // streaming stores, as in write_walls
+                    uint4 *o = &out[lane + 64 * j];
+                    __builtin_nontemporal_store(v[j].x, &o->x); __builtin_nontemporal_store(v[j].y, &o->y);
+                    __builtin_nontemporal_store(v[j].z, &o->z); __builtin_nontemporal_store(v[j].w, &o->w);
+                }
+        }
+    }
+    __syncthreads();
+
+    {   // the four slots -> p.snap[0..2] and p.state: rows of 64 envs = 16 vectors of 16 bytes, [3][H + 10][N] is one row range
+        const int n_rows = fused_snap_rows(H), snap_rows = 3 * PMX_SNAP_WORDS(H);
+        for (int i = threadIdx.x; i < n_rows * 16; i += PMX_FUSED_WAVES * 64) {
+            const int row = i >> 4, q4 = 4 * (i & 15);
+            const uint4 w = *reinterpret_cast<const uint4 *>(snapL + row * PMX_RULE_BLOCK + q4);
+            uint32_t *dst = row < snap_rows ? p.snap + (size_t)row * p.N : p.state + (size_t)(row - snap_rows) * p.N;
+            *reinterpret_cast<uint4 *>(dst + (size_t)group * PMX_RULE_BLOCK + q4) = w;
+        }
+    }
+
+    const int n_words = (8 * HW + 31) >> 5;
+    const uint32_t wallw = lane < 32 ? wstream[lane] : 0u;           // (zero behind the H*W wall bits)
+    for (int it = 0; it < NB / PMX_FUSED_WAVES; ++it) {
+        const int b = it * PMX_FUSED_WAVES + wave;
+        const int ql = reverse ? NB - 1 - b : b;
+        const int agent = ql & 3;
+        const uint32_t *S = snapL + agent * slot_words + (ql >> 2);      // agent 3: the final state
+        const uint32_t food = lane < H ? S[lane * PMX_RULE_BLOCK] : 0u;
+        uint32_t pt = 0;
+        if (lane < 4) pt = S[PMX_W_AGENT_A(H, lane) * PMX_RULE_BLOCK];
+        else if (lane < 8) pt = S[PMX_W_CAPS(H, (lane - 4) >> 1) * PMX_RULE_BLOCK];
+        const uint32_t a_self = S[PMX_W_AGENT_A(H, agent) * PMX_RULE_BLOCK];
+        const uint32_t b_self = S[PMX_W_AGENT_B(H, agent) * PMX_RULE_BLOCK];
+        for (int k = lane; k < n_words + 1; k += 64) T[k] = k < 32 ? wallw : 0u;
+        __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
+        __builtin_amdgcn_wave_barrier();
+        if (lane < H) {
+            stream_or_row(T, (uint32_t)((6 * H + lane) * W), food & p.hi_mask, W);    // blue food: x >= int(W/2) (capture.py:336)
+            stream_or_row(T, (uint32_t)((7 * H + lane) * W), food & p.lo_mask, W);    // red food
+        }
+        if (lane < 4) {
+            const int x = pt & 0xFF, y = (pt >> 8) & 0xFF;
+            const int plane = lane == agent ? 1 : (((lane ^ agent) == 2) ? 4 : 5);      // gymPacMan.py:205-215
+            const uint32_t off = (uint32_t)((plane * H + y) * W + x);
+            atomicOr(&T[off >> 5], 1u << (off & 31));
+        } else if (lane < 8) {
+            const uint32_t cxy = (pt >> (16 * ((lane - 4) & 1))) & 0xFFFFu;
+            if (cxy != 0xFFFFu) {
+                const int x = cxy & 0xFF, y = cxy >> 8;
+                const int plane = (2 * x > W) ? 2 : 3;                                  // halfList: blue x > W/2, red x <= W/2
+                const uint32_t off = (uint32_t)((plane * H + y) * W + x);
+                atomicOr(&T[off >> 5], 1u << (off & 31));
+            }
+        }
+        const uint32_t carry = (b_self >> 8) & 0xFFF;
+        const int fself = (H + (int)((a_self >> 8) & 0xFF)) * W + (int)(a_self & 0xFF);
+        __builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "wavefront");
+        __builtin_amdgcn_wave_barrier();
+
+        uint4 *out = obs + (size_t)ql * n_vec;
+        for (int k = first_vec + lane; k < n_vec; k += 64) {
+            const uint32_t e0 = (uint32_t)k * VEC;
+            const uint32_t bits = T[e0 >> 5] >> (e0 & 31);
+            uint4 v = *reinterpret_cast<const uint4 *>(&lut[(bits & 15u) * 4]);
+            const uint32_t d = (uint32_t)(fself - (int)e0);
+            if (d < (uint32_t)VEC) patch_self<0>(v, (int)d, carry);
+            out[k] = v;
+        }
+        __builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "wavefront");     // the table is rewritten for the next block
+        __builtin_amdgcn_wave_barrier();
+    }
+}
+
+// ---------------------------------------------------------------------------------------------------------------
 // The same expansion with ONE wavefront per ENV for uint8 planes: at 1 byte per element an (env, agent) block is 1.2 KB, i.e.
 // one or two store instructions per lane behind a fixed ~2 us of snapshot-load latency and table set-up -- pmx_expand_kernel is
 // issue / latency bound there (0.39 of the HBM peak).  Here a wave issues the snapshot loads of all four agents together, builds
@@ -1497,6 +1684,23 @@ extern "C" hipError_t pmx_launch_rule(const PmxTickParams *p, int H, hipStream_t
     default: PMX_RULE_LAUNCH(B, 32); break;                                                   \
     }
     if (p->dist) { PMX_RULE_PICK(true) } else { PMX_RULE_PICK(false) }
+    return hipGetLastError();
+}
+
+// The fused tick (pmx_tick_fused_kernel): N / 64 workgroups of 16 waves.  The caller (pmx_step) has checked what the kernel
+// assumes: float32 planes of all four agents, one layout, no bots, H <= 20, N % 64 == 0.  With H <= 20 and W <= 32 the LDS
+// request is at most 61 952 bytes, inside the 64 KB a launch may ask for without a function attribute.
+extern "C" hipError_t pmx_launch_tick_fused(const PmxTickParams *p, int reverse, hipStream_t st)
+{
+    const int H = p->lay_H, W = p->lay_W;
+    if (H > 20 || (p->N % PMX_RULE_BLOCK) != 0 || p->layout_idx || p->dist || !p->obs || p->n_emit != 4) return hipErrorInvalidValue;
+    const size_t lds = ((size_t)fused_rule_words(H) + (size_t)fused_snap_rows(H) * PMX_RULE_BLOCK + 64 + 32 +
+                        (size_t)PMX_FUSED_WAVES * fused_tab_stride(H, W)) * sizeof(uint32_t);
+    if (lds > ((size_t)64 << 10)) return hipErrorInvalidValue;
+    const dim3 grid(p->N / PMX_RULE_BLOCK), block(PMX_FUSED_WAVES * 64);
+    if (H <= 12) hipLaunchKernelGGL(pmx_tick_fused_kernel<12>, grid, block, lds, st, *p, reverse);
+    else if (H <= 16) hipLaunchKernelGGL(pmx_tick_fused_kernel<16>, grid, block, lds, st, *p, reverse);
+    else hipLaunchKernelGGL(pmx_tick_fused_kernel<20>, grid, block, lds, st, *p, reverse);
     return hipGetLastError();
 }
 

@@ -211,9 +211,13 @@ class PmxVecEnv:
         _lib.check(self.lib.pmx_profile_begin(self.handle, int(max_launches)), "pmx_profile_begin")
 
     def set_tuning(self, key, value):
-        """Launch tuning of the expansion kernel for measurements (pmx_set_tuning): "expand_alt" (0 = always the same sweep
-        direction, -1 = the default alternation)."""
+        """Launch tuning (pmx_set_tuning): "expand_alt" (0 = always the same sweep direction, -1 = the default alternation)
+        and "fused_min_envs" (step() runs the tick in one launch from this many envs on, -1 = one workgroup per CU)."""
         _lib.check(self.lib.pmx_set_tuning(self.handle, key.encode(), int(value)), "pmx_set_tuning")
+
+    def last_step_fused(self):
+        """True when the last step() ran the whole tick in one launch (pmx_last_step_fused)."""
+        return bool(self.lib.pmx_last_step_fused(self.handle))
 
     def profile_end(self):
         """-> dict(rule_ms, rule_launches, expand_ms, expand_launches): summed kernel times from HIP events."""
