@@ -670,7 +670,8 @@ __device__ __forceinline__ void init_env(Env &e, const Ctx &c)
 
 // gymPacMan.py:171-193: everything after the four sub-steps.
 // Returns true when the env finished and was reset to the fresh game (auto_reset).
-template <int HB = 0>
+// FRESH_SNAP = false (pmx_tick_fused_kernel): the caller stores the fresh game's snapshots itself.
+template <int HB = 0, bool FRESH_SNAP = true>
 __device__ __forceinline__ bool tick_finish(Env &e, Acc &a, const Ctx &c_in, const PmxTickParams &p, int env, bool fused)
 {
     Ctx c = c_in;             // a reset may move the env to another layout of the pool (redraw_layouts)
@@ -707,8 +708,10 @@ __device__ __forceinline__ bool tick_finish(Env &e, Acc &a, const Ctx &c_in, con
         if (p.layout_idx_rw) switch_layout(c, p, env, redraw_layout(c.rng_key, e.ticks, p.n_layouts));
         init_env(e, c);
         // the observations of a finished env are those of the fresh game for all four agents (gymPacMan.py:135-137)
-        const size_t snap_sz = (size_t)PMX_SNAP_WORDS(c.H) * p.N;
-        for (int s = 0; s < 3; ++s) store_snapshot(e, c, p.snap + s * snap_sz, p.N, env);
+        if constexpr (FRESH_SNAP) {
+            const size_t snap_sz = (size_t)PMX_SNAP_WORDS(c.H) * p.N;
+            for (int s = 0; s < 3; ++s) store_snapshot(e, c, p.snap + s * snap_sz, p.N, env);
+        }
     }
     if (p.legal) {
         uint32_t m = 0;
@@ -1161,20 +1164,27 @@ __global__ __launch_bounds__(PMX_BLOCK) void pmx_expand_kernel(PmxExpandParams p
 // ---------------------------------------------------------------------------------------------------------------
 // The whole tick in ONE launch (pmx_step with float32 planes, all four agents, one layout, no bots, H <= 20, N % 64 == 0 and at
 // least one workgroup per CU: pmx_step's fused_min_envs).  Workgroup g owns envs 64 g .. 64 g + 63 from the state load to the last
-// plane byte: no workgroup reads what another one wrote in this launch, and the only synchronisation is ONE __syncthreads().
-//   phase A  wave 0 runs the rules of its 64 envs with pmx_rule_kernel's device functions and lane mapping; where that kernel
-//            stores a snapshot to global memory, this one copies the H + 10 words into the LDS area snap[4][..][64] (slot 3: the
-//            H + 13 words of the final state).  Waves 1-15 store the wall vectors of the workgroup's 256 (env, agent) blocks with
-//            streaming stores, as write_walls does.
-//   phase B  all 16 waves: the four LDS slots go to p.snap / p.state with 16-byte stores (pmx_observe, pmx_emit_team_obs,
-//            pmx_step_agent and the next tick read them there); the 256 blocks are dealt to the waves, and each is expanded as
-//            pmx_expand_kernel<0, false, true> expands it, the snapshot words coming from LDS.
+// plane byte: no workgroup reads what another one wrote in this launch, and the only synchronisation is TWO __syncthreads().
+//   phase A0 wave 0 loads the state of its 64 envs and runs sub-step 0 with pmx_rule_kernel's device functions and lane mapping;
+//            where that kernel stores a snapshot to global memory, this one copies the H + 10 words into the LDS area
+//            snap[4][..][64].  Waves 1-15 store the wall vectors of the workgroup's 256 (env, agent) blocks with streaming
+//            stores, as write_walls does.  Barrier.
+//   phase A1 wave 0 runs sub-steps 1-3 and tick_finish (slots 1, 2 and, with the H + 13 words of the final state, 3); waves 1-15
+//            expand the 64 agent-0 blocks from slot 0, which is complete: HBM has plane bytes to store while the rule wave runs.
+//            An env that finishes shows the fresh game to all four agents, so its agent-0 block is stale: wave 0 writes the fresh
+//            game to slots 1 and 2 (NOT to slot 0, which the other waves are reading) and leaves the ballot of such envs in LDS.
+//            Barrier.
+//   phase B  wave 0 copies slot 1 over slot 0 for the envs of the ballot and writes slot 0 to p.snap, the other waves write slots
+//            1-3 to p.snap / p.state with 16-byte stores (pmx_observe, pmx_emit_team_obs, pmx_step_agent and the next tick read
+//            them there); every wave expands the agent-0 blocks of the ballot it stored in A1 again, from slot 1 (the same lane
+//            stores to the same address twice, in program order); the 192 blocks of agents 1-3 are dealt to the 16 waves, and
+//            each is expanded as pmx_expand_kernel<0, false, true> expands it, the snapshot words coming from LDS.
 // What the two launches cost and this one does not: the end-of-kernel write-back and the second dispatch, and the snapshot
-// round trip through memory in front of every expansion wave.  No global load is issued in phase B: loads return in order
-// behind the stores in front of them, and a wave that waited for one would wait for its plane stores.
+// round trip through memory in front of every expansion wave.  No global load is issued by waves 1-15, or by any wave in phase
+// B: loads return in order behind the stores in front of them, and a wave that waited for one would wait for its plane stores.
 // (That is also why the wall words of the stream tables come from an LDS copy of the layout's wall_stream.)
-// LDS (dynamic): make_ctx's area | snap | look-up table (16 x 16 bytes) | wall_stream (32 words) | 16 stream tables of
-// fused_tab_stride words.
+// LDS (dynamic): make_ctx's area | snap | look-up table (16 x 16 bytes) | wall_stream (32 words) | ballot (2 words + 2 of
+// padding) | 16 stream tables of fused_tab_stride words.
 // ---------------------------------------------------------------------------------------------------------------
 #define PMX_FUSED_WAVES 16
 __host__ __device__ inline int fused_rule_words(int H) { return 32 + (3 * H + 16) * PMX_RULE_BLOCK; }
@@ -1205,6 +1215,58 @@ __device__ __forceinline__ void snapshot_to_lds(const Env &e, const Ctx &c, uint
     }
 }
 
+// One wave expands the planes behind the wall vectors of one (env, agent) block: S = the env's column of the snapshot slot,
+// T = the wave's stream table, out = the block.  Ordinary stores from first_vec on.
+__device__ __forceinline__ void fused_expand_block(const PmxTickParams &p, const uint32_t *S, int agent, uint32_t *T, const uint32_t *lut,
+                                                   uint32_t wallw, uint4 *out, int lane)
+{
+    constexpr int VEC = ObsVec<0>::VEC;
+    const int H = p.lay_H, W = p.lay_W, HW = H * W;
+    const int first_vec = HW / VEC, n_vec = 8 * HW / VEC, n_words = (8 * HW + 31) >> 5;
+    const uint32_t food = lane < H ? S[lane * PMX_RULE_BLOCK] : 0u;
+    uint32_t pt = 0;
+    if (lane < 4) pt = S[PMX_W_AGENT_A(H, lane) * PMX_RULE_BLOCK];
+    else if (lane < 8) pt = S[PMX_W_CAPS(H, (lane - 4) >> 1) * PMX_RULE_BLOCK];
+    const uint32_t a_self = S[PMX_W_AGENT_A(H, agent) * PMX_RULE_BLOCK];
+    const uint32_t b_self = S[PMX_W_AGENT_B(H, agent) * PMX_RULE_BLOCK];
+    for (int k = lane; k < n_words + 1; k += 64) T[k] = k < 32 ? wallw : 0u;
+    __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
+    __builtin_amdgcn_wave_barrier();
+    if (lane < H) {
+        stream_or_row(T, (uint32_t)((6 * H + lane) * W), food & p.hi_mask, W);    // blue food: x >= int(W/2) (capture.py:336)
+        stream_or_row(T, (uint32_t)((7 * H + lane) * W), food & p.lo_mask, W);    // red food
+    }
+    if (lane < 4) {
+        const int x = pt & 0xFF, y = (pt >> 8) & 0xFF;
+        const int plane = lane == agent ? 1 : (((lane ^ agent) == 2) ? 4 : 5);      // gymPacMan.py:205-215
+        const uint32_t off = (uint32_t)((plane * H + y) * W + x);
+        atomicOr(&T[off >> 5], 1u << (off & 31));
+    } else if (lane < 8) {
+        const uint32_t cxy = (pt >> (16 * ((lane - 4) & 1))) & 0xFFFFu;
+        if (cxy != 0xFFFFu) {
+            const int x = cxy & 0xFF, y = cxy >> 8;
+            const int plane = (2 * x > W) ? 2 : 3;                                  // halfList: blue x > W/2, red x <= W/2
+            const uint32_t off = (uint32_t)((plane * H + y) * W + x);
+            atomicOr(&T[off >> 5], 1u << (off & 31));
+        }
+    }
+    const uint32_t carry = (b_self >> 8) & 0xFFF;
+    const int fself = (H + (int)((a_self >> 8) & 0xFF)) * W + (int)(a_self & 0xFF);
+    __builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "wavefront");
+    __builtin_amdgcn_wave_barrier();
+
+    for (int k = first_vec + lane; k < n_vec; k += 64) {
+        const uint32_t e0 = (uint32_t)k * VEC;
+        const uint32_t bits = T[e0 >> 5] >> (e0 & 31);
+        uint4 v = *reinterpret_cast<const uint4 *>(&lut[(bits & 15u) * 4]);
+        const uint32_t d = (uint32_t)(fself - (int)e0);
+        if (d < (uint32_t)VEC) patch_self<0>(v, (int)d, carry);
+        out[k] = v;
+    }
+    __builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "wavefront");     // the table is rewritten for the next block
+    __builtin_amdgcn_wave_barrier();
+}
+
 template <int HB>
 __global__ __launch_bounds__(PMX_FUSED_WAVES * 64) void pmx_tick_fused_kernel(PmxTickParams p, int reverse)
 {
@@ -1218,38 +1280,33 @@ __global__ __launch_bounds__(PMX_FUSED_WAVES * 64) void pmx_tick_fused_kernel(Pm
     uint32_t *snapL = lds + fused_rule_words(H);
     uint32_t *lut = snapL + fused_snap_rows(H) * PMX_RULE_BLOCK;
     uint32_t *wstream = lut + 64;                                    // the layout's wall_stream: plane 0 of every stream table
-    uint32_t *T = wstream + 32 + wave * fused_tab_stride(H, W);
+    uint32_t *freshL = wstream + 32;                                 // the ballot of the envs that finished in this tick
+    uint32_t *T = freshL + 4 + wave * fused_tab_stride(H, W);
     const int slot_words = PMX_SNAP_WORDS(H) * PMX_RULE_BLOCK;
     const int first_vec = HW / VEC, n_vec = 8 * HW / VEC;
     uint4 *obs = reinterpret_cast<uint4 *>(p.obs) + (size_t)group * NB * n_vec;
+    const int env = group * PMX_RULE_BLOCK + lane;
 
+    // what the rule wave keeps across the first barrier (wave 0 only; both branches on `wave` are wave-uniform)
+    Env e;
+    Acc a = { 0.0, 0.0, 0, 0, 0, 0, 0 };
+    Ctx c;
+    uint32_t av = 0;
+    uint32_t *col = snapL + lane;
+
+    // ---- phase A0 ----
     if (wave == 0) {
-        const int env = group * PMX_RULE_BLOCK + lane;
         RawEnv raw;
         uint32_t rows[HB];
         load_env_issue<HB>(raw, rows, p.state, p.N, env, H);
-        const uint32_t av = reinterpret_cast<const uint32_t *>(p.actions)[env];   // 4 int8 actions
-        Ctx c = make_ctx_fill(p, lds, env, lane);
+        av = reinterpret_cast<const uint32_t *>(p.actions)[env];   // 4 int8 actions
+        c = make_ctx_fill(p, lds, env, lane);
         __builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "wavefront");     // the wall rows: only this wave reads them
         __builtin_amdgcn_wave_barrier();
-        Env e;
         load_env_commit<HB>(e, c, raw, rows);
-        Acc a = { 0.0, 0.0, 0, 0, 0, 0, 0 };
         count_food<HB>(a, c, rows);
-        uint32_t *col = snapL + lane;
         tick_substep<0, false>(e, a, c, (int)(int8_t)(av & 0xFF));
         snapshot_to_lds<HB, false>(e, c, col);
-        tick_substep<1, false>(e, a, c, (int)(int8_t)((av >> 8) & 0xFF));
-        snapshot_to_lds<HB, false>(e, c, col + slot_words);
-        tick_substep<2, false>(e, a, c, (int)(int8_t)((av >> 16) & 0xFF));
-        snapshot_to_lds<HB, false>(e, c, col + 2 * slot_words);
-        tick_substep<3, false>(e, a, c, (int)(int8_t)((av >> 24) & 0xFF));
-        const bool fresh = tick_finish<HB>(e, a, c, p, env, true);
-        snapshot_to_lds<HB, true>(e, c, col + 3 * slot_words);
-        if (fresh) {   // the observations of a finished env are those of the fresh game for all four agents (tick_finish stored the
-                       // same words to p.snap; phase B stores them again)
-            for (int s = 0; s < 3; ++s) snapshot_to_lds<HB, false>(e, c, col + s * slot_words);
-        }
     } else {
         constexpr int MAXJ = 32 * 32 / VEC / 64;
         if (wave == 1 && lane < 16) *reinterpret_cast<uint4 *>(&lut[4 * lane]) = pack_obs<0>(lane);
@@ -1273,9 +1330,46 @@ __global__ __launch_bounds__(PMX_FUSED_WAVES * 64) void pmx_tick_fused_kernel(Pm
     }
     __syncthreads();
 
-    {   // the four slots -> p.snap[0..2] and p.state: rows of 64 envs = 16 vectors of 16 bytes, [3][H + 10][N] is one row range
-        const int n_rows = fused_snap_rows(H), snap_rows = 3 * PMX_SNAP_WORDS(H);
-        for (int i = threadIdx.x; i < n_rows * 16; i += PMX_FUSED_WAVES * 64) {
+    // ---- phase A1: slot 0, the look-up table and wstream are complete ----
+    const uint32_t wallw = lane < 32 ? wstream[lane] : 0u;           // (zero behind the H*W wall bits)
+    if (wave == 0) {
+        tick_substep<1, false>(e, a, c, (int)(int8_t)((av >> 8) & 0xFF));
+        snapshot_to_lds<HB, false>(e, c, col + slot_words);
+        tick_substep<2, false>(e, a, c, (int)(int8_t)((av >> 16) & 0xFF));
+        snapshot_to_lds<HB, false>(e, c, col + 2 * slot_words);
+        tick_substep<3, false>(e, a, c, (int)(int8_t)((av >> 24) & 0xFF));
+        const bool fresh = tick_finish<HB, false>(e, a, c, p, env, true);
+        snapshot_to_lds<HB, true>(e, c, col + 3 * slot_words);
+        if (fresh) {   // the observations of a finished env are those of the fresh game for all four agents; slot 0 follows in
+                       // phase B, when no wave reads it any more
+            snapshot_to_lds<HB, false>(e, c, col + slot_words);
+            snapshot_to_lds<HB, false>(e, c, col + 2 * slot_words);
+        }
+        const unsigned long long fb = __ballot(fresh);
+        if (lane == 0) { freshL[0] = (uint32_t)fb; freshL[1] = (uint32_t)(fb >> 32); }
+    } else {
+        for (int j = wave - 1; j < PMX_RULE_BLOCK; j += PMX_FUSED_WAVES - 1) {
+            const int el = reverse ? PMX_RULE_BLOCK - 1 - j : j;
+            fused_expand_block(p, snapL + el, 0, T, lut, wallw, obs + (size_t)(4 * el) * n_vec, lane);
+        }
+    }
+    __syncthreads();
+
+    // ---- phase B ----
+    {   // the four slots -> p.snap[0..2] and p.state: rows of 64 envs = 16 vectors of 16 bytes, [3][H + 10][N] is one row range.
+        // Slot 0 is wave 0's: it first gives the envs that finished the fresh game there (slot 1 holds it), in program order.
+        const int n_rows = fused_snap_rows(H), rows0 = PMX_SNAP_WORDS(H), snap_rows = 3 * rows0;
+        int i, i_end, i_step;
+        if (wave == 0) {
+            if ((lane < 32 ? freshL[0] >> lane : freshL[1] >> (lane - 32)) & 1u)
+                for (int r = 0; r < rows0; ++r) col[r * PMX_RULE_BLOCK] = col[slot_words + r * PMX_RULE_BLOCK];
+            __builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "wavefront");
+            __builtin_amdgcn_wave_barrier();
+            i = lane; i_end = rows0 * 16; i_step = 64;
+        } else {
+            i = rows0 * 16 + (int)threadIdx.x - 64; i_end = n_rows * 16; i_step = (PMX_FUSED_WAVES - 1) * 64;
+        }
+        for (; i < i_end; i += i_step) {
             const int row = i >> 4, q4 = 4 * (i & 15);
             const uint4 w = *reinterpret_cast<const uint4 *>(snapL + row * PMX_RULE_BLOCK + q4);
             uint32_t *dst = row < snap_rows ? p.snap + (size_t)row * p.N : p.state + (size_t)(row - snap_rows) * p.N;
@@ -1283,56 +1377,24 @@ __global__ __launch_bounds__(PMX_FUSED_WAVES * 64) void pmx_tick_fused_kernel(Pm
         }
     }
 
-    const int n_words = (8 * HW + 31) >> 5;
-    const uint32_t wallw = lane < 32 ? wstream[lane] : 0u;           // (zero behind the H*W wall bits)
-    for (int it = 0; it < NB / PMX_FUSED_WAVES; ++it) {
-        const int b = it * PMX_FUSED_WAVES + wave;
-        const int ql = reverse ? NB - 1 - b : b;
-        const int agent = ql & 3;
-        const uint32_t *S = snapL + agent * slot_words + (ql >> 2);      // agent 3: the final state
-        const uint32_t food = lane < H ? S[lane * PMX_RULE_BLOCK] : 0u;
-        uint32_t pt = 0;
-        if (lane < 4) pt = S[PMX_W_AGENT_A(H, lane) * PMX_RULE_BLOCK];
-        else if (lane < 8) pt = S[PMX_W_CAPS(H, (lane - 4) >> 1) * PMX_RULE_BLOCK];
-        const uint32_t a_self = S[PMX_W_AGENT_A(H, agent) * PMX_RULE_BLOCK];
-        const uint32_t b_self = S[PMX_W_AGENT_B(H, agent) * PMX_RULE_BLOCK];
-        for (int k = lane; k < n_words + 1; k += 64) T[k] = k < 32 ? wallw : 0u;
-        __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
-        __builtin_amdgcn_wave_barrier();
-        if (lane < H) {
-            stream_or_row(T, (uint32_t)((6 * H + lane) * W), food & p.hi_mask, W);    // blue food: x >= int(W/2) (capture.py:336)
-            stream_or_row(T, (uint32_t)((7 * H + lane) * W), food & p.lo_mask, W);    // red food
+    // the agent-0 blocks of the envs that finished, again and by the wave that stored them in A1: from slot 1, the fresh game
+    const uint32_t fresh_lo = __builtin_amdgcn_readfirstlane(freshL[0]), fresh_hi = __builtin_amdgcn_readfirstlane(freshL[1]);
+    if (wave != 0 && (fresh_lo | fresh_hi) != 0u) {
+        for (int j = wave - 1; j < PMX_RULE_BLOCK; j += PMX_FUSED_WAVES - 1) {
+            const int el = reverse ? PMX_RULE_BLOCK - 1 - j : j;
+            if (((el < 32 ? fresh_lo >> el : fresh_hi >> (el - 32)) & 1u) == 0u) continue;
+            fused_expand_block(p, snapL + slot_words + el, 0, T, lut, wallw, obs + (size_t)(4 * el) * n_vec, lane);
         }
-        if (lane < 4) {
-            const int x = pt & 0xFF, y = (pt >> 8) & 0xFF;
-            const int plane = lane == agent ? 1 : (((lane ^ agent) == 2) ? 4 : 5);      // gymPacMan.py:205-215
-            const uint32_t off = (uint32_t)((plane * H + y) * W + x);
-            atomicOr(&T[off >> 5], 1u << (off & 31));
-        } else if (lane < 8) {
-            const uint32_t cxy = (pt >> (16 * ((lane - 4) & 1))) & 0xFFFFu;
-            if (cxy != 0xFFFFu) {
-                const int x = cxy & 0xFF, y = cxy >> 8;
-                const int plane = (2 * x > W) ? 2 : 3;                                  // halfList: blue x > W/2, red x <= W/2
-                const uint32_t off = (uint32_t)((plane * H + y) * W + x);
-                atomicOr(&T[off >> 5], 1u << (off & 31));
-            }
-        }
-        const uint32_t carry = (b_self >> 8) & 0xFFF;
-        const int fself = (H + (int)((a_self >> 8) & 0xFF)) * W + (int)(a_self & 0xFF);
-        __builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "wavefront");
-        __builtin_amdgcn_wave_barrier();
+    }
 
-        uint4 *out = obs + (size_t)ql * n_vec;
-        for (int k = first_vec + lane; k < n_vec; k += 64) {
-            const uint32_t e0 = (uint32_t)k * VEC;
-            const uint32_t bits = T[e0 >> 5] >> (e0 & 31);
-            uint4 v = *reinterpret_cast<const uint4 *>(&lut[(bits & 15u) * 4]);
-            const uint32_t d = (uint32_t)(fself - (int)e0);
-            if (d < (uint32_t)VEC) patch_self<0>(v, (int)d, carry);
-            out[k] = v;
-        }
-        __builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "wavefront");     // the table is rewritten for the next block
-        __builtin_amdgcn_wave_barrier();
+    // agents 1-3: 192 blocks over 16 waves, an env's three blocks on neighbouring waves (their shared 128-byte lines are stored
+    // close together in time)
+    constexpr int NB3 = 3 * PMX_RULE_BLOCK;
+    for (int it = 0; it < NB3 / PMX_FUSED_WAVES; ++it) {
+        const int b = it * PMX_FUSED_WAVES + wave;
+        const int m = reverse ? NB3 - 1 - b : b;
+        const int el = m / 3, agent = 1 + m - 3 * el;
+        fused_expand_block(p, snapL + agent * slot_words + el, agent, T, lut, wallw, obs + (size_t)(4 * el + agent) * n_vec, lane);   // agent 3: the final state
     }
 }
 
@@ -1694,7 +1756,7 @@ extern "C" hipError_t pmx_launch_tick_fused(const PmxTickParams *p, int reverse,
 {
     const int H = p->lay_H, W = p->lay_W;
     if (H > 20 || (p->N % PMX_RULE_BLOCK) != 0 || p->layout_idx || p->dist || !p->obs || p->n_emit != 4) return hipErrorInvalidValue;
-    const size_t lds = ((size_t)fused_rule_words(H) + (size_t)fused_snap_rows(H) * PMX_RULE_BLOCK + 64 + 32 +
+    const size_t lds = ((size_t)fused_rule_words(H) + (size_t)fused_snap_rows(H) * PMX_RULE_BLOCK + 64 + 32 + 4 +
                         (size_t)PMX_FUSED_WAVES * fused_tab_stride(H, W)) * sizeof(uint32_t);
     if (lds > ((size_t)64 << 10)) return hipErrorInvalidValue;
     const dim3 grid(p->N / PMX_RULE_BLOCK), block(PMX_FUSED_WAVES * 64);
