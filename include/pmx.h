@@ -365,9 +365,11 @@ int pmx_flatten_sum_to_f32(int32_t n, const void *const *src_dev, const uint8_t 
  * MAPPOAgent.actor_backbone (pacman_mappo_resnet.py:104-113 with ResidualBlock :49-67):
  *   conv3x3(8->16) GELU conv3x3(16->32) GELU 3 x [conv3x3 GroupNorm(4) GELU conv3x3 GroupNorm(4) (+x) GELU], bf16 matrix-core
  *   products with fp32 accumulation, GroupNorm and GELU in fp32 on the bf16-rounded convolution output (what bf16 autocast
- *   computes).  Boards whose padded area H*(W+2) needs 10, 11 or 28 position tiles of 16 are supported (tinyCapture,
- *   smallCapture; the 20 x 20 boards: bloxCapture and the generated mazes); pmx_actor_supported() says so and callers keep the
- *   library convolutions for the rest.
+ *   computes).  Domain: every board with W in 8..32, H in 3..32 and H*W <= 640 cells -- the boards on which the attention
+ *   backward kernel runs too, so such a board trains without a library convolution.  The padded area H*(W+2) <= 704 then needs
+ *   2 .. 44 position tiles of 16; a board runs on the smallest tile-count bucket (10, 11, 16, 28, 36, 44) that holds its own
+ *   count, and every buffer size below is the bucket's.  pmx_actor_supported() returns 1 on the domain and 0 elsewhere (above 640
+ *   cells, sides out of range); the other entry points then return PMX_ERR_UNSUPPORTED and callers keep the library convolutions.
  * Parameters arrive as float32 device pointers in nn.Module order: conv_w[l] is [cout][cin][3][3], l = 0,1 the stem, then
  * conv1 / conv2 of the three blocks; gn_w / gn_b [6][32] are gn1, gn2 of the three blocks. */
 typedef struct {
@@ -380,7 +382,8 @@ typedef struct {
 #define PMX_ACTOR_GRAD_FLOATS 74496    /* backward's fp32 gradient buffer: weight-gradient tiles + bias / GroupNorm gradients */
 int pmx_actor_supported(int32_t H, int32_t W);
 /* bytes of the activation save area (training forward -> backward) and of backward's scratch for B samples, and of the
- * scratch an inference-only forward needs (independent of B); any of the three pointers may be NULL */
+ * scratch an inference-only forward needs (independent of B); any of the three pointers may be NULL.  The single source of
+ * these sizes: they follow the board's tile-count bucket, not its own tile count, and grow monotonically with B. */
 int pmx_actor_sizes(int32_t H, int32_t W, int64_t B, int64_t *save_bytes, int64_t *scratch_bytes, int64_t *infer_scratch_bytes);
 /* parameters -> pack_dev [PMX_ACTOR_PACK_BYTES]; once per optimizer step (the weights changed) or once per rollout */
 int pmx_actor_pack(const pmx_actor_params *params, void *pack_dev, void *stream);
@@ -469,7 +472,8 @@ typedef struct {
 int pmx_encoder_pack(int32_t n_layers, const pmx_encoder_layer_params *layers, void *stream);
 
 /* ---- The critic's projector: conv3x3(8 -> 32) + bias + 2-D positional encoding -> batch-major tokens ---------------------
- * MAPPOAgent.critic_projector and pos_encoder (pacman_mappo_resnet.py:126-127, :69-95, :164) on boards pmx_actor_supported() accepts:
+ * MAPPOAgent.critic_projector and pos_encoder (pacman_mappo_resnet.py:126-127, :69-95, :164) on boards pmx_actor_supported() accepts
+ * (W in 8..32, H in 3..32, H*W <= 640; PMX_ERR_UNSUPPORTED elsewhere):
  * obs_dev [B][8][H][W] of PMX_OBS_* elements -> tokens_dev [B][H*W][32] bfloat16 (what flatten(2).permute(2, 0, 1) yields, batch-major),
  * bf16 products with fp32 accumulation, the convolution (+ bias) rounded to bfloat16 before the table (posenc_dev [H*W][32] float32) is
  * added in bfloat16, as autocast computes it.  Backward returns the weight and bias gradients only (the observations need none):

@@ -400,6 +400,10 @@ __global__ __launch_bounds__(256, 2) void pmx_actor_fwd_kernel(const IN_T *__res
 // map done, all partial sums there); every wave normalises / activates its tiles and writes them back; barrier.  Same arithmetic
 // per element as pmx_actor_fwd_kernel (the statistics are summed in another order), same dumps for the backward kernels.
 // ---------------------------------------------------------------------------------------------------------------
+// block shape of the several-waves-per-sample kernels: four waves shared by 4 / WS samples, or one sample's eight waves
+__host__ __device__ constexpr int split_threads(int ws) { return ws > 4 ? 64 * ws : 256; }
+__host__ __device__ constexpr int split_samples(int ws) { return ws > 4 ? 1 : 4 / ws; }
+
 template <typename IN_T>
 __device__ __forceinline__ void load_obs_block(const IN_T *__restrict__ obs, char *map, const Geom &G, int tid, int nthreads)
 {
@@ -418,13 +422,13 @@ __device__ __forceinline__ void load_obs_block(const IN_T *__restrict__ obs, cha
 }
 
 template <int NT, typename IN_T, bool SAVE, int WS>
-__global__ __launch_bounds__(256, 2) void pmx_actor_fwd_split_kernel(const IN_T *__restrict__ obs, const char *__restrict__ pack,
+__global__ __launch_bounds__(split_threads(WS), 2) void pmx_actor_fwd_split_kernel(const IN_T *__restrict__ obs, const char *__restrict__ pack,
                                                                     uint2 *__restrict__ feat, uint2 *__restrict__ hsave,
                                                                     uint2 *__restrict__ ysave, float *__restrict__ stats,
                                                                     uint2 *__restrict__ rtmp, int B, int H, int W, float eps)
 {
     constexpr int NTW = (NT + WS - 1) / WS;                    // tiles per wave; WS waves per sample, 4 / WS samples per block
-    constexpr int SPB = 4 / WS;
+    constexpr int SPB = split_samples(WS), NTHR = split_threads(WS);   // (WS = 8: one sample per 512-thread block)
     extern __shared__ __attribute__((aligned(16))) char smem[];
     const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
     const int p = lane & 15, g = lane >> 4;
@@ -433,9 +437,9 @@ __global__ __launch_bounds__(256, 2) void pmx_actor_fwd_split_kernel(const IN_T 
     const int sub = __builtin_amdgcn_readfirstlane(wave / WS), wq = __builtin_amdgcn_readfirstlane(wave % WS);
     char *map = smem + (size_t)sub * G.MP * 64;
     float *xs = reinterpret_cast<float *>(smem + (size_t)SPB * G.MP * 64) + sub * (WS * 8);   // [WS waves][4 groups][sum, sum of squares]
-    for (int i = threadIdx.x; i < SPB * G.MP * 4; i += 256) reinterpret_cast<uint4 *>(smem)[i] = uint4{0, 0, 0, 0};
+    for (int i = threadIdx.x; i < SPB * G.MP * 4; i += NTHR) reinterpret_cast<uint4 *>(smem)[i] = uint4{0, 0, 0, 0};
     __shared__ int cell_tab[NT * 16];                           // position -> board cell of the feature row (see pmx_actor_fwd_kernel)
-    for (int i = threadIdx.x; i < NT * 16; i += 256) {
+    for (int i = threadIdx.x; i < NT * 16; i += NTHR) {
         const int q = G.WP + i, row = q / G.WP, col = q - row * G.WP;
         cell_tab[i] = (col >= 1 && col <= W && row <= H) ? (row - 1) * W + (col - 1) : -1;
     }
@@ -853,13 +857,14 @@ __global__ __launch_bounds__(256, 1) void pmx_actor_bwd_data_kernel(const char *
 // wave per SIMD either way), the point is the length of a sample's serial chain.
 // ---------------------------------------------------------------------------------------------------------------
 template <int NT, int WS>
-__global__ __launch_bounds__(256, 2) void pmx_actor_bwd_data_split_kernel(const char *__restrict__ pack, const uint2 *__restrict__ dfeat,
+__global__ __launch_bounds__(split_threads(WS), 2) void pmx_actor_bwd_data_split_kernel(const char *__restrict__ pack, const uint2 *__restrict__ dfeat,
                                                                          const uint2 *__restrict__ hsave, const uint2 *__restrict__ ysave,
                                                                          const float *__restrict__ stats, bf16x8 *__restrict__ dasave,
                                                                          uint2 *__restrict__ sktmp, float *__restrict__ accpart, int B,
                                                                          int H, int W)
 {
-    constexpr int NTW = (NT + WS - 1) / WS, SPB = 4 / WS, KS = (NT + 1) / 2;
+    constexpr int NTW = (NT + WS - 1) / WS, SPB = split_samples(WS), KS = (NT + 1) / 2;
+    constexpr int NTHR = split_threads(WS), NW = NTHR / 64;
     // large boards (7 tiles per wave): the skip input of a layer is asked for at the top of that layer instead of one layer ahead
     // -- 28 registers that would be live across the input-gradient convolution next to the parked skip gradient (the kernel
     // spilled 27 registers at its 256-register budget with them)
@@ -870,11 +875,11 @@ __global__ __launch_bounds__(256, 2) void pmx_actor_bwd_data_split_kernel(const 
     Geom G;
     G.H = H, G.W = W, G.WP = W + 2, G.HW = H * W, G.MP = map_positions(NT, W + 2);
     const int sub = __builtin_amdgcn_readfirstlane(wave / WS), wq = __builtin_amdgcn_readfirstlane(wave % WS);
-    // LDS: [SPB maps][4 per-wave accumulators of NLAYER * 96 floats][SPB x WS x 8 floats of partial sums]
+    // LDS: [SPB maps][NW per-wave accumulators of NLAYER * 96 floats][SPB x WS x 8 floats of partial sums]
     char *map = smem + (size_t)sub * G.MP * 64;
     float *acc = reinterpret_cast<float *>(smem + (size_t)SPB * G.MP * 64) + wave * (NLAYER * 96);
-    float *xs = reinterpret_cast<float *>(smem + (size_t)SPB * G.MP * 64) + 4 * (NLAYER * 96) + sub * (WS * 8);
-    for (int i = threadIdx.x; i < SPB * G.MP * 4; i += 256) reinterpret_cast<uint4 *>(smem)[i] = uint4{0, 0, 0, 0};
+    float *xs = reinterpret_cast<float *>(smem + (size_t)SPB * G.MP * 64) + NW * (NLAYER * 96) + sub * (WS * 8);
+    for (int i = threadIdx.x; i < SPB * G.MP * 4; i += NTHR) reinterpret_cast<uint4 *>(smem)[i] = uint4{0, 0, 0, 0};
     for (int i = lane; i < NLAYER * 96; i += 64) acc[i] = 0.0f;
     const int t0 = __builtin_amdgcn_readfirstlane(wq * NTW);
     uint32_t vmask = 0;
@@ -1114,9 +1119,12 @@ __global__ __launch_bounds__(256, 2) void pmx_actor_bwd_data_split_kernel(const 
         __syncthreads();                                        // the last layer's map reads are done before the next sample's writes
     }
     __syncthreads();
-    for (int i = threadIdx.x; i < NLAYER * 96; i += 256) {
+    for (int i = threadIdx.x; i < NLAYER * 96; i += NTHR) {
         const float *a0 = reinterpret_cast<const float *>(smem + (size_t)SPB * G.MP * 64);
-        accpart[(size_t)blockIdx.x * (NLAYER * 96) + i] = (a0[i] + a0[NLAYER * 96 + i]) + (a0[2 * NLAYER * 96 + i] + a0[3 * NLAYER * 96 + i]);
+        float v = (a0[i] + a0[NLAYER * 96 + i]) + (a0[2 * NLAYER * 96 + i] + a0[3 * NLAYER * 96 + i]);
+        if constexpr (NW == 8)
+            v += (a0[4 * NLAYER * 96 + i] + a0[5 * NLAYER * 96 + i]) + (a0[6 * NLAYER * 96 + i] + a0[7 * NLAYER * 96 + i]);
+        accpart[(size_t)blockIdx.x * (NLAYER * 96) + i] = v;
     }
 }
 
@@ -1424,27 +1432,40 @@ int tiles_for(int H, int W) { return (H * (W + 2) + 15) / 16; }
 static const int kCin[NLAYER] = {8, 16, 32, 32, 32, 32, 32, 32};
 static const int kCout[NLAYER] = {16, 32, 32, 32, 32, 32, 32, 32};
 
-// position tiles with a kernel instantiation: 10 / 11 (tinyCapture 7 x 20, smallCapture 11 x 14: one wave per sample, or 2 / 4
-// waves per sample for small batches) and 28 (the 20 x 20 boards -- bloxCapture, the generated mazes: always four waves per sample)
-static bool tiles_supported(int nt) { return nt == 10 || nt == 11 || nt == 28; }
-constexpr bool large_board(int nt) { return nt > 16; }
+// Tile-count BUCKETS with a kernel instantiation.  A board runs on the smallest bucket >= its own tile count; the tail tiles lie
+// below the board's last row, so the kernels' own validity tests (vmask, cell_tab) mask them like pad columns and their part of the
+// map stays zero.  Every size a kernel or the host derives from the tile count -- dump strides, map_positions, the key-pair
+// blocks of the dH operand, the scratch slots, pmx_actor_sizes -- is the bucket's (the template parameter NT).
+//   10 / 11  exactly those counts (tinyCapture 7 x 20, smallCapture 11 x 14): one wave per sample, or 2 / 4 for small batches
+//   16       every other count up to 16: four waves per sample at every batch (<= 4 tiles per wave)
+//   28       17 .. 28 (the 20 x 20 boards -- bloxCapture, the generated mazes): four waves per sample (<= 7 tiles per wave)
+//   36 / 44  29 .. 36 and 37 .. 44: EIGHT waves per sample in one 512-thread block (<= 5 / 6 tiles per wave)
+static int bucket_for(int nt)
+{
+    if (nt == 10 || nt == 11) return nt;
+    return nt <= 16 ? 16 : nt <= 28 ? 28 : nt <= 36 ? 36 : nt <= 44 ? 44 : 0;
+}
+constexpr bool large_board(int nt) { return nt > 11; }                   // the several-waves-per-sample kernels at every batch
+constexpr int large_waves(int nt) { return nt > 28 ? 8 : 4; }            // ... with this many waves per sample
 
 extern "C" int pmx_actor_supported(int32_t H, int32_t W)
 {
-    if (H < 1 || W < 1 || H > PMX_MAX_DIM || W > PMX_MAX_DIM) return 0;
-    return tiles_supported(tiles_for(H, W)) ? 1 : 0;
+    // every board pmx_create takes, up to the 640 cells the attention backward kernel covers
+    if (H < 3 || W < 8 || H > PMX_MAX_DIM || W > PMX_MAX_DIM || H * W > 640) return 0;
+    return bucket_for(tiles_for(H, W)) ? 1 : 0;
 }
 
 extern "C" int pmx_actor_sizes(int32_t H, int32_t W, int64_t B, int64_t *save_bytes, int64_t *scratch_bytes, int64_t *infer_scratch_bytes)
 {
     if (!pmx_actor_supported(H, W) || B < 0) return PMX_ERR_UNSUPPORTED;
-    const int64_t dump = (int64_t)tiles_for(H, W) * 1024;            // one P-layout dump of one sample
+    const int nt = bucket_for(tiles_for(H, W));                      // the bucket's tile count: the kernels' strides
+    const int64_t dump = (int64_t)nt * 1024;                         // one P-layout dump of one sample
     if (save_bytes) *save_bytes = B * (8 * dump + 8 * dump + 8 * 4 * 2 * 4);
     const int64_t infer = 2048 * dump;                               // inference: one skip-input slot per resident sample
     if (infer_scratch_bytes) *infer_scratch_bytes = infer;
     // backward: dH operand fragments of the 8 layers + skip slots + the two kernels' partial rows
     if (scratch_bytes)
-        *scratch_bytes = B * 8 * (int64_t)((tiles_for(H, W) + 1) / 2) * 2048 + infer + 1024 * 768 * 4 + (int64_t)W_PART_ROWS * NLAYER * 36 * 256 * 4;
+        *scratch_bytes = B * 8 * (int64_t)((nt + 1) / 2) * 2048 + infer + 1024 * 768 * 4 + (int64_t)W_PART_ROWS * NLAYER * 36 * 256 * 4;
     return PMX_OK;
 }
 
@@ -1493,7 +1514,9 @@ template <typename K> int allow_lds(K kernel, size_t lds)
     const void *fn = reinterpret_cast<const void *>(kernel);
     for (int i = 0; i < n_done; ++i)
         if (done[i].fn == fn && done[i].dev == dev) return PMX_OK;
-    if (hipFuncSetAttribute(fn, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024) != hipSuccess) return PMX_ERR_HIP;
+    // the 160 KB of a CU hold the kernel's static LDS too (cell_tab / pos_tab, < 4 KB): ask for the rest.  The largest launch is two
+    // 50 KB maps.
+    if (hipFuncSetAttribute(fn, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024 - 4096) != hipSuccess) return PMX_ERR_HIP;
     if (n_done < 256) done[n_done++] = Key{fn, dev};               // (past 256 entries the attribute is simply set again)
     return PMX_OK;
 }
@@ -1527,8 +1550,8 @@ int launch_fwd(const void *obs, const void *pack, void *feat, void *save, void *
     if (large_board(NT) || B <= SPLIT_MAX_BATCH) {
         // several waves per sample (pmx_actor_fwd_split_kernel): small batches, and every batch of a large board (its
         // pre-activations do not fit one wave's registers); 2 048 skip slots exist in the scratch area
-        const int ws = large_board(NT) ? 4 : split_waves(B);
-        const int spb = 4 / ws;
+        const int ws = large_board(NT) ? large_waves(NT) : split_waves(B);
+        const int spb = split_samples(ws);
         const size_t lds_s = (size_t)spb * map_positions(NT, W + 2) * 64 + (size_t)spb * ws * 8 * sizeof(float);
         int64_t g64 = (B + spb - 1) / spb;
         if (g64 * spb > 2048) g64 = 2048 / spb;
@@ -1537,11 +1560,11 @@ int launch_fwd(const void *obs, const void *pack, void *feat, void *save, void *
     do {                                                                                                                    \
         int rc = allow_lds(pmx_actor_fwd_split_kernel<NT, IN_T, SAVEV, WSV>, lds_s);                                        \
         if (rc) return rc;                                                                                                  \
-        hipLaunchKernelGGL((pmx_actor_fwd_split_kernel<NT, IN_T, SAVEV, WSV>), dim3(grid), dim3(256), lds_s, st, (const IN_T *)obs, \
+        hipLaunchKernelGGL((pmx_actor_fwd_split_kernel<NT, IN_T, SAVEV, WSV>), dim3(grid), dim3(split_threads(WSV)), lds_s, st, (const IN_T *)obs, \
                            (const char *)pack, (uint2 *)feat, hs, ys, stt, rtmp, (int)B, H, W, 1e-5f);                       \
     } while (0)
         if constexpr (large_board(NT)) {
-            if (save) PMX_FWD_SPLIT(true, 4); else PMX_FWD_SPLIT(false, 4);
+            if (save) PMX_FWD_SPLIT(true, large_waves(NT)); else PMX_FWD_SPLIT(false, large_waves(NT));
         } else {
             if (save) { if (ws == 2) PMX_FWD_SPLIT(true, 2); else PMX_FWD_SPLIT(true, 4); }
             else { if (ws == 2) PMX_FWD_SPLIT(false, 2); else PMX_FWD_SPLIT(false, 4); }
@@ -1587,8 +1610,8 @@ int launch_bwd(const void *obs, const void *pack, const void *save, const void *
         // sample: the one-wave kernel holds a sample's 44 + 44 registers of gradient and pre-activation and runs one wave per
         // SIMD; halves of a sample fit two waves per SIMD, and the second wave fills the first one's stalls: backward of 16 384
         // samples 2.29 -> 2.19 ms, of 8 192 1.21 -> 1.14 ms; between 1 024 and 2 048 samples the one-wave kernel is still ahead)
-        const int ws = large_board(NT) ? 4 : (two_wave ? 2 : split_waves(B)), spb = 4 / ws;
-        const size_t lds_s = (size_t)spb * mp * 64 + (size_t)4 * NLAYER * 96 * 4 + (size_t)spb * ws * 8 * 4;
+        const int ws = large_board(NT) ? large_waves(NT) : (two_wave ? 2 : split_waves(B)), spb = split_samples(ws);
+        const size_t lds_s = (size_t)spb * mp * 64 + (size_t)(split_threads(ws) / 64) * NLAYER * 96 * 4 + (size_t)spb * ws * 8 * 4;
         int64_t g64 = (B + spb - 1) / spb;
         if (g64 > 1024) g64 = 1024;                          // accpart has 1 024 rows; the skip slots (2 048) cover grid * spb
         grid_d = (int)g64;
@@ -1600,9 +1623,10 @@ int launch_bwd(const void *obs, const void *pack, const void *save, const void *
                                    (const uint2 *)dfeat, hs, ys, stt, da, sk, accpart, (int)B, H, W);
             }
         } else {
-            rc = allow_lds(pmx_actor_bwd_data_split_kernel<NT, 4>, lds_s);
+            constexpr int WSL = large_board(NT) ? large_waves(NT) : 4;
+            rc = allow_lds(pmx_actor_bwd_data_split_kernel<NT, WSL>, lds_s);
             if (rc) return rc;
-            hipLaunchKernelGGL((pmx_actor_bwd_data_split_kernel<NT, 4>), dim3(grid_d), dim3(256), lds_s, st, (const char *)pack,
+            hipLaunchKernelGGL((pmx_actor_bwd_data_split_kernel<NT, WSL>), dim3(grid_d), dim3(split_threads(WSL)), lds_s, st, (const char *)pack,
                                (const uint2 *)dfeat, hs, ys, stt, da, sk, accpart, (int)B, H, W);
         }
     } else {
@@ -1661,7 +1685,7 @@ extern "C" int pmx_actor_forward(const void *obs_dev, int32_t obs_dtype, const v
     if (!obs_dev || !pack_dev || !feat_dev || B < 0) return PMX_ERR_INVALID;
     if (!pmx_actor_supported(H, W)) return PMX_ERR_UNSUPPORTED;
     hipStream_t st = reinterpret_cast<hipStream_t>(stream);
-    const int nt = tiles_for(H, W);
+    const int nt = bucket_for(tiles_for(H, W));
 #define PMX_FWD(NT)                                                                                                      \
     switch (obs_dtype) {                                                                                                 \
     case PMX_OBS_F32: return launch_fwd<NT, float>(obs_dev, pack_dev, feat_dev, save_dev, scratch_dev, B, H, W, st);                  \
@@ -1670,7 +1694,10 @@ extern "C" int pmx_actor_forward(const void *obs_dev, int32_t obs_dtype, const v
     default: return PMX_ERR_INVALID;                                                                                     \
     }
     if (nt == 10) { PMX_FWD(10) }
+    if (nt == 16) { PMX_FWD(16) }
     if (nt == 28) { PMX_FWD(28) }
+    if (nt == 36) { PMX_FWD(36) }
+    if (nt == 44) { PMX_FWD(44) }
     PMX_FWD(11)
 #undef PMX_FWD
 }
@@ -1684,7 +1711,7 @@ extern "C" int pmx_actor_backward(const void *obs_dev, int32_t obs_dtype, const 
     hipStream_t st = reinterpret_cast<hipStream_t>(stream);
     if (B == 0) return hipMemsetAsync(grad_dev, 0, sizeof(float) * GRAD_FLOATS, st) == hipSuccess ? PMX_OK : PMX_ERR_HIP;
     // (no memset otherwise: the two row-sum kernels write every word of the gradient)
-    const int nt = tiles_for(H, W);
+    const int nt = bucket_for(tiles_for(H, W));
 #define PMX_BWD(NT)                                                                                                                  \
     switch (obs_dtype) {                                                                                                             \
     case PMX_OBS_F32: return launch_bwd<NT, float>(obs_dev, pack_dev, save_dev, dfeat_dev, scratch_dev, grad_dev, B, H, W, st);      \
@@ -1693,7 +1720,10 @@ extern "C" int pmx_actor_backward(const void *obs_dev, int32_t obs_dtype, const 
     default: return PMX_ERR_INVALID;                                                                                                 \
     }
     if (nt == 10) { PMX_BWD(10) }
+    if (nt == 16) { PMX_BWD(16) }
     if (nt == 28) { PMX_BWD(28) }
+    if (nt == 36) { PMX_BWD(36) }
+    if (nt == 44) { PMX_BWD(44) }
     PMX_BWD(11)
 #undef PMX_BWD
 }
@@ -1906,7 +1936,7 @@ __global__ __launch_bounds__(256) void pmx_proj_sum_kernel(const float *__restri
 template <int NT, typename IN_T>
 int launch_proj_fwd(const void *obs, const void *pack, const float *pe, void *tok, int64_t B, int H, int W, hipStream_t st)
 {
-    constexpr int WPB = large_board(NT) ? 2 : 4;
+    constexpr int WPB = NT > 16 ? 2 : 4;                       // waves (= samples, one map each) per block
     const size_t lds = (size_t)WPB * map_positions(NT, W + 2) * 64;
     int rc = allow_lds(pmx_proj_fwd_kernel<NT, IN_T, WPB>, lds);
     if (rc) return rc;
@@ -1948,7 +1978,7 @@ extern "C" int pmx_proj_forward(const void *obs_dev, int32_t obs_dtype, const vo
     if (!obs_dev || !pack_dev || !posenc_dev || !tokens_dev || B < 0) return PMX_ERR_INVALID;
     if (!pmx_actor_supported(H, W)) return PMX_ERR_UNSUPPORTED;
     hipStream_t st = reinterpret_cast<hipStream_t>(stream);
-    const int nt = tiles_for(H, W);
+    const int nt = bucket_for(tiles_for(H, W));
 #define PMX_PF(NT)                                                                                                        \
     switch (obs_dtype) {                                                                                                  \
     case PMX_OBS_F32: return launch_proj_fwd<NT, float>(obs_dev, pack_dev, posenc_dev, tokens_dev, B, H, W, st);              \
@@ -1957,7 +1987,10 @@ extern "C" int pmx_proj_forward(const void *obs_dev, int32_t obs_dtype, const vo
     default: return PMX_ERR_INVALID;                                                                                      \
     }
     if (nt == 10) { PMX_PF(10) }
+    if (nt == 16) { PMX_PF(16) }
     if (nt == 28) { PMX_PF(28) }
+    if (nt == 36) { PMX_PF(36) }
+    if (nt == 44) { PMX_PF(44) }
     PMX_PF(11)
 #undef PMX_PF
 }
@@ -1973,7 +2006,7 @@ extern "C" int pmx_proj_backward(const void *obs_dev, int32_t obs_dtype, const v
         return PMX_OK;
     }
     if (!obs_dev || !dtokens_dev || !partial_dev) return PMX_ERR_INVALID;
-    const int nt = tiles_for(H, W);
+    const int nt = bucket_for(tiles_for(H, W));
 #define PMX_PB(NT)                                                                                                                  \
     switch (obs_dtype) {                                                                                                            \
     case PMX_OBS_F32: return launch_proj_bwd<NT, float>(obs_dev, dtokens_dev, partial_dev, dw_dev, db_dev, B, H, W, st);                \
@@ -1982,7 +2015,10 @@ extern "C" int pmx_proj_backward(const void *obs_dev, int32_t obs_dtype, const v
     default: return PMX_ERR_INVALID;                                                                                                \
     }
     if (nt == 10) { PMX_PB(10) }
+    if (nt == 16) { PMX_PB(16) }
     if (nt == 28) { PMX_PB(28) }
+    if (nt == 36) { PMX_PB(36) }
+    if (nt == 44) { PMX_PB(44) }
     PMX_PB(11)
 #undef PMX_PB
 }
