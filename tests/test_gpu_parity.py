@@ -367,7 +367,7 @@ def _gae(mode, rew, val, done, last, gamma, lam):
     pmx = _pmx()
     lib = pmx._lib.load()
     T, n = rew.shape
-    adv = torch.empty_like(rew); ret = torch.empty_like(rew)
+    adv = torch.full_like(rew, float("nan")); ret = torch.full_like(rew, float("nan"))    # an element left unwritten compares unequal
     st = C.c_void_p(torch.cuda.current_stream().cuda_stream)
     if mode is None:
         rc = lib.pmx_gae(rew.data_ptr(), val.data_ptr(), done.data_ptr(), last.data_ptr(), T, n, gamma, lam, adv.data_ptr(), ret.data_ptr(), st)
@@ -403,6 +403,69 @@ def test_gae_batched_vs_oracle():
     for i in range(0, n, 97):
         a, r = O.gae(rew[:, i], val[:, i], done[:, i], float(last[i]), 0.99, 0.95)
         assert a.tobytes() == adv[:, i].tobytes() and r.tobytes() == ret[:, i].tobytes()
+
+
+def _gae_done_pattern(kind, T):
+    """done flags [T] that stress the wave kernel's 64-step chunks: it scans t = hi .. hi - 63 for hi = T - 1, T - 65, ..., so
+    chunk k starts at t = T - 1 - 64 k, and a 1 there or on either neighbour cuts the recurrence right at, before or behind
+    the carry handed from one chunk to the next"""
+    d = np.zeros(T, np.float32)
+    if kind == "last":
+        d[T - 1] = 1
+    elif kind == "everywhere":
+        d[:] = 1
+    elif kind != "nowhere":
+        off = {"edge-1": -1, "edge": 0, "edge+1": 1}[kind]
+        for k in range(T // 64 + 2):
+            t = T - 1 - 64 * k + off
+            if 0 <= t < T:
+                d[t] = 1
+    return d
+
+
+_GAE_PATTERNS = ("last", "edge-1", "edge", "edge+1", "everywhere", "nowhere")
+
+
+def _gae_check(adv, ret, rew, val, done, last, exact, tag, series=None):
+    """adv, ret [T, n] of the device against O.gae per series: byte for byte, or within the wave kernel's stated tolerance"""
+    adv, ret = adv.cpu().numpy(), ret.cpu().numpy()
+    for i in (range(rew.shape[1]) if series is None else series):
+        a, r = O.gae(rew[:, i], val[:, i], done[:, i], float(last[i]), 0.99, 0.95)
+        if exact:
+            assert a.tobytes() == adv[:, i].tobytes() and r.tobytes() == ret[:, i].tobytes(), (tag, i)
+        else:
+            tol = 1e-5 * (float(np.abs(a).max()) + 1.0)
+            ea, er = np.abs(adv[:, i] - a).max(), np.abs(ret[:, i] - r).max()     # NaN (unwritten) fails the comparison below
+            assert ea <= tol and er <= tol, (tag, i, float(ea), float(er), tol)
+
+
+@pytest.mark.parametrize("T", [1, 63, 64, 65, 128, 129, 200])
+@pytest.mark.parametrize("n", [2, 3, 5])
+def test_gae_wave_kernel_several_series(n, T):
+    """pmx_gae_wave_kernel with more than one series: element (t, i) is at t * n + i and the next value at + n, which one
+    series cannot get wrong visibly.  Every series has its own rewards, values and last value; in launch p series i has done
+    pattern (p + i) mod 6, so neighbouring series always differ and every series meets every pattern."""
+    rng = np.random.RandomState(1000 * n + T)
+    rew = rng.randn(T, n).astype(np.float32); val = rng.randn(T, n).astype(np.float32)
+    last = rng.randn(n).astype(np.float32)
+    for p in range(len(_GAE_PATTERNS)):
+        kinds = [_GAE_PATTERNS[(p + i) % len(_GAE_PATTERNS)] for i in range(n)]
+        done = np.stack([_gae_done_pattern(k, T) for k in kinds], 1)
+        adv, ret = _gae(1, torch.tensor(rew).cuda(), torch.tensor(val).cuda(), torch.tensor(done).cuda(), torch.tensor(last).cuda(), 0.99, 0.95)
+        _gae_check(adv, ret, rew, val, done, last, False, kinds)
+
+
+@pytest.mark.parametrize("T,n,wave", [(127, 3, False), (128, 3, True), (128, 2047, True), (128, 2048, False)])
+def test_gae_default_dispatch_both_sides(T, n, wave):
+    """pmx_gae itself on both sides of both thresholds of its rule (the wave kernel when n < 2048 and T >= 128): where the rule
+    picks the lane kernel the result is the oracle's byte for byte, which the re-associating wave kernel does not give"""
+    rng = np.random.RandomState(T * 10000 + n)
+    rew = rng.randn(T, n).astype(np.float32); val = rng.randn(T, n).astype(np.float32)
+    done = (rng.rand(T, n) < 0.05).astype(np.float32); last = rng.randn(n).astype(np.float32)
+    done[T - 1, ::2] = 1
+    done[T - 65:T - 62, 1::3] = 1
+    adv, ret = _gae(None, torch.tensor(rew).cuda(), torch.tensor(val).cuda(), torch.tensor(done).cuda(), torch.tensor(last).cuda(), 0.99, 0.95)
+    _gae_check(adv, ret, rew, val, done, last, not wave, (T, n))
 
 
 def test_canonicalize_merge_golden():
