@@ -462,6 +462,28 @@ int pmx_critic_tail_forward(const void *tokens_dev, const float *w1, const float
 int pmx_critic_tail_backward(const float *pooled_dev, const float *dvalue_dev, const float *w1, const float *b1, const float *w2,
                              void *dtokens_dev, void *scratch_dev, float *grad_dev, int64_t B, int32_t S, void *stream);
 
+/* ---- The first layer of the actor head on the matrix cores (csrc/pmx_actor_head.hip) ---------------------------------------
+ * MAPPOAgent.actor_head[0], Linear(32 H W -> 512) (pacman_mappo_resnet.py:117-119), between pmx_actor_forward and pmx_actor_tail_forward,
+ * on the boards pmx_actor_supported() accepts (PMX_ERR_UNSUPPORTED elsewhere; a null pointer or B < 0: PMX_ERR_INVALID; B == 0: PMX_OK,
+ * nothing is launched or written):
+ *   w         [512][32 H W] float32, the parameter as nn.Linear stores it (column ch * HW + cell); bias, db_dev [512] float32
+ *   feat_dev, dfeat_dev [B][H W][32] bfloat16 (what pmx_actor_forward writes and pmx_actor_backward reads; contraction index cell * 32 + ch)
+ *   h_dev, dh_dev       [B][512] bfloat16 (what pmx_actor_tail_forward / _backward take and return with h_bf16 = 1)
+ *   dw_dev    [512][32 H W] float32 in the parameter's own order, written in full
+ * pmx_actor_head_sizes (host only) gives the bytes of the packed operand images pmx_actor_head_pack writes (the weight rounded to
+ * bfloat16 once, cell-major, and its transpose) and of the scratch either direction needs for B samples (both 16-byte aligned).
+ * Products are v_mfma_f32_16x16x32_bf16 with float32 accumulation; the bias is added in float32 before the single rounding of h; dw and
+ * db stay float32.  Partial sums (split K forward, split batch in the weight gradient) go to slabs in the scratch and are added in a
+ * fixed order: no atomics, the same call on the same inputs returns the same bits.  B above PMX_ACTOR_HEAD_MAX_BATCH (row indices and
+ * grid sizes stay inside 32 bits): PMX_ERR_UNSUPPORTED. */
+#define PMX_ACTOR_HEAD_MAX_BATCH 4194304
+int pmx_actor_head_sizes(int32_t H, int32_t W, int64_t B, int64_t *pack_bytes, int64_t *scratch_bytes);   /* pacman_mappo_resnet.py:117-119 */
+int pmx_actor_head_pack(const float *w, void *pack_dev, int32_t H, int32_t W, void *stream);              /* pacman_mappo_resnet.py:117-119 */
+int pmx_actor_head_forward(const void *feat_dev, const void *pack_dev, const float *bias, void *h_dev, void *scratch_dev, int64_t B,
+                           int32_t H, int32_t W, void *stream);                                           /* pacman_mappo_resnet.py:117-119 */
+int pmx_actor_head_backward(const void *feat_dev, const void *dh_dev, const void *pack_dev, void *dfeat_dev, float *dw_dev, float *db_dev,
+                            void *scratch_dev, int64_t B, int32_t H, int32_t W, void *stream);            /* pacman_mappo_resnet.py:117-119 */
+
 /* All parameter packs of up to four encoder layers in one launch (what pmx_tok96_pack, pmx_tok32ln_pack and pmx_ffn_pack produce, into
  * the three pack buffers of each layer). */
 typedef struct {

@@ -129,6 +129,10 @@ PROTOTYPES = [
     ("pmx_actor_tail_backward", C.c_int, [_VP, _I32, _VP, _VP, _VP, _VP, _VP, _VP, _VP, C.c_int64, _VP]),
     ("pmx_critic_tail_forward", C.c_int, [_VP, _VP, _VP, _VP, _VP, _VP, _VP, C.c_int64, _I32, _VP]),
     ("pmx_critic_tail_backward", C.c_int, [_VP, _VP, _VP, _VP, _VP, _VP, _VP, _VP, C.c_int64, _I32, _VP]),
+    ("pmx_actor_head_sizes", C.c_int, [_I32, _I32, C.c_int64, C.POINTER(C.c_int64), C.POINTER(C.c_int64)]),
+    ("pmx_actor_head_pack", C.c_int, [_VP, _VP, _I32, _I32, _VP]),
+    ("pmx_actor_head_forward", C.c_int, [_VP, _VP, _VP, _VP, _VP, C.c_int64, _I32, _I32, _VP]),
+    ("pmx_actor_head_backward", C.c_int, [_VP, _VP, _VP, _VP, _VP, _VP, _VP, C.c_int64, _I32, _I32, _VP]),
     ("pmx_encoder_pack", C.c_int, [_I32, C.POINTER(EncoderLayerParams), _VP]),
     ("pmx_proj_pack", C.c_int, [_VP, _VP, _VP, _VP]),
     ("pmx_proj_forward", C.c_int, [_VP, _I32, _VP, _VP, _VP, C.c_int64, _I32, _I32, _VP]),

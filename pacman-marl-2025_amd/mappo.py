@@ -440,6 +440,66 @@ class _Projector(torch.autograd.Function):
         return None, dw.to(ctx.dtypes[0]), db.to(ctx.dtypes[1]), None
 
 
+def actor_head_sizes(H, W, B):
+    """-> (pack bytes, scratch bytes) of the first actor-head layer's kernels for B samples (pmx_actor_head_sizes)"""
+    pk, sc = C.c_int64(), C.c_int64()
+    _lib.check(_lib.load().pmx_actor_head_sizes(int(H), int(W), int(B), C.byref(pk), C.byref(sc)), "pmx_actor_head_sizes")
+    return pk.value, sc.value
+
+
+def pack_actor_head(w, H, W):
+    """The bfloat16 operand images of actor_head[0].weight (float32 [512, 32 H W], nn.Linear's own order): one kernel, one rounding."""
+    lib = _lib.load()
+    wf = w.detach().contiguous()
+    pack = torch.empty(actor_head_sizes(H, W, 0)[0], dtype=torch.uint8, device=wf.device)
+    st = C.c_void_p(torch.cuda.current_stream(wf.device).cuda_stream)
+    _lib.check(lib.pmx_actor_head_pack(wf.data_ptr(), pack.data_ptr(), int(H), int(W), st), "pmx_actor_head_pack")
+    return pack
+
+
+class _ActorHead(torch.autograd.Function):
+    """h [B, 512] bf16 = Linear(32 H W -> 512)(features) on the tower's channels-last features [B, H*W, 32] bf16, through
+    pmx_actor_head_forward / _backward (csrc/pmx_actor_head.hip): the weight is read in nn.Linear's (channel, cell) order and packed
+    cell-major by one kernel (no permuted copy of it or of its gradient), the weight and bias gradients come back float32 in the
+    parameters' own order.  `pack`: the packed weight of a caller that knows it is frozen (inference), else None."""
+
+    @staticmethod
+    def forward(ctx, feat, w, b, H, W, pack):
+        lib = _lib.load()
+        feat = feat.contiguous()
+        B, dev = feat.shape[0], feat.device
+        if pack is None:
+            pack = pack_actor_head(w, H, W)
+        bf = b.detach().contiguous()
+        h = torch.empty(B, 512, dtype=torch.bfloat16, device=dev)
+        # scratch belongs to THIS call (see actor_tower._ActorTower.backward)
+        scratch = torch.empty(actor_head_sizes(H, W, B)[1], dtype=torch.uint8, device=dev)
+        st = C.c_void_p(torch.cuda.current_stream(dev).cuda_stream)
+        _lib.check(lib.pmx_actor_head_forward(feat.data_ptr(), pack.data_ptr(), bf.data_ptr(), h.data_ptr(), scratch.data_ptr(), B, H, W, st),
+                   "pmx_actor_head_forward")
+        ctx.save_for_backward(feat, pack)
+        ctx.board = (H, W)
+        ctx.dtypes = (w.dtype, b.dtype)
+        return h
+
+    @staticmethod
+    def backward(ctx, dh):
+        lib = _lib.load()
+        feat, pack = ctx.saved_tensors
+        H, W = ctx.board
+        B, dev = feat.shape[0], feat.device
+        dh = dh.to(torch.bfloat16).contiguous()
+        dfeat = torch.empty_like(feat)
+        alloc = torch.zeros if B == 0 else torch.empty                    # (an empty batch launches nothing)
+        dw = alloc(512, 32 * H * W, dtype=torch.float32, device=dev)
+        db = alloc(512, dtype=torch.float32, device=dev)
+        scratch = torch.empty(actor_head_sizes(H, W, B)[1], dtype=torch.uint8, device=dev)
+        st = C.c_void_p(torch.cuda.current_stream(dev).cuda_stream)
+        _lib.check(lib.pmx_actor_head_backward(feat.data_ptr(), dh.data_ptr(), pack.data_ptr(), dfeat.data_ptr(), dw.data_ptr(), db.data_ptr(),
+                                               scratch.data_ptr(), B, H, W, st), "pmx_actor_head_backward")
+        return dfeat, dw.to(ctx.dtypes[0]), db.to(ctx.dtypes[1]), None, None, None
+
+
 class _ActorTail(torch.autograd.Function):
     """logits = Linear_5(gelu(LayerNorm_512(h))) through pmx_actor_tail_forward / _backward (csrc/pmx_heads.hip): one launch each
     way (+ a row sum) instead of LayerNorm, GELU, a skinny GEMM, their backward kernels, two bias reductions and the casts."""
@@ -759,6 +819,32 @@ class MAPPOAgent(nn.Module):
                 and tuple(ah[3].weight.shape) == (5, 512) and tuple(ch[0].weight.shape) == (512, 32) and tuple(ch[2].weight.shape) == (1, 512)
                 and ah[1].weight.dtype == torch.float32)
 
+    fused_head = True       # the first actor-head layer on the project's own matrix-core kernels under bf16 autocast (csrc/pmx_actor_head.hip)
+    fused_head_max_batch = 0     # ... up to this many samples per call; above it the permuted F.linear below stays, untouched.  0: the
+                                 # model keeps the library everywhere -- alone the kernels are ahead of it up to 2 048 samples, but the
+                                 # replayed 512-sample optimizer step measured 4 % slower with them; a caller
+                                 # that runs the layer by itself (evaluation on a frozen pack, eager steps) may raise it
+    head_pack = None        # its packed weight for inference, set beside tower_pack by a caller that knows the weights are frozen
+
+    def head_kernels_for(self, batch):
+        """Whether logits() runs the first head layer on pmx_actor_head_* for a training call of `batch` samples under bf16 autocast (what
+        PPOLearner asks before it decides whether the layer reads its bfloat16 shadow)."""
+        _, H, W = self.obs_shape
+        lin = self.actor_head[0]
+        return bool(self.fused_head and self.fused_tower and batch is not None and 0 < batch <= self.fused_head_max_batch
+                    and lin.in_features == 32 * H * W and lin.out_features == 512 and lin.bias is not None
+                    and actor_tower.tower_supported(H, W))
+
+    def _fused_head_ok(self, lin, HW, batch):
+        """The kernels take the fused tower's features under bf16 autocast and the float32 master weight of the reference's shape, up to
+        fused_head_max_batch samples.  A call without gradients takes them only on a frozen pack: packing the 5 - 13 MB weight for one
+        inference call costs more than the product saves."""
+        return (self.fused_head and batch <= self.fused_head_max_batch and torch.is_autocast_enabled()
+                and torch.get_autocast_dtype("cuda") == torch.bfloat16
+                and (torch.is_grad_enabled() or self.head_pack is not None)
+                and lin.weight.dtype == torch.float32 and lin.bias is not None and lin.bias.dtype == torch.float32
+                and lin.in_features == 32 * HW and lin.out_features == 512)
+
     def _use_fused_tower(self, obs):
         if not (self.fused_tower and obs.is_cuda and obs.dim() == 4 and obs.dtype in (torch.bfloat16, torch.uint8)):
             return False
@@ -779,6 +865,13 @@ class MAPPOAgent(nn.Module):
             # gradient back through the view
             lin = self.actor_head[0]
             HW = feat.shape[1]
+            if self._fused_head_ok(lin, HW, feat.shape[0]):
+                pack = self.head_pack if not torch.is_grad_enabled() else None
+                h = _ActorHead.apply(feat, lin.weight, lin.bias, obs.shape[2], obs.shape[3], pack)
+                if self._fused_heads_ok(h):
+                    ln, out = self.actor_head[1], self.actor_head[3]
+                    return _ActorTail.apply(h, ln.weight, ln.bias, out.weight, out.bias, ln.eps)
+                return self.actor_head[1:](h)
             w = lin.weight.view(lin.out_features, 32, HW).permute(0, 2, 1).reshape(lin.out_features, HW * 32)
             h = F.linear(feat.reshape(feat.shape[0], HW * 32), w, lin.bias)
             if self._fused_heads_ok(h) and h.shape[1] == 512:
@@ -1170,25 +1263,30 @@ class PPOLearner:
     # (the head-tail kernels and the projector kernel read their layers' float32 masters and round the operands themselves)
     SMALL_HEAD_LAYERS = ("actor_head.3.", "critic_head.0.", "critic_head.2.")
 
-    def _shadowed_prefixes(self):
+    def _shadowed_prefixes(self, batch=None):
+        """batch: the actor samples of the step about to run, None when the caller does not say (the first head layer then keeps its
+        shadow and the library path, as before the kernels existed)."""
         keep = self.SHADOWED
         if getattr(self.model, "fused_heads", False):
             keep = tuple(k for k in keep if k not in self.SMALL_HEAD_LAYERS)
         if getattr(self.model, "fused_projector", False):
             keep = tuple(k for k in keep if k != "critic_projector.0.")
+        kernels = getattr(self.model, "head_kernels_for", None)
+        if kernels is not None and kernels(batch):           # pmx_actor_head_pack reads the float32 master, the gradients come back float32
+            keep = tuple(k for k in keep if k != "actor_head.0.")
         return keep
     shadow_weights = True
 
-    def _shadow_context(self):
+    def _shadow_context(self, batch=None):
         """Context manager under which the module's library-op parameters are their bfloat16 shadows (and a no-op when the
-        shadows do not apply: CPU, float32 steps)."""
+        shadows do not apply: CPU, float32 steps).  batch: see _shadowed_prefixes."""
         if not (self.shadow_weights and self.autocast_dtype == torch.bfloat16 and self.bucket.data.is_cuda):
             self._shadow_views = None
             return contextlib.nullcontext()
         if self._sh16 is None:
             self._sh16 = self.bucket.data.to(torch.bfloat16).requires_grad_(True)
-            keep = self._shadowed_prefixes()
-            self._shadow_slots = [(i, n) for i, n in enumerate(self.bucket.names) if n.startswith(keep)]
+        keep = self._shadowed_prefixes(batch)
+        self._shadow_slots = [(i, n) for i, n in enumerate(self.bucket.names) if n.startswith(keep)]
         self._shadow_views, pd = {}, {}
         for i, n in self._shadow_slots:
             v = self._sh16[self._offsets[i]:self._offsets[i + 1]].view(self.bucket.params[i].shape)
@@ -1201,7 +1299,7 @@ class PPOLearner:
         if self.autocast_dtype is None:
             self._shadow_views = None
             return ppo_loss(self.model, obs, merged, act, old_logp, adv, ret, clip_eps, ent_coef)
-        with self._shadow_context(), torch.autocast(device_type=self.bucket.data.device.type, dtype=self.autocast_dtype):
+        with self._shadow_context(obs.shape[0]), torch.autocast(device_type=self.bucket.data.device.type, dtype=self.autocast_dtype):
             return ppo_loss(self.model, obs, merged, act, old_logp, adv, ret, clip_eps, ent_coef)
 
     def set_lr(self, lr):

@@ -178,13 +178,18 @@ class VecMAPPOTrainer:
         return x.float()
 
     def _freeze_tower_packs(self, on):
-        """The rollout runs thousands of inference calls on frozen weights: pack the actor towers' parameters once."""
+        """The rollout runs thousands of inference calls on frozen weights: pack the actor towers' parameters once, and the
+        first head layer's weight with them (one pack per rollout, not one per tick)."""
         from . import actor_tower
         H, W = self.obs_shape[1], self.obs_shape[2]
         for m in (self.model, self.opponent_model):
-            m.tower_pack = None
+            m.tower_pack = m.head_pack = None
             if on and self.autocast_dtype is not None and m.fused_tower and actor_tower.tower_supported(H, W):
                 m.tower_pack = actor_tower.pack_params(actor_tower._tower_params(m.actor_backbone))
+                lin = m.actor_head[0]
+                if (m.fused_head and m.fused_head_max_batch > 0 and self.autocast_dtype == torch.bfloat16 and lin.weight.is_cuda and lin.weight.dtype == torch.float32
+                        and lin.in_features == 32 * H * W and lin.out_features == 512):
+                    m.head_pack = mappo.pack_actor_head(lin.weight, H, W)
 
     def _forward_policy(self, model, obs2, merged, want_value):
         ctx = torch.autocast(device_type=self.device.type, dtype=self.autocast_dtype) if self.autocast_dtype else _NullCtx()
