@@ -30,14 +30,9 @@
 #include <stdint.h>
 
 #include "../../include/pmx.h"
+#include "pmx_common.h"
 
 namespace {
-
-typedef __attribute__((ext_vector_type(8))) short bf16x8;
-typedef __attribute__((ext_vector_type(4))) short bf16x4;
-typedef __attribute__((ext_vector_type(4))) float f32x4;
-typedef __attribute__((ext_vector_type(2))) float f32x2;
-typedef __attribute__((ext_vector_type(2))) __bf16 bf16x2_t;
 
 constexpr int NLAYER = 8;
 constexpr int GUARD = 1;                       // map positions in front of padded index 0 (a tap reads q - WP - 1 >= -1)
@@ -67,14 +62,6 @@ __host__ __device__ constexpr int map_positions(int nt, int wp) { return GUARD +
 // LDS -- 8-16 % busy with the swizzle.  Plain addresses are 2-way conflicted on that read and leave the address one add.)
 __device__ __forceinline__ int map_off(int pos, int chunk) { return pos * 64 + (chunk << 4); }
 
-__device__ __forceinline__ uint32_t pack2(float a, float b)
-{
-    f32x2 f = {a, b};
-    return __builtin_bit_cast(uint32_t, __builtin_convertvector(f, bf16x2_t));
-}
-__device__ __forceinline__ float lo_f(uint32_t u) { return __uint_as_float(u << 16); }
-__device__ __forceinline__ float hi_f(uint32_t u) { return __uint_as_float(u & 0xFFFF0000u); }
-
 // Phi(z) = 0.5 (1 + erf(z / sqrt 2)) by Abramowitz-Stegun 7.1.26 (|error of erf| <= 1.5e-7) and e = exp(-z^2 / 2), for a PAIR of
 // values.  GELU(z) = z Phi(z) (nn.GELU() exact form, pacman_mappo_resnet.py:53), GELU'(z) = Phi(z) + z e / sqrt(2 pi).
 // Written so that every step but the reciprocal, the exponential, |z| and the final select is one packed instruction for the pair
@@ -83,7 +70,7 @@ __device__ __forceinline__ float hi_f(uint32_t u) { return __uint_as_float(u & 0
 // exact power of two).
 __device__ __forceinline__ f32x2 fma2(f32x2 a, f32x2 b, f32x2 c) { return __builtin_elementwise_fma(a, b, c); }
 __device__ __forceinline__ f32x2 splat2(float v) { return f32x2{v, v}; }
-__device__ __forceinline__ f32x2 unpack2(uint32_t u) { return f32x2{lo_f(u), hi_f(u)}; }
+__device__ __forceinline__ f32x2 unpack2(uint32_t u) { return f32x2{bf_lo(u), bf_hi(u)}; }
 __device__ __forceinline__ f32x2 phi_cdf2(f32x2 z, f32x2 &e)
 {
     const f32x2 den = {fmaf(0.3275911f * 0.70710678118654752f, fabsf(z.x), 1.0f), fmaf(0.3275911f * 0.70710678118654752f, fabsf(z.y), 1.0f)};
@@ -109,7 +96,7 @@ __device__ __forceinline__ uint2 gelu_quad(uint2 h2, uint2 r2, float mean, float
         f32x2 e;
         v[k] = z * phi_cdf2(z, e) * splat2(vm);
     }
-    return uint2{pack2(v[0].x, v[0].y), pack2(v[1].x, v[1].y)};
+    return uint2{bf_pack(v[0].x, v[0].y), bf_pack(v[1].x, v[1].y)};
 }
 // Pass 1 of the data gradient for the four channels a lane holds of one position: z from the saved convolution output h (GroupNorm,
 // affine, + the skip input x), dz = dY GELU'(z) rounded to bf16 as autograd would round it; the bf16-rounded dz joins the lane's
@@ -128,7 +115,7 @@ __device__ __forceinline__ uint2 dgelu_quad(uint2 dy, uint2 h2, uint2 x2, float 
         const f32x2 phi = phi_cdf2(z, e);
         dzf[k] = d * fma2(z * splat2(0.3989422804014327f), e, phi);
     }
-    uint2 dzq = {pack2(dzf[0].x, dzf[0].y), pack2(dzf[1].x, dzf[1].y)};
+    uint2 dzq = {bf_pack(dzf[0].x, dzf[0].y), bf_pack(dzf[1].x, dzf[1].y)};
     asm volatile("" : "+v"(dzq.x), "+v"(dzq.y));
 #pragma unroll
     for (int k = 0; k < 2; ++k) {
@@ -192,7 +179,7 @@ __device__ __forceinline__ void load_obs(const IN_T *__restrict__ obs, char *map
         float v[8];
 #pragma unroll
         for (int c = 0; c < 8; ++c) v[c] = in_to_f<IN_T>(obs[c * G.HW + i]);
-        uint4 w = {pack2(v[0], v[1]), pack2(v[2], v[3]), pack2(v[4], v[5]), pack2(v[6], v[7])};
+        uint4 w = {bf_pack(v[0], v[1]), bf_pack(v[2], v[3]), bf_pack(v[4], v[5]), bf_pack(v[6], v[7])};
         *reinterpret_cast<uint4 *>(map + map_off(pos, 0)) = w;
         const uint4 z = {0, 0, 0, 0};
 #pragma unroll
@@ -321,11 +308,11 @@ __global__ __launch_bounds__(256, 2) void pmx_actor_fwd_kernel(const IN_T *__res
                     float v[4];
 #pragma unroll
                     for (int r = 0; r < 4; ++r) v[r] = (a[m][r] + bias[m][r]) * vm;
-                    uint2 h2 = {pack2(v[0], v[1]), pack2(v[2], v[3])};
+                    uint2 h2 = {bf_pack(v[0], v[1]), bf_pack(v[2], v[3])};
                     asm volatile("" : "+v"(h2.x), "+v"(h2.y));   // pins the pack next to its tile (else it sinks to pass 2 and
                                                                  // all NT x 8 fp32 accumulators stay live through the layer)
                     hp[t][m] = h2;
-                    const float h0 = lo_f(h2.x), h1 = hi_f(h2.x), h2f = lo_f(h2.y), h3 = hi_f(h2.y);
+                    const float h0 = bf_lo(h2.x), h1 = bf_hi(h2.x), h2f = bf_lo(h2.y), h3 = bf_hi(h2.y);
                     s1[m] += (h0 + h1) + (h2f + h3);
                     s2[m] += fmaf(h0, h0, h1 * h1) + fmaf(h2f, h2f, h3 * h3);
                     if (SAVE) hsave[dump_index((size_t)l * B + s, NT, t, m, lane)] = h2;
@@ -413,7 +400,7 @@ __device__ __forceinline__ void load_obs_block(const IN_T *__restrict__ obs, cha
         float v[8];
 #pragma unroll
         for (int c = 0; c < 8; ++c) v[c] = in_to_f<IN_T>(obs[c * G.HW + i]);
-        uint4 w = {pack2(v[0], v[1]), pack2(v[2], v[3]), pack2(v[4], v[5]), pack2(v[6], v[7])};
+        uint4 w = {bf_pack(v[0], v[1]), bf_pack(v[2], v[3]), bf_pack(v[4], v[5]), bf_pack(v[6], v[7])};
         *reinterpret_cast<uint4 *>(map + map_off(pos, 0)) = w;
         const uint4 z = {0, 0, 0, 0};
 #pragma unroll
@@ -503,10 +490,10 @@ __global__ __launch_bounds__(split_threads(WS), 2) void pmx_actor_fwd_split_kern
                         float v[4];
 #pragma unroll
                         for (int r = 0; r < 4; ++r) v[r] = (a[m][r] + bias[m][r]) * vm;
-                        uint2 h2 = {pack2(v[0], v[1]), pack2(v[2], v[3])};
+                        uint2 h2 = {bf_pack(v[0], v[1]), bf_pack(v[2], v[3])};
                         asm volatile("" : "+v"(h2.x), "+v"(h2.y));
                         hp[tl][m] = h2;
-                        const float h0 = lo_f(h2.x), h1 = hi_f(h2.x), h2f = lo_f(h2.y), h3 = hi_f(h2.y);
+                        const float h0 = bf_lo(h2.x), h1 = bf_hi(h2.x), h2f = bf_lo(h2.y), h3 = bf_hi(h2.y);
                         s1[m] += (h0 + h1) + (h2f + h3);
                         s2[m] += fmaf(h0, h0, h1 * h1) + fmaf(h2f, h2f, h3 * h3);
                         if (SAVE) hsave[dump_index((size_t)l * B + s, NT, t, m, lane)] = h2;
@@ -750,14 +737,14 @@ __global__ __launch_bounds__(256, 1) void pmx_actor_bwd_data_kernel(const char *
 #pragma unroll
                 for (int m = 0; m < 2; ++m) {
                     const uint2 h2 = hp[t][m];
-                    const float hv[4] = {lo_f(h2.x), hi_f(h2.x), lo_f(h2.y), hi_f(h2.y)};
-                    const float dzr[4] = {lo_f(dv[t][m].x), hi_f(dv[t][m].x), lo_f(dv[t][m].y), hi_f(dv[t][m].y)};
+                    const float hv[4] = {bf_lo(h2.x), bf_hi(h2.x), bf_lo(h2.y), bf_hi(h2.y)};
+                    const float dzr[4] = {bf_lo(dv[t][m].x), bf_hi(dv[t][m].x), bf_lo(dv[t][m].y), bf_hi(dv[t][m].y)};
                     float dh[4];
 #pragma unroll
                     for (int r = 0; r < 4; ++r) dh[r] = vm * fmaf(Ad[m][r], dzr[r], fmaf(hv[r], K2[m], K3[m]));
-                    const uint2 d2 = {pack2(dh[0], dh[1]), pack2(dh[2], dh[3])};
+                    const uint2 d2 = {bf_pack(dh[0], dh[1]), bf_pack(dh[2], dh[3])};
                     // the bias gradient sums what the matrix cores see (the bf16-rounded dh), like autograd on a bf16 tensor
-                    dbias[m][0] += lo_f(d2.x), dbias[m][1] += hi_f(d2.x), dbias[m][2] += lo_f(d2.y), dbias[m][3] += hi_f(d2.y);
+                    dbias[m][0] += bf_lo(d2.x), dbias[m][1] += bf_hi(d2.x), dbias[m][2] += bf_lo(d2.y), dbias[m][3] += bf_hi(d2.y);
                     *reinterpret_cast<uint2 *>(wbase + (WPv + 16 * t) * 64 + m * 32) = d2;
                 }
                 __builtin_amdgcn_sched_barrier(0);
@@ -822,9 +809,9 @@ __global__ __launch_bounds__(256, 1) void pmx_actor_bwd_data_kernel(const char *
 #pragma unroll
                     for (int m = 0; m < 2; ++m) {
                         const uint32_t sx = skip[t][m].x, sy = skip[t][m].y;
-                        const float v0 = (lo_f(sx) + a[m][0]) * vm, v1 = (hi_f(sx) + a[m][1]) * vm;
-                        const float v2 = (lo_f(sy) + a[m][2]) * vm, v3 = (hi_f(sy) + a[m][3]) * vm;
-                        uint2 nx = {pack2(v0, v1), pack2(v2, v3)};
+                        const float v0 = (bf_lo(sx) + a[m][0]) * vm, v1 = (bf_hi(sx) + a[m][1]) * vm;
+                        const float v2 = (bf_lo(sy) + a[m][2]) * vm, v3 = (bf_hi(sy) + a[m][3]) * vm;
+                        uint2 nx = {bf_pack(v0, v1), bf_pack(v2, v3)};
                         asm volatile("" : "+v"(nx.x), "+v"(nx.y));
                         dv[t][m] = nx;
                     }
@@ -1043,13 +1030,13 @@ __global__ __launch_bounds__(split_threads(WS), 2) void pmx_actor_bwd_data_split
 #pragma unroll
                     for (int m = 0; m < 2; ++m) {
                         const uint2 h2 = hp[tl][m];
-                        const float hv[4] = {lo_f(h2.x), hi_f(h2.x), lo_f(h2.y), hi_f(h2.y)};
-                        const float dzr[4] = {lo_f(dv[tl][m].x), hi_f(dv[tl][m].x), lo_f(dv[tl][m].y), hi_f(dv[tl][m].y)};
+                        const float hv[4] = {bf_lo(h2.x), bf_hi(h2.x), bf_lo(h2.y), bf_hi(h2.y)};
+                        const float dzr[4] = {bf_lo(dv[tl][m].x), bf_hi(dv[tl][m].x), bf_lo(dv[tl][m].y), bf_hi(dv[tl][m].y)};
                         float dh[4];
 #pragma unroll
                         for (int r = 0; r < 4; ++r) dh[r] = vm * fmaf(Ad[m][r], dzr[r], fmaf(hv[r], K2[m], K3[m]));
-                        const uint2 d2 = {pack2(dh[0], dh[1]), pack2(dh[2], dh[3])};
-                        dbias[m][0] += lo_f(d2.x), dbias[m][1] += hi_f(d2.x), dbias[m][2] += lo_f(d2.y), dbias[m][3] += hi_f(d2.y);
+                        const uint2 d2 = {bf_pack(dh[0], dh[1]), bf_pack(dh[2], dh[3])};
+                        dbias[m][0] += bf_lo(d2.x), dbias[m][1] += bf_hi(d2.x), dbias[m][2] += bf_lo(d2.y), dbias[m][3] += bf_hi(d2.y);
                         *reinterpret_cast<uint2 *>(wbase + (WPv + 16 * t) * 64 + m * 32) = d2;
                     }
                 }
@@ -1105,9 +1092,9 @@ __global__ __launch_bounds__(split_threads(WS), 2) void pmx_actor_bwd_data_split
 #pragma unroll
                         for (int m = 0; m < 2; ++m) {
                             const uint32_t sx = skip[tl][m].x, sy = skip[tl][m].y;
-                            const float v0 = (lo_f(sx) + a[m][0]) * vm, v1 = (hi_f(sx) + a[m][1]) * vm;
-                            const float v2 = (lo_f(sy) + a[m][2]) * vm, v3 = (hi_f(sy) + a[m][3]) * vm;
-                            uint2 nx = {pack2(v0, v1), pack2(v2, v3)};
+                            const float v0 = (bf_lo(sx) + a[m][0]) * vm, v1 = (bf_hi(sx) + a[m][1]) * vm;
+                            const float v2 = (bf_lo(sy) + a[m][2]) * vm, v3 = (bf_hi(sy) + a[m][3]) * vm;
+                            uint2 nx = {bf_pack(v0, v1), bf_pack(v2, v3)};
                             asm volatile("" : "+v"(nx.x), "+v"(nx.y));
                             dv[tl][m] = nx;
                         }
@@ -1387,8 +1374,8 @@ __global__ __launch_bounds__(256) void pmx_actor_pack_kernel(PackArgs a, char *_
         if (row < cout && kk < cin) vf = a.w[l][((size_t)row * cin + kk) * 9 + k];
         // input gradient: row = input channel, kk = output channel, tap flipped
         if (row < cin && kk < cout) vb = a.w[l][((size_t)kk * cin + row) * 9 + (8 - k)];
-        fw[i] = (short)(pack2(vf, 0.f) & 0xFFFF);
-        bw[i] = (short)(pack2(vb, 0.f) & 0xFFFF);
+        fw[i] = (short)(bf_pack(vf, 0.f) & 0xFFFF);
+        bw[i] = (short)(bf_pack(vb, 0.f) & 0xFFFF);
     }
     if (blockIdx.x == 0 && threadIdx.x < 32) {
         const int c = threadIdx.x;
@@ -1481,7 +1468,7 @@ extern "C" int pmx_actor_pack(const pmx_actor_params *p, void *pack_dev, void *s
     }
     hipLaunchKernelGGL(pmx_actor_pack_kernel, dim3(9, NLAYER), dim3(256), 0, reinterpret_cast<hipStream_t>(stream), a,
                        reinterpret_cast<char *>(pack_dev));
-    return hipGetLastError() == hipSuccess ? PMX_OK : PMX_ERR_HIP;
+    return pmx_launch_rc();
 }
 
 extern "C" int pmx_actor_unpack_grads(const float *grad_dev, const pmx_actor_params *out, void *stream)
@@ -1496,37 +1483,22 @@ extern "C" int pmx_actor_unpack_grads(const float *grad_dev, const pmx_actor_par
         if (!a.w[l] || !a.b[l] || (l >= 2 && (!a.gw[l] || !a.gb[l]))) return PMX_ERR_INVALID;
     }
     hipLaunchKernelGGL(pmx_actor_unpack_kernel, dim3(9, NLAYER), dim3(256), 0, reinterpret_cast<hipStream_t>(stream), a, grad_dev);
-    return hipGetLastError() == hipSuccess ? PMX_OK : PMX_ERR_HIP;
+    return pmx_launch_rc();
 }
 
 namespace {
 
 template <typename K> int allow_lds(K kernel, size_t lds)
 {
-    // the attribute belongs to ONE kernel on the CURRENT device: latched per (kernel address, device).  (A static flag inside this
-    // template is shared by every instantiation with the same function-pointer TYPE -- e.g. the <10> and <11> data kernels.)
-    if (lds <= 65536) return PMX_OK;
-    struct Key { const void *fn; int dev; };
-    static Key done[256];
-    static int n_done = 0;
-    int dev = 0;
-    if (hipGetDevice(&dev) != hipSuccess) return PMX_ERR_HIP;
-    const void *fn = reinterpret_cast<const void *>(kernel);
-    for (int i = 0; i < n_done; ++i)
-        if (done[i].fn == fn && done[i].dev == dev) return PMX_OK;
     // the 160 KB of a CU hold the kernel's static LDS too (cell_tab / pos_tab, < 4 KB): ask for the rest.  The largest launch is two
     // 50 KB maps.
-    if (hipFuncSetAttribute(fn, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024 - 4096) != hipSuccess) return PMX_ERR_HIP;
-    if (n_done < 256) done[n_done++] = Key{fn, dev};               // (past 256 entries the attribute is simply set again)
-    return PMX_OK;
+    return pmx_allow_lds(reinterpret_cast<const void *>(kernel), lds, PMX_LDS_PER_CU - 4096);
 }
 
 int grid_for(int64_t B, int blocks_per_cu)
 {
-    int dev = 0, cus = 256;
-    if (hipGetDevice(&dev) != hipSuccess || hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, dev) != hipSuccess) cus = 256;
     const int64_t want = (B + 3) / 4;
-    const int64_t cap = (int64_t)cus * blocks_per_cu;
+    const int64_t cap = (int64_t)pmx_cu_count() * blocks_per_cu;
     return (int)(want < cap ? want : cap);
 }
 
@@ -1570,7 +1542,7 @@ int launch_fwd(const void *obs, const void *pack, void *feat, void *save, void *
             else { if (ws == 2) PMX_FWD_SPLIT(false, 2); else PMX_FWD_SPLIT(false, 4); }
         }
 #undef PMX_FWD_SPLIT
-        return hipGetLastError() == hipSuccess ? PMX_OK : PMX_ERR_HIP;
+        return pmx_launch_rc();
     }
     if constexpr (!large_board(NT)) {
         const size_t lds = (size_t)4 * map_positions(NT, W + 2) * 64;
@@ -1586,7 +1558,7 @@ int launch_fwd(const void *obs, const void *pack, void *feat, void *save, void *
                                (const char *)pack, (uint2 *)feat, hs, ys, stt, rtmp, (int)B, H, W, 1e-5f);
         }
     }
-    return hipGetLastError() == hipSuccess ? PMX_OK : PMX_ERR_HIP;
+    return pmx_launch_rc();
 }
 
 template <int NT, typename IN_T>
@@ -1639,9 +1611,8 @@ int launch_bwd(const void *obs, const void *pack, const void *save, const void *
         }
     }
     hipLaunchKernelGGL(pmx_actor_sum_acc_kernel, dim3(NLAYER * 96 / 32), dim3(256), 0, st, (const float *)accpart, grid_d, grad);
-    if (hipGetLastError() != hipSuccess) return PMX_ERR_HIP;
-    int dev = 0, cus = 256;
-    if (hipGetDevice(&dev) != hipSuccess || hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, dev) != hipSuccess) cus = 256;
+    if (pmx_launch_rc()) return PMX_ERR_HIP;
+    const int cus = pmx_cu_count();
     float *wpart = accpart + (size_t)1024 * 768;                             // then the weight kernel's partial rows
     if constexpr (large_board(NT)) {
         // weight gradient, large boards: layers x blocks of two sample PAIRS-of-waves; a partial row per pair (<= W_PART_ROWS rows),
@@ -1673,7 +1644,7 @@ int launch_bwd(const void *obs, const void *pack, const void *save, const void *
                            (const bf16x8 *)da, wpart, (int)B, H, W, (int)per_wave);
         hipLaunchKernelGGL(pmx_actor_sum_w_kernel, dim3(NLAYER * 36 * 256 / 32), dim3(256), 0, st, (const float *)wpart, (int)chunks, grad);
     }
-    return hipGetLastError() == hipSuccess ? PMX_OK : PMX_ERR_HIP;
+    return pmx_launch_rc();
 }
 
 }   // namespace
@@ -1754,7 +1725,7 @@ __global__ __launch_bounds__(256) void pmx_proj_pack_kernel(const float *__restr
         const int j = i & 7, lane = (i >> 3) & 63, ky = (i >> 9) % 3, m = i / (512 * 3);
         const int co = 16 * m + (lane & 15), kx = lane >> 4;                    // k-slot 8 kx + j = (tap kx of the row, input channel j)
         const float v = kx < 3 ? w[((size_t)co * 8 + j) * 9 + ky * 3 + kx] : 0.f;
-        fw[i] = (short)(pack2(v, 0.f) & 0xFFFF);
+        fw[i] = (short)(bf_pack(v, 0.f) & 0xFFFF);
     }
     if (blockIdx.x == 0 && threadIdx.x < 32) reinterpret_cast<float *>(pack + PROJ_PACK_BIAS)[threadIdx.x] = b[threadIdx.x];
 }
@@ -1807,9 +1778,9 @@ __global__ __launch_bounds__(64 * WPB) void pmx_proj_fwd_kernel(const IN_T *__re
                 for (int m = 0; m < 2; ++m) {
                     const float4 e = *reinterpret_cast<const float4 *>(pe + (size_t)ci * 32 + 16 * m + 4 * g);
                     // what bf16 autocast computes: the convolution (+ bias) rounded to bf16, then the bf16 sum with the bf16 table
-                    const uint2 c2 = {pack2(a[m][0] + bias[m][0], a[m][1] + bias[m][1]), pack2(a[m][2] + bias[m][2], a[m][3] + bias[m][3])};
-                    const uint2 e2 = {pack2(e.x, e.y), pack2(e.z, e.w)};
-                    const uint2 y2 = {pack2(lo_f(c2.x) + lo_f(e2.x), hi_f(c2.x) + hi_f(e2.x)), pack2(lo_f(c2.y) + lo_f(e2.y), hi_f(c2.y) + hi_f(e2.y))};
+                    const uint2 c2 = {bf_pack(a[m][0] + bias[m][0], a[m][1] + bias[m][1]), bf_pack(a[m][2] + bias[m][2], a[m][3] + bias[m][3])};
+                    const uint2 e2 = {bf_pack(e.x, e.y), bf_pack(e.z, e.w)};
+                    const uint2 y2 = {bf_pack(bf_lo(c2.x) + bf_lo(e2.x), bf_hi(c2.x) + bf_hi(e2.x)), bf_pack(bf_lo(c2.y) + bf_lo(e2.y), bf_hi(c2.y) + bf_hi(e2.y))};
                     tok[((size_t)s * G.HW + ci) * 8 + 4 * m + g] = y2;
                 }
             }
@@ -1849,8 +1820,8 @@ __global__ __launch_bounds__(256, 2) void pmx_proj_wgrad_kernel(const IN_T *__re
         for (int i = threadIdx.x; i < G.HW * 4; i += 256) {
             const uint4 u = dtok[(size_t)s * G.HW * 4 + i];
             *reinterpret_cast<uint4 *>(mapD + (size_t)pos_tab[i >> 2] * 64 + (i & 3) * 16) = u;
-            db[0] += lo_f(u.x), db[1] += hi_f(u.x), db[2] += lo_f(u.y), db[3] += hi_f(u.y);
-            db[4] += lo_f(u.z), db[5] += hi_f(u.z), db[6] += lo_f(u.w), db[7] += hi_f(u.w);
+            db[0] += bf_lo(u.x), db[1] += bf_hi(u.x), db[2] += bf_lo(u.y), db[3] += bf_hi(u.y);
+            db[4] += bf_lo(u.z), db[5] += bf_hi(u.z), db[6] += bf_lo(u.w), db[7] += bf_hi(u.w);
         }
         __syncthreads();
         for (int ks = wave; ks < KS; ks += 4) {
@@ -1943,7 +1914,7 @@ int launch_proj_fwd(const void *obs, const void *pack, const float *pe, void *to
     int64_t want = (B + WPB - 1) / WPB, cap = 256 * 8;
     hipLaunchKernelGGL((pmx_proj_fwd_kernel<NT, IN_T, WPB>), dim3((unsigned)(want < cap ? want : cap)), dim3(64 * WPB), lds, st, (const IN_T *)obs,
                        (const char *)pack, pe, (uint2 *)tok, (int)B, H, W);
-    return hipGetLastError() == hipSuccess ? PMX_OK : PMX_ERR_HIP;
+    return pmx_launch_rc();
 }
 
 template <int NT, typename IN_T>
@@ -1959,7 +1930,7 @@ int launch_proj_bwd(const void *obs, const void *dtok, float *part, float *dw, f
     hipLaunchKernelGGL((pmx_proj_wgrad_kernel<NT, IN_T>), dim3((unsigned)blocks), dim3(256), lds, st, (const IN_T *)obs, (const uint4 *)dtok, part,
                        (int)B, H, W, (int)per_block);
     hipLaunchKernelGGL(pmx_proj_sum_kernel, dim3((32 * 72 + 32 + 31) / 32), dim3(256), 0, st, (const float *)part, (int)blocks, dw, db);
-    return hipGetLastError() == hipSuccess ? PMX_OK : PMX_ERR_HIP;
+    return pmx_launch_rc();
 }
 
 }   // namespace
@@ -1968,7 +1939,7 @@ extern "C" int pmx_proj_pack(const float *w, const float *b, void *pack_dev, voi
 {
     if (!w || !b || !pack_dev) return PMX_ERR_INVALID;
     hipLaunchKernelGGL(pmx_proj_pack_kernel, dim3(6), dim3(256), 0, reinterpret_cast<hipStream_t>(stream), w, b, reinterpret_cast<char *>(pack_dev));
-    return hipGetLastError() == hipSuccess ? PMX_OK : PMX_ERR_HIP;
+    return pmx_launch_rc();
 }
 
 extern "C" int pmx_proj_forward(const void *obs_dev, int32_t obs_dtype, const void *pack_dev, const float *posenc_dev, void *tokens_dev, int64_t B,

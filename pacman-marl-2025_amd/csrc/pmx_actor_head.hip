@@ -20,14 +20,11 @@
 #include <stdint.h>
 
 #include "../../include/pmx.h"
+#include "pmx_common.h"
 
 extern "C" int pmx_actor_supported(int32_t H, int32_t W);
 
 namespace {
-
-typedef __attribute__((ext_vector_type(8))) short bf16x8;
-typedef __attribute__((ext_vector_type(4))) short bf16x4;
-typedef __attribute__((ext_vector_type(4))) float f32x4;
 
 constexpr int HID = 512;              // output features of the layer
 constexpr int TILE = 128;             // output tile side
@@ -38,13 +35,6 @@ constexpr int FWD_MAX_SPLIT = 64;
 constexpr int WG_BLOCKS = 512;        // weight gradient: split the batch until about two blocks per CU
 constexpr int DB_ROWS = 64;           // partial rows of the bias gradient
 
-__device__ __forceinline__ uint32_t bf_pack(float a, float b)
-{
-    typedef __attribute__((ext_vector_type(2))) float f2;
-    typedef __attribute__((ext_vector_type(2))) __bf16 b2;
-    const f2 f = {a, b};
-    return __builtin_bit_cast(uint32_t, __builtin_convertvector(f, b2));
-}
 __device__ __forceinline__ unsigned short bf_one(float a) { return (unsigned short)(bf_pack(a, 0.f) & 0xFFFFu); }
 
 // 16 bytes from global memory (per-lane address) to LDS (wave-uniform base + 16 * lane)
@@ -424,7 +414,7 @@ extern "C" int pmx_actor_head_pack(const float *w, void *pack_dev, int32_t H, in
     hipStream_t st = reinterpret_cast<hipStream_t>(stream);
     hipLaunchKernelGGL(pmx_head_pack_kernel, dim3((p.Kp / 32 + 63) / 64, HID / 8), dim3(256), 0, st, w, wp, (int)(H * W), p.Kp);
     hipLaunchKernelGGL(pmx_head_pack_t_kernel, dim3(p.Kp / 64, HID / 64), dim3(256), 0, st, (const unsigned short *)wp, wpt, p.K, p.Kp);
-    return hipGetLastError() == hipSuccess ? PMX_OK : PMX_ERR_HIP;
+    return pmx_launch_rc();
 }
 
 extern "C" int pmx_actor_head_forward(const void *feat_dev, const void *pack_dev, const float *bias, void *h_dev, void *scratch_dev, int64_t B,
@@ -448,7 +438,7 @@ extern "C" int pmx_actor_head_forward(const void *feat_dev, const void *pack_dev
         hipLaunchKernelGGL(pmx_head_fwd_sum_kernel, dim3((unsigned)((quads + 255) / 256)), dim3(256), 0, st, (const float *)scratch_dev, bias,
                            (unsigned short *)h_dev, quads, B * HID, p.splits);
     }
-    return hipGetLastError() == hipSuccess ? PMX_OK : PMX_ERR_HIP;
+    return pmx_launch_rc();
 }
 
 extern "C" int pmx_actor_head_backward(const void *feat_dev, const void *dh_dev, const void *pack_dev, void *dfeat_dev, float *dw_dev, float *db_dev,
@@ -471,5 +461,5 @@ extern "C" int pmx_actor_head_backward(const void *feat_dev, const void *dh_dev,
     const int cell_blocks = (H * W + 31) / 32;
     hipLaunchKernelGGL(pmx_head_wgrad_sum_kernel, dim3(cell_blocks * HID + HID / 256), dim3(256), 0, st, (const float *)slab, (const float *)partial, dw_dev,
                        db_dev, (int)(H * W), p.chunks, p.db_rows, cell_blocks);
-    return hipGetLastError() == hipSuccess ? PMX_OK : PMX_ERR_HIP;
+    return pmx_launch_rc();
 }

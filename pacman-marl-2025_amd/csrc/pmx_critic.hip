@@ -22,14 +22,9 @@
 #include <stdint.h>
 
 #include "../../include/pmx.h"
+#include "pmx_common.h"
 
 namespace {
-
-typedef __attribute__((ext_vector_type(8))) short bf16x8;
-typedef __attribute__((ext_vector_type(4))) short bf16x4;
-typedef __attribute__((ext_vector_type(4))) float f32x4;
-typedef __attribute__((ext_vector_type(2))) float f32x2;
-typedef __attribute__((ext_vector_type(2))) __bf16 bf16x2_t;
 
 // packed-parameter buffer (bytes)
 constexpr int FRAG = 64 * 8;                                 // bf16 elements of one operand fragment
@@ -44,14 +39,6 @@ static_assert(P_BYTES == PMX_FFN_PACK_BYTES, "include/pmx.h and pmx_critic.hip d
 constexpr int G_W2 = 0, G_W1 = G_W2 + 32 * 128, G_B1 = G_W1 + 128 * 32, G_B2 = G_B1 + 128, G_GAMMA = G_B2 + 32, G_BETA = G_GAMMA + 32;
 constexpr int G_FLOATS = G_BETA + 32;
 static_assert(G_FLOATS == PMX_FFN_GRAD_FLOATS, "include/pmx.h and pmx_critic.hip disagree on the gradient size");
-
-__device__ __forceinline__ uint32_t pack2(float a, float b)
-{
-    f32x2 f = {a, b};
-    return __builtin_bit_cast(uint32_t, __builtin_convertvector(f, bf16x2_t));
-}
-__device__ __forceinline__ float lo_f(uint32_t u) { return __uint_as_float(u << 16); }
-__device__ __forceinline__ float hi_f(uint32_t u) { return __uint_as_float(u & 0xFFFF0000u); }
 
 __device__ __forceinline__ bf16x8 frag_of(uint32_t a, uint32_t b, uint32_t c, uint32_t d)
 {
@@ -116,8 +103,8 @@ __device__ __forceinline__ void ffn_tile(const Weights &w, const uint4 xb, const
     for (int m = 0; m < 8; ++m) {
         f32x4 c = {b1[m][0], b1[m][1], b1[m][2], b1[m][3]};
         c = __builtin_amdgcn_mfma_f32_16x16x32_bf16(w.A1[m], B0, c, 0, 0, 0);
-        hr[m][0] = pack2(fmaxf(c[0], 0.f), fmaxf(c[1], 0.f));
-        hr[m][1] = pack2(fmaxf(c[2], 0.f), fmaxf(c[3], 0.f));
+        hr[m][0] = bf_pack(fmaxf(c[0], 0.f), fmaxf(c[1], 0.f));
+        hr[m][1] = bf_pack(fmaxf(c[2], 0.f), fmaxf(c[3], 0.f));
     }
     f32x4 f0 = {b2[0], b2[1], b2[2], b2[3]}, f1 = {b2[4], b2[5], b2[6], b2[7]};
 #pragma unroll
@@ -126,7 +113,7 @@ __device__ __forceinline__ void ffn_tile(const Weights &w, const uint4 xb, const
         f0 = __builtin_amdgcn_mfma_f32_16x16x32_bf16(w.A2[0][s], B1, f0, 0, 0, 0);
         f1 = __builtin_amdgcn_mfma_f32_16x16x32_bf16(w.A2[1][s], B1, f1, 0, 0, 0);
     }
-    const float x[8] = {lo_f(xb.x), hi_f(xb.x), lo_f(xb.y), hi_f(xb.y), lo_f(xb.z), hi_f(xb.z), lo_f(xb.w), hi_f(xb.w)};
+    const float x[8] = {bf_lo(xb.x), bf_hi(xb.x), bf_lo(xb.y), bf_hi(xb.y), bf_lo(xb.z), bf_hi(xb.z), bf_lo(xb.w), bf_hi(xb.w)};
 #pragma unroll
     for (int r = 0; r < 4; ++r) z[r] = x[r] + f0[r], z[4 + r] = x[4 + r] + f1[r];
 }
@@ -178,7 +165,7 @@ __global__ __launch_bounds__(256, 2) void pmx_ffn_fwd_kernel(const uint4 *__rest
 #pragma unroll
         for (int j = 0; j < 8; ++j) o[j] = fmaf(z[j] * rstd, gamma[j], beta[j]);
         const long tok = tile * 16 + p;
-        if (tok < T) y[tok * 4 + g] = uint4{pack2(o[0], o[1]), pack2(o[2], o[3]), pack2(o[4], o[5]), pack2(o[6], o[7])};
+        if (tok < T) y[tok * 4 + g] = uint4{bf_pack(o[0], o[1]), bf_pack(o[2], o[3]), bf_pack(o[4], o[5]), bf_pack(o[6], o[7])};
         x0 = x1, x1 = x2;
     }
 }
@@ -263,7 +250,7 @@ __global__ __launch_bounds__(256, 1) void pmx_ffn_bwd_kernel(const uint4 *__rest
                 s2 = fmaf(z[j], z[j], s2);
             }
             const float rstd = __builtin_amdgcn_rsqf(token_sum(s2) * (1.0f / 32.0f) + eps);
-            const float d[8] = {lo_f(dc[u].x), hi_f(dc[u].x), lo_f(dc[u].y), hi_f(dc[u].y), lo_f(dc[u].z), hi_f(dc[u].z), lo_f(dc[u].w), hi_f(dc[u].w)};
+            const float d[8] = {bf_lo(dc[u].x), bf_hi(dc[u].x), bf_lo(dc[u].y), bf_hi(dc[u].y), bf_lo(dc[u].z), bf_hi(dc[u].z), bf_lo(dc[u].w), bf_hi(dc[u].w)};
             float gd[8], t1 = 0.f, t2 = 0.f;
 #pragma unroll
             for (int j = 0; j < 8; ++j) {
@@ -279,9 +266,9 @@ __global__ __launch_bounds__(256, 1) void pmx_ffn_bwd_kernel(const uint4 *__rest
             float dz[8];
 #pragma unroll
             for (int j = 0; j < 8; ++j) dz[j] = rstd * (gd[j] - t1 - z[j] * t2);
-            const uint4 dzb = {pack2(dz[0], dz[1]), pack2(dz[2], dz[3]), pack2(dz[4], dz[5]), pack2(dz[6], dz[7])};
+            const uint4 dzb = {bf_pack(dz[0], dz[1]), bf_pack(dz[2], dz[3]), bf_pack(dz[4], dz[5]), bf_pack(dz[6], dz[7])};
             {   // the bias gradient of the second product sums what the matrix cores see
-                const float q[8] = {lo_f(dzb.x), hi_f(dzb.x), lo_f(dzb.y), hi_f(dzb.y), lo_f(dzb.z), hi_f(dzb.z), lo_f(dzb.w), hi_f(dzb.w)};
+                const float q[8] = {bf_lo(dzb.x), bf_hi(dzb.x), bf_lo(dzb.y), bf_hi(dzb.y), bf_lo(dzb.z), bf_hi(dzb.z), bf_lo(dzb.w), bf_hi(dzb.w)};
 #pragma unroll
                 for (int j = 0; j < 8; ++j) db2[j] += q[j];
             }
@@ -292,10 +279,10 @@ __global__ __launch_bounds__(256, 1) void pmx_ffn_bwd_kernel(const uint4 *__rest
             for (int m = 0; m < 8; ++m) {
                 f32x4 c = {0.f, 0.f, 0.f, 0.f};
                 c = __builtin_amdgcn_mfma_f32_16x16x32_bf16(A3[m], Bd, c, 0, 0, 0);
-                const float h0 = lo_f(hr[m][0]), h1 = hi_f(hr[m][0]), h2 = lo_f(hr[m][1]), h3 = hi_f(hr[m][1]);
+                const float h0 = bf_lo(hr[m][0]), h1 = bf_hi(hr[m][0]), h2 = bf_lo(hr[m][1]), h3 = bf_hi(hr[m][1]);
                 const float c0 = h0 > 0.f ? c[0] : 0.f, c1 = h1 > 0.f ? c[1] : 0.f, c2 = h2 > 0.f ? c[2] : 0.f, c3 = h3 > 0.f ? c[3] : 0.f;
-                dh[m][0] = pack2(c0, c1), dh[m][1] = pack2(c2, c3);
-                db1[m][0] += lo_f(dh[m][0]), db1[m][1] += hi_f(dh[m][0]), db1[m][2] += lo_f(dh[m][1]), db1[m][3] += hi_f(dh[m][1]);
+                dh[m][0] = bf_pack(c0, c1), dh[m][1] = bf_pack(c2, c3);
+                db1[m][0] += bf_lo(dh[m][0]), db1[m][1] += bf_hi(dh[m][0]), db1[m][2] += bf_lo(dh[m][1]), db1[m][3] += bf_hi(dh[m][1]);
             }
             f32x4 e0 = {dz[0], dz[1], dz[2], dz[3]}, e1 = {dz[4], dz[5], dz[6], dz[7]};
 #pragma unroll
@@ -305,7 +292,7 @@ __global__ __launch_bounds__(256, 1) void pmx_ffn_bwd_kernel(const uint4 *__rest
                 e1 = __builtin_amdgcn_mfma_f32_16x16x32_bf16(A4[1][s], Bh, e1, 0, 0, 0);
             }
             const long tok = pair * 32 + 16 * u + p;
-            if (tok < T) dx[tok * 4 + g] = uint4{pack2(e0[0], e0[1]), pack2(e0[2], e0[3]), pack2(e1[0], e1[1]), pack2(e1[2], e1[3])};
+            if (tok < T) dx[tok * 4 + g] = uint4{bf_pack(e0[0], e0[1]), bf_pack(e0[2], e0[3]), bf_pack(e1[0], e1[1]), bf_pack(e1[2], e1[3])};
             // stage this tile's operands of the weight gradients: [token][x | dF | H | dH]
             char *row = stg + (16 * u + p) * STG_ROW;
             *reinterpret_cast<uint4 *>(row + STG_X + 16 * g) = xc[u];
@@ -430,13 +417,13 @@ __device__ __forceinline__ void ffn_pack_body(const float *__restrict__ w1, cons
         const int psi_row = 8 * (row >> 2) + (row & 3);                 // + 4 * half
         auto phi = [&](int s) { return 32 * s + 16 * (j >> 2) + 4 * g + (j & 3); };
         // A1[m = f]: W1[hidden 16 m + row][in 8 g + j]
-        a1[i] = (short)(pack2(w1[(16 * f + row) * 32 + 8 * g + j], 0.f) & 0xFFFF);
+        a1[i] = (short)(bf_pack(w1[(16 * f + row) * 32 + 8 * g + j], 0.f) & 0xFFFF);
         // A2[mo][s], f = mo * 4 + s: W2[out psi(mo, row)][hidden phi(s, g, j)]
-        a2[i] = (short)(pack2(w2[(psi_row + 4 * (f >> 2)) * 128 + phi(f & 3)], 0.f) & 0xFFFF);
+        a2[i] = (short)(bf_pack(w2[(psi_row + 4 * (f >> 2)) * 128 + phi(f & 3)], 0.f) & 0xFFFF);
         // A3[m = f]: W2[out 8 g + j][hidden 16 m + row]      (dH = W2^T dF)
-        a3[i] = (short)(pack2(w2[(8 * g + j) * 128 + 16 * f + row], 0.f) & 0xFFFF);
+        a3[i] = (short)(bf_pack(w2[(8 * g + j) * 128 + 16 * f + row], 0.f) & 0xFFFF);
         // A4[mo][s]: W1[hidden phi(s, g, j)][in psi(mo, row)]  (dX = W1^T dH)
-        a4[i] = (short)(pack2(w1[phi(f & 3) * 32 + psi_row + 4 * (f >> 2)], 0.f) & 0xFFFF);
+        a4[i] = (short)(bf_pack(w1[phi(f & 3) * 32 + psi_row + 4 * (f >> 2)], 0.f) & 0xFFFF);
     }
     if (bx == 0) {
         float *pb = reinterpret_cast<float *>(pack + P_B1);
@@ -507,7 +494,7 @@ __global__ __launch_bounds__(256, 2) void pmx_tok_fwd_kernel(const uint4 *__rest
             c1 = __builtin_amdgcn_mfma_f32_16x16x32_bf16(A[2 * q + 1], B0, c1, 0, 0, 0);
             float o[8] = {c0[0], c0[1], c0[2], c0[3], c1[0], c1[1], c1[2], c1[3]};
             if (LN) {
-                const float xv[8] = {lo_f(x0.x), hi_f(x0.x), lo_f(x0.y), hi_f(x0.y), lo_f(x0.z), hi_f(x0.z), lo_f(x0.w), hi_f(x0.w)};
+                const float xv[8] = {bf_lo(x0.x), bf_hi(x0.x), bf_lo(x0.y), bf_hi(x0.y), bf_lo(x0.z), bf_hi(x0.z), bf_lo(x0.w), bf_hi(x0.w)};
                 float s1 = 0.f, s2 = 0.f;
 #pragma unroll
                 for (int j = 0; j < 8; ++j) o[j] += xv[j], s1 += o[j];
@@ -518,7 +505,7 @@ __global__ __launch_bounds__(256, 2) void pmx_tok_fwd_kernel(const uint4 *__rest
 #pragma unroll
                 for (int j = 0; j < 8; ++j) o[j] = fmaf(o[j] * rstd, gamma[j], beta[j]);
             }
-            if (tok < T) y[tok * (4 * NP) + 4 * q + g] = uint4{pack2(o[0], o[1]), pack2(o[2], o[3]), pack2(o[4], o[5]), pack2(o[6], o[7])};
+            if (tok < T) y[tok * (4 * NP) + 4 * q + g] = uint4{bf_pack(o[0], o[1]), bf_pack(o[2], o[3]), bf_pack(o[4], o[5]), bf_pack(o[6], o[7])};
         }
         a0 = a1, a1 = a2, x0 = x1, x1 = x2;
     }
@@ -600,7 +587,7 @@ __global__ __launch_bounds__(256, 2) void pmx_tok_bwd_kernel(const uint4 *__rest
                 c0 = __builtin_amdgcn_mfma_f32_16x16x32_bf16(A[0], B0, c0, 0, 0, 0);
                 c1 = __builtin_amdgcn_mfma_f32_16x16x32_bf16(A[1], B0, c1, 0, 0, 0);
                 const uint4 xb = xv4[u];
-                const float xf[8] = {lo_f(xb.x), hi_f(xb.x), lo_f(xb.y), hi_f(xb.y), lo_f(xb.z), hi_f(xb.z), lo_f(xb.w), hi_f(xb.w)};
+                const float xf[8] = {bf_lo(xb.x), bf_hi(xb.x), bf_lo(xb.y), bf_hi(xb.y), bf_lo(xb.z), bf_hi(xb.z), bf_lo(xb.w), bf_hi(xb.w)};
                 float z[8] = {c0[0], c0[1], c0[2], c0[3], c1[0], c1[1], c1[2], c1[3]};
                 float s1 = 0.f, s2 = 0.f;
 #pragma unroll
@@ -610,7 +597,7 @@ __global__ __launch_bounds__(256, 2) void pmx_tok_bwd_kernel(const uint4 *__rest
                 for (int j = 0; j < 8; ++j) z[j] -= mean, s2 = fmaf(z[j], z[j], s2);
                 const float rstd = __builtin_amdgcn_rsqf(token_sum(s2) * (1.0f / 32.0f) + eps);
                 const uint4 db4 = dv[u][0];
-                const float d[8] = {lo_f(db4.x), hi_f(db4.x), lo_f(db4.y), hi_f(db4.y), lo_f(db4.z), hi_f(db4.z), lo_f(db4.w), hi_f(db4.w)};
+                const float d[8] = {bf_lo(db4.x), bf_hi(db4.x), bf_lo(db4.y), bf_hi(db4.y), bf_lo(db4.z), bf_hi(db4.z), bf_lo(db4.w), bf_hi(db4.w)};
                 float gd[8], t1 = 0.f, t2 = 0.f;
 #pragma unroll
                 for (int j = 0; j < 8; ++j) {
@@ -626,7 +613,7 @@ __global__ __launch_bounds__(256, 2) void pmx_tok_bwd_kernel(const uint4 *__rest
                 float dz[8];
 #pragma unroll
                 for (int j = 0; j < 8; ++j) dz[j] = rstd * (gd[j] - t1 - z[j] * t2);
-                dt[0] = uint4{pack2(dz[0], dz[1]), pack2(dz[2], dz[3]), pack2(dz[4], dz[5]), pack2(dz[6], dz[7])};
+                dt[0] = uint4{bf_pack(dz[0], dz[1]), bf_pack(dz[2], dz[3]), bf_pack(dz[4], dz[5]), bf_pack(dz[6], dz[7])};
                 const long tok = pair * 32 + 16 * u + p;
                 if (tok < T) dx[tok * 4 + g] = dt[0];
             } else {
@@ -640,7 +627,7 @@ __global__ __launch_bounds__(256, 2) void pmx_tok_bwd_kernel(const uint4 *__rest
                 const bf16x8 Bd = __builtin_bit_cast(bf16x8, dt[q]);
                 e0 = __builtin_amdgcn_mfma_f32_16x16x32_bf16(At[0][q], Bd, e0, 0, 0, 0);
                 e1 = __builtin_amdgcn_mfma_f32_16x16x32_bf16(At[1][q], Bd, e1, 0, 0, 0);
-                const float v[8] = {lo_f(dt[q].x), hi_f(dt[q].x), lo_f(dt[q].y), hi_f(dt[q].y), lo_f(dt[q].z), hi_f(dt[q].z), lo_f(dt[q].w), hi_f(dt[q].w)};
+                const float v[8] = {bf_lo(dt[q].x), bf_hi(dt[q].x), bf_lo(dt[q].y), bf_hi(dt[q].y), bf_lo(dt[q].z), bf_hi(dt[q].z), bf_lo(dt[q].w), bf_hi(dt[q].w)};
 #pragma unroll
                 for (int j = 0; j < 8; ++j) db[q][j] += v[j];
             }
@@ -648,11 +635,11 @@ __global__ __launch_bounds__(256, 2) void pmx_tok_bwd_kernel(const uint4 *__rest
                 // the residual branch's gradient of the same tokens (the encoder layer's input feeds the in-projection AND the residual
                 // add in front of norm1): summed here in float32 and rounded once, instead of by an add kernel of autograd's
                 const uint4 r = xv4[u];
-                e0[0] += lo_f(r.x), e0[1] += hi_f(r.x), e0[2] += lo_f(r.y), e0[3] += hi_f(r.y);
-                e1[0] += lo_f(r.z), e1[1] += hi_f(r.z), e1[2] += lo_f(r.w), e1[3] += hi_f(r.w);
+                e0[0] += bf_lo(r.x), e0[1] += bf_hi(r.x), e0[2] += bf_lo(r.y), e0[3] += bf_hi(r.y);
+                e1[0] += bf_lo(r.z), e1[1] += bf_hi(r.z), e1[2] += bf_lo(r.w), e1[3] += bf_hi(r.w);
             }
             const long tok = pair * 32 + 16 * u + p;
-            if (tok < T) da[tok * 4 + g] = uint4{pack2(e0[0], e0[1]), pack2(e0[2], e0[3]), pack2(e1[0], e1[1]), pack2(e1[2], e1[3])};
+            if (tok < T) da[tok * 4 + g] = uint4{bf_pack(e0[0], e0[1]), bf_pack(e0[2], e0[3]), bf_pack(e1[0], e1[1]), bf_pack(e1[2], e1[3])};
             char *row = stg + (16 * u + p) * ROW;
             *reinterpret_cast<uint4 *>(row + 16 * g) = av[u];
 #pragma unroll
@@ -715,9 +702,9 @@ __device__ __forceinline__ void tok_pack_body(const float *__restrict__ w, const
         const int row = lane & 15, g = lane >> 4;
         const int psi_row = 8 * (row >> 2) + (row & 3);
         // forward fragment f = 2 q + m': W[out 32 q + psi(m', row)][in 8 g + j]
-        af[i] = (short)(pack2(w[(32 * (f >> 1) + psi_row + 4 * (f & 1)) * 32 + 8 * g + j], 0.f) & 0xFFFF);
+        af[i] = (short)(bf_pack(w[(32 * (f >> 1) + psi_row + 4 * (f & 1)) * 32 + 8 * g + j], 0.f) & 0xFFFF);
         // backward fragment f = mo * NP + q: W[out 32 q + 8 g + j][in psi(mo, row)]
-        ab[i] = (short)(pack2(w[(32 * (f % NP) + 8 * g + j) * 32 + psi_row + 4 * (f / NP)], 0.f) & 0xFFFF);
+        ab[i] = (short)(bf_pack(w[(32 * (f % NP) + 8 * g + j) * 32 + psi_row + 4 * (f / NP)], 0.f) & 0xFFFF);
     }
     if (bx == 0) {
         float *pf = reinterpret_cast<float *>(pack + TokPack<NP>::FLT);
@@ -750,13 +737,6 @@ __global__ __launch_bounds__(256) void pmx_encoder_pack_kernel(EncoderPackArgs a
     else ffn_pack_body(L.lin1_w, L.lin1_b, L.lin2_w, L.lin2_b, L.norm2_w, L.norm2_b, reinterpret_cast<char *>(L.pack_ffn), bx, nbx);
 }
 
-int cu_count()
-{
-    int dev = 0, cus = 256;
-    if (hipGetDevice(&dev) != hipSuccess || hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, dev) != hipSuccess) cus = 256;
-    return cus;
-}
-
 }   // namespace
 
 extern "C" int pmx_encoder_pack(int32_t n_layers, const pmx_encoder_layer_params *layers, void *stream)
@@ -771,7 +751,7 @@ extern "C" int pmx_encoder_pack(int32_t n_layers, const pmx_encoder_layer_params
             return PMX_ERR_INVALID;
     }
     hipLaunchKernelGGL(pmx_encoder_pack_kernel, dim3(8, 3 * n_layers), dim3(256), 0, reinterpret_cast<hipStream_t>(stream), a);
-    return hipGetLastError() == hipSuccess ? PMX_OK : PMX_ERR_HIP;
+    return pmx_launch_rc();
 }
 
 extern "C" int pmx_ffn_pack(const float *w1, const float *b1, const float *w2, const float *b2, const float *gamma, const float *beta,
@@ -780,7 +760,7 @@ extern "C" int pmx_ffn_pack(const float *w1, const float *b1, const float *w2, c
     if (!w1 || !b1 || !w2 || !b2 || !gamma || !beta || !pack_dev) return PMX_ERR_INVALID;
     hipLaunchKernelGGL(pmx_ffn_pack_kernel, dim3(16), dim3(256), 0, reinterpret_cast<hipStream_t>(stream), w1, b1, w2, b2, gamma, beta,
                        reinterpret_cast<char *>(pack_dev));
-    return hipGetLastError() == hipSuccess ? PMX_OK : PMX_ERR_HIP;
+    return pmx_launch_rc();
 }
 
 extern "C" int pmx_ffn_forward(const void *x_dev, const void *pack_dev, void *y_dev, int64_t tokens, float eps, void *stream)
@@ -788,18 +768,19 @@ extern "C" int pmx_ffn_forward(const void *x_dev, const void *pack_dev, void *y_
     if (tokens == 0) return PMX_OK;
     if (!x_dev || !pack_dev || !y_dev || tokens < 0) return PMX_ERR_INVALID;
     const int64_t tiles = (tokens + 15) / 16;
-    const int64_t want = (tiles + 3) / 4, cap = (int64_t)cu_count() * 2;
+    const int64_t want = (tiles + 3) / 4, cap = (int64_t)pmx_cu_count() * 2;
     hipLaunchKernelGGL(pmx_ffn_fwd_kernel, dim3((unsigned)(want < cap ? want : cap)), dim3(256), 0, reinterpret_cast<hipStream_t>(stream),
                        (const uint4 *)x_dev, (const char *)pack_dev, (uint4 *)y_dev, (long)tokens, eps);
-    return hipGetLastError() == hipSuccess ? PMX_OK : PMX_ERR_HIP;
+    return pmx_launch_rc();
 }
 
 // Deferred row sums: with pmx_defer_row_sums(1) the backward entry points of this file and of pmx_heads.hip leave their partial rows
 // unsummed and report how many there are (pmx_last_partial_rows); the caller adds them with pmx_sum_partial_rows on a stream of its
 // choice -- a side stream, so that the second stage of one gradient reduction runs beside the next backward kernel instead of in
-// front of it (six small launches on the critical path of the launch-bound 512-sample step).  Per host thread.
-thread_local int pmx_defer_sums_flag = 0;
-thread_local int pmx_last_rows_value = 0;
+// front of it (six small launches on the critical path of the launch-bound 512-sample step).  Per host thread.  Every such entry
+// point ends in pmx_finish_partial_rows (or says pmx_no_partial_rows): nothing else reads or writes the two variables.
+static thread_local int pmx_defer_sums_flag = 0;
+static thread_local int pmx_last_rows_value = 0;
 extern "C" int pmx_defer_row_sums(int32_t on) { pmx_defer_sums_flag = on ? 1 : 0; return PMX_OK; }
 extern "C" int pmx_last_partial_rows(void) { return pmx_last_rows_value; }
 extern "C" int pmx_sum_partial_rows(float *buf_dev, int32_t n_rows, int32_t floats, void *stream)
@@ -807,7 +788,15 @@ extern "C" int pmx_sum_partial_rows(float *buf_dev, int32_t n_rows, int32_t floa
     if (!buf_dev || n_rows < 0 || floats < 1) return PMX_ERR_INVALID;
     if (n_rows == 0) return PMX_OK;
     hipLaunchKernelGGL(pmx_sum_rows_kernel, dim3((floats + 31) / 32), dim3(256), 0, reinterpret_cast<hipStream_t>(stream), buf_dev, (int)n_rows, (int)floats);
-    return hipGetLastError() == hipSuccess ? PMX_OK : PMX_ERR_HIP;
+    return pmx_launch_rc();
+}
+void pmx_no_partial_rows() { pmx_last_rows_value = 0; }
+int pmx_finish_partial_rows(float *grad, int rows, int floats, hipStream_t st)
+{
+    pmx_last_rows_value = rows;
+    if (rows > 0 && !pmx_defer_sums_flag)
+        hipLaunchKernelGGL(pmx_sum_rows_kernel, dim3((floats + 31) / 32), dim3(256), 0, st, grad, rows, floats);
+    return pmx_launch_rc();
 }
 
 extern "C" int pmx_ffn_backward(const void *x_dev, const void *dy_dev, const void *pack_dev, void *dx_dev, float *grad_dev, int64_t tokens,
@@ -815,28 +804,19 @@ extern "C" int pmx_ffn_backward(const void *x_dev, const void *dy_dev, const voi
 {
     if (!grad_dev) return PMX_ERR_INVALID;
     hipStream_t st = reinterpret_cast<hipStream_t>(stream);
-    pmx_last_rows_value = 0;                                  // (row 0 is final on every path that launches no partial rows)
+    pmx_no_partial_rows();                                    // (row 0 is final on every path that launches no partial rows)
     if (tokens == 0) return hipMemsetAsync(grad_dev, 0, sizeof(float) * G_FLOATS, st) == hipSuccess ? PMX_OK : PMX_ERR_HIP;
     if (!x_dev || !dy_dev || !pack_dev || !dx_dev || tokens < 0) return PMX_ERR_INVALID;
     const size_t lds = (size_t)4 * 32 * STG_ROW;
-    static bool attr_dev[64] = {};
-    int dev = 0;
-    if (hipGetDevice(&dev) != hipSuccess || dev < 0 || dev >= 64) return PMX_ERR_HIP;
-    if (lds > 65536 && !attr_dev[dev]) {
-        if (hipFuncSetAttribute(reinterpret_cast<const void *>(pmx_ffn_bwd_kernel), hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024) != hipSuccess)
-            return PMX_ERR_HIP;
-        attr_dev[dev] = true;
-    }
+    int rc = pmx_allow_lds(reinterpret_cast<const void *>(pmx_ffn_bwd_kernel), lds, PMX_LDS_PER_CU);
+    if (rc) return rc;
     const int64_t pairs = (tokens + 31) / 32;
-    int64_t want = (pairs + 3) / 4, cap = (int64_t)cu_count();
+    int64_t want = (pairs + 3) / 4, cap = (int64_t)pmx_cu_count();
     if (cap > PMX_GRAD_PARTIAL_ROWS) cap = PMX_GRAD_PARTIAL_ROWS;
     const unsigned blocks = (unsigned)(want < cap ? want : cap);
     hipLaunchKernelGGL(pmx_ffn_bwd_kernel, dim3(blocks), dim3(256), lds, st, (const uint4 *)x_dev, (const uint4 *)dy_dev,
                        (const char *)pack_dev, (uint4 *)dx_dev, grad_dev, (long)tokens, eps);
-    pmx_last_rows_value = (int)blocks;
-    if (!pmx_defer_sums_flag)
-        hipLaunchKernelGGL(pmx_sum_rows_kernel, dim3((G_FLOATS + 31) / 32), dim3(256), 0, st, grad_dev, (int)blocks, (int)G_FLOATS);
-    return hipGetLastError() == hipSuccess ? PMX_OK : PMX_ERR_HIP;
+    return pmx_finish_partial_rows(grad_dev, (int)blocks, G_FLOATS, st);
 }
 
 namespace {
@@ -845,30 +825,27 @@ int tok_forward(const void *a, const void *x, const void *pack, void *y, int64_t
 {
     if (tokens == 0) return PMX_OK;
     if (!a || !pack || !y || (LN && !x) || tokens < 0) return PMX_ERR_INVALID;
-    const int64_t tiles = (tokens + 15) / 16, want = (tiles + 3) / 4, cap = (int64_t)cu_count() * 2;
+    const int64_t tiles = (tokens + 15) / 16, want = (tiles + 3) / 4, cap = (int64_t)pmx_cu_count() * 2;
     hipLaunchKernelGGL((pmx_tok_fwd_kernel<NP, LN>), dim3((unsigned)(want < cap ? want : cap)), dim3(256), 0, st, (const uint4 *)a, (const uint4 *)x,
                        (const char *)pack, (uint4 *)y, (long)tokens, eps);
-    return hipGetLastError() == hipSuccess ? PMX_OK : PMX_ERR_HIP;
+    return pmx_launch_rc();
 }
 template <int NP, bool LN>
 int tok_backward(const void *a, const void *x, const void *dy, const void *pack, void *da, void *dx, float *grad, int64_t tokens, float eps,
                  hipStream_t st)
 {
     if (!grad) return PMX_ERR_INVALID;
-    pmx_last_rows_value = 0;
+    pmx_no_partial_rows();
     if (tokens == 0) return hipMemsetAsync(grad, 0, sizeof(float) * TokPack<NP>::G_FLOATS, st) == hipSuccess ? PMX_OK : PMX_ERR_HIP;
     if (!a || !dy || !pack || !da || (LN && (!x || !dx)) || tokens < 0) return PMX_ERR_INVALID;
     const size_t stage = (size_t)4 * 32 * tok_stg_row<NP>(), reduce = (size_t)4 * 4 * NP * 1024 + 4096;   // staging areas, then the block-level sums
     const size_t lds = stage > reduce ? stage : reduce;
-    int64_t pairs = (tokens + 31) / 32, want = (pairs + 3) / 4, cap = (int64_t)cu_count() * 2;
+    int64_t pairs = (tokens + 31) / 32, want = (pairs + 3) / 4, cap = (int64_t)pmx_cu_count() * 2;
     if (cap > PMX_GRAD_PARTIAL_ROWS) cap = PMX_GRAD_PARTIAL_ROWS;
     const unsigned blocks = (unsigned)(want < cap ? want : cap);
     hipLaunchKernelGGL((pmx_tok_bwd_kernel<NP, LN>), dim3(blocks), dim3(256), lds, st, (const uint4 *)a, (const uint4 *)x,
                        (const uint4 *)dy, (const char *)pack, (uint4 *)da, (uint4 *)dx, grad, (long)tokens, eps);
-    pmx_last_rows_value = (int)blocks;
-    if (!pmx_defer_sums_flag)
-        hipLaunchKernelGGL(pmx_sum_rows_kernel, dim3((TokPack<NP>::G_FLOATS + 31) / 32), dim3(256), 0, st, grad, (int)blocks, (int)TokPack<NP>::G_FLOATS);
-    return hipGetLastError() == hipSuccess ? PMX_OK : PMX_ERR_HIP;
+    return pmx_finish_partial_rows(grad, (int)blocks, TokPack<NP>::G_FLOATS, st);
 }
 }   // namespace
 
@@ -877,7 +854,7 @@ extern "C" int pmx_tok96_pack(const float *w, const float *b, void *pack_dev, vo
     if (!w || !b || !pack_dev) return PMX_ERR_INVALID;
     hipLaunchKernelGGL(pmx_tok_pack_kernel<3>, dim3(12), dim3(256), 0, reinterpret_cast<hipStream_t>(stream), w, b, (const float *)nullptr,
                        (const float *)nullptr, reinterpret_cast<char *>(pack_dev));
-    return hipGetLastError() == hipSuccess ? PMX_OK : PMX_ERR_HIP;
+    return pmx_launch_rc();
 }
 extern "C" int pmx_tok96_forward(const void *a_dev, const void *pack_dev, void *y_dev, int64_t tokens, void *stream)
 {
@@ -898,7 +875,7 @@ extern "C" int pmx_tok32ln_pack(const float *w, const float *b, const float *gam
     if (!w || !b || !gamma || !beta || !pack_dev) return PMX_ERR_INVALID;
     hipLaunchKernelGGL(pmx_tok_pack_kernel<1>, dim3(4), dim3(256), 0, reinterpret_cast<hipStream_t>(stream), w, b, gamma, beta,
                        reinterpret_cast<char *>(pack_dev));
-    return hipGetLastError() == hipSuccess ? PMX_OK : PMX_ERR_HIP;
+    return pmx_launch_rc();
 }
 extern "C" int pmx_tok32ln_forward(const void *x_dev, const void *a_dev, const void *pack_dev, void *y_dev, int64_t tokens, float eps, void *stream)
 {

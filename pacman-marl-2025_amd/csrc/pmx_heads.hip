@@ -16,43 +16,12 @@
 #include <stdint.h>
 
 #include "../../include/pmx.h"
-
-extern thread_local int pmx_defer_sums_flag;       // pmx_critic.hip: deferred row sums (pmx_defer_row_sums)
-extern thread_local int pmx_last_rows_value;
+#include "pmx_common.h"
 
 namespace {
 
 constexpr int HID = 512, PER_LANE = 8, NACT = 5, DM = 32;
 static_assert(HID == 64 * PER_LANE, "a lane owns 8 hidden features");
-
-__device__ __forceinline__ float bf_round(float x)
-{
-    typedef __attribute__((ext_vector_type(2))) float f2;
-    typedef __attribute__((ext_vector_type(2))) __bf16 b2;
-    const f2 f = {x, 0.f};
-    const uint32_t u = __builtin_bit_cast(uint32_t, __builtin_convertvector(f, b2));
-    return __uint_as_float(u << 16);
-}
-__device__ __forceinline__ float bf_lo(uint32_t u) { return __uint_as_float(u << 16); }
-__device__ __forceinline__ float bf_hi(uint32_t u) { return __uint_as_float(u & 0xFFFF0000u); }
-__device__ __forceinline__ uint32_t bf_pack(float a, float b)
-{
-    typedef __attribute__((ext_vector_type(2))) float f2;
-    typedef __attribute__((ext_vector_type(2))) __bf16 b2;
-    const f2 f = {a, b};
-    return __builtin_bit_cast(uint32_t, __builtin_convertvector(f, b2));
-}
-__device__ __forceinline__ float wave_sum(float v)
-{
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o, 64);
-    return v;
-}
-__device__ __forceinline__ float gelu_exact(float z) { return 0.5f * z * (1.0f + erff(z * 0.70710678118654752f)); }
-__device__ __forceinline__ float gelu_grad(float z)
-{
-    return 0.5f * (1.0f + erff(z * 0.70710678118654752f)) + z * 0.3989422804014327f * __expf(-0.5f * z * z);
-}
 
 // the 8 features of a lane from a row of 512 bf16 (16 bytes per lane) or float32 (two 16-byte loads)
 template <typename T> __device__ __forceinline__ void load8(const T *row, int lane, float (&v)[8]);
@@ -192,25 +161,6 @@ __global__ __launch_bounds__(256) void pmx_actor_tail_bwd_kernel(const T *__rest
     __syncthreads();
     float *row = grad + (size_t)(1 + blockIdx.x) * AT_FLOATS;
     for (int i = threadIdx.x; i < AT_FLOATS; i += 256) row[i] = (red[0][i] + red[1][i]) + (red[2][i] + red[3][i]);
-}
-
-// out[i] = sum of rows 1 .. n_rows of buf (row 0 receives it): 32 columns x 8 row slices per block
-__global__ __launch_bounds__(256) void pmx_heads_sum_rows_kernel(float *__restrict__ buf, int n_rows, int floats)
-{
-    __shared__ float part[8][33];
-    const int c = threadIdx.x & 31, sl = threadIdx.x >> 5;
-    const int i = blockIdx.x * 32 + c;
-    float acc = 0.f;
-    if (i < floats)
-        for (int r = 1 + sl; r <= n_rows; r += 8) acc += buf[(size_t)r * floats + i];
-    part[sl][c] = acc;
-    __syncthreads();
-    if (sl == 0 && i < floats) {
-        float t = 0.f;
-#pragma unroll
-        for (int k = 0; k < 8; ++k) t += part[k][c];
-        buf[i] = t;
-    }
 }
 
 // ---------------------------------------------------------------------------------------------------------------
@@ -434,7 +384,7 @@ extern "C" int pmx_actor_tail_forward(const void *h_dev, int32_t h_bf16, const f
     const int blocks = heads_blocks(B, 1024);
     if (h_bf16) hipLaunchKernelGGL(pmx_actor_tail_fwd_kernel<__hip_bfloat16>, dim3(blocks), dim3(256), 0, st, (const __hip_bfloat16 *)h_dev, ln_w, ln_b, w2, b2, logits_dev, stats_dev, (int)B, eps);
     else hipLaunchKernelGGL(pmx_actor_tail_fwd_kernel<float>, dim3(blocks), dim3(256), 0, st, (const float *)h_dev, ln_w, ln_b, w2, b2, logits_dev, stats_dev, (int)B, eps);
-    return hipGetLastError() == hipSuccess ? PMX_OK : PMX_ERR_HIP;
+    return pmx_launch_rc();
 }
 
 extern "C" int pmx_actor_tail_backward(const void *h_dev, int32_t h_bf16, const float *stats_dev, const float *dlogits_dev, const float *ln_w,
@@ -442,34 +392,14 @@ extern "C" int pmx_actor_tail_backward(const void *h_dev, int32_t h_bf16, const 
 {
     if (!grad_dev || B < 0) return PMX_ERR_INVALID;
     hipStream_t st = reinterpret_cast<hipStream_t>(stream);
-    pmx_last_rows_value = 0;
+    pmx_no_partial_rows();
     if (B == 0) return hipMemsetAsync(grad_dev, 0, sizeof(float) * AT_FLOATS, st) == hipSuccess ? PMX_OK : PMX_ERR_HIP;
     if (!h_dev || !stats_dev || !dlogits_dev || !ln_w || !ln_b || !w2 || !dh_dev) return PMX_ERR_INVALID;
     const int blocks = heads_blocks(B, PMX_HEADS_PARTIAL_ROWS);
     if (h_bf16) hipLaunchKernelGGL(pmx_actor_tail_bwd_kernel<__hip_bfloat16>, dim3(blocks), dim3(256), 0, st, (const __hip_bfloat16 *)h_dev, stats_dev, dlogits_dev, ln_w, ln_b, w2, (__hip_bfloat16 *)dh_dev, grad_dev, (int)B);
     else hipLaunchKernelGGL(pmx_actor_tail_bwd_kernel<float>, dim3(blocks), dim3(256), 0, st, (const float *)h_dev, stats_dev, dlogits_dev, ln_w, ln_b, w2, (float *)dh_dev, grad_dev, (int)B);
-    pmx_last_rows_value = blocks;
-    if (!pmx_defer_sums_flag)
-        hipLaunchKernelGGL(pmx_heads_sum_rows_kernel, dim3((AT_FLOATS + 31) / 32), dim3(256), 0, st, grad_dev, blocks, (int)AT_FLOATS);
-    return hipGetLastError() == hipSuccess ? PMX_OK : PMX_ERR_HIP;
+    return pmx_finish_partial_rows(grad_dev, blocks, AT_FLOATS, st);
 }
-
-namespace {
-int allow_big_lds(const void *fn, size_t lds)
-{
-    if (lds <= 65536) return PMX_OK;
-    struct Key { const void *fn; int dev; };
-    static Key done[16];
-    static int n_done = 0;
-    int dev = 0;
-    if (hipGetDevice(&dev) != hipSuccess) return PMX_ERR_HIP;
-    for (int i = 0; i < n_done; ++i)
-        if (done[i].fn == fn && done[i].dev == dev) return PMX_OK;
-    if (hipFuncSetAttribute(fn, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024) != hipSuccess) return PMX_ERR_HIP;
-    if (n_done < 16) done[n_done++] = Key{fn, dev};
-    return PMX_OK;
-}
-}   // namespace
 
 extern "C" int pmx_critic_tail_forward(const void *tokens_dev, const float *w1, const float *b1, const float *w2, const float *b2,
                                        float *value_dev, float *pooled_dev, int64_t B, int32_t S, void *stream)
@@ -478,11 +408,11 @@ extern "C" int pmx_critic_tail_forward(const void *tokens_dev, const float *w1, 
     if (!tokens_dev || !w1 || !b1 || !w2 || !b2 || !value_dev || !pooled_dev || B < 0 || S < 1) return PMX_ERR_INVALID;
     hipStream_t st = reinterpret_cast<hipStream_t>(stream);
     const size_t lds = sizeof(float) * (HID * DM + 4 * DM);
-    int rc = allow_big_lds(reinterpret_cast<const void *>(pmx_critic_tail_fwd_kernel), lds);
+    int rc = pmx_allow_lds(reinterpret_cast<const void *>(pmx_critic_tail_fwd_kernel), lds, PMX_LDS_PER_CU);
     if (rc) return rc;
     hipLaunchKernelGGL(pmx_critic_tail_fwd_kernel, dim3(heads_blocks(B, 512)), dim3(256), lds, st, (const __hip_bfloat16 *)tokens_dev, w1, b1, w2, b2,
                        value_dev, pooled_dev, (int)B, (int)S);
-    return hipGetLastError() == hipSuccess ? PMX_OK : PMX_ERR_HIP;
+    return pmx_launch_rc();
 }
 
 extern "C" int pmx_critic_tail_backward(const float *pooled_dev, const float *dvalue_dev, const float *w1, const float *b1, const float *w2,
@@ -490,12 +420,12 @@ extern "C" int pmx_critic_tail_backward(const float *pooled_dev, const float *dv
 {
     if (!grad_dev || B < 0) return PMX_ERR_INVALID;
     hipStream_t st = reinterpret_cast<hipStream_t>(stream);
-    pmx_last_rows_value = 0;
+    pmx_no_partial_rows();
     if (B == 0) return hipMemsetAsync(grad_dev, 0, sizeof(float) * CT_FLOATS, st) == hipSuccess ? PMX_OK : PMX_ERR_HIP;
     if (!pooled_dev || !dvalue_dev || !w1 || !b1 || !w2 || !dtokens_dev || !scratch_dev || S < 1) return PMX_ERR_INVALID;
     __hip_bfloat16 *dh = reinterpret_cast<__hip_bfloat16 *>(scratch_dev), *g = dh + (size_t)B * HID;       // scratch: 2 x B x 512 bf16
     const size_t lds = sizeof(float) * (HID * DM + 4 * DM + 4 * 64 * 33);
-    int rc = allow_big_lds(reinterpret_cast<const void *>(pmx_critic_tail_bwd_kernel), lds);
+    int rc = pmx_allow_lds(reinterpret_cast<const void *>(pmx_critic_tail_bwd_kernel), lds, PMX_LDS_PER_CU);
     if (rc) return rc;
     hipLaunchKernelGGL(pmx_critic_tail_bwd_kernel, dim3(heads_blocks(B, 512)), dim3(256), lds, st, pooled_dev, dvalue_dev, w1, b1, w2,
                        (__hip_bfloat16 *)dtokens_dev, dh, g, (int)B, (int)S);
@@ -505,8 +435,5 @@ extern "C" int pmx_critic_tail_backward(const float *pooled_dev, const float *dv
     const int n_chunks = (int)((B + chunk - 1) / chunk);
     hipLaunchKernelGGL(pmx_critic_tail_wgrad_kernel, dim3(HID / 8, n_chunks), dim3(256), 0, st, (const __hip_bfloat16 *)dh, (const __hip_bfloat16 *)g,
                        pooled_dev, dvalue_dev, grad_dev, (int)B, (int)chunk, n_chunks == 1 ? 1 : 0);
-    pmx_last_rows_value = n_chunks > 1 ? n_chunks : 0;                 // (one chunk: the sums went straight to row 0)
-    if (n_chunks > 1 && !pmx_defer_sums_flag)
-        hipLaunchKernelGGL(pmx_heads_sum_rows_kernel, dim3((CT_FLOATS + 31) / 32), dim3(256), 0, st, grad_dev, n_chunks, (int)CT_FLOATS);
-    return hipGetLastError() == hipSuccess ? PMX_OK : PMX_ERR_HIP;
+    return pmx_finish_partial_rows(grad_dev, n_chunks > 1 ? n_chunks : 0, CT_FLOATS, st);     // (one chunk: the sums went straight to row 0)
 }

@@ -9,6 +9,7 @@
 #include <hip/hip_bf16.h>
 
 #include "../../include/pmx.h"
+#include "pmx_common.h"
 #include "pmx_device.h"
 
 // ---------------------------------------------------------------------------------------------------------------
@@ -181,7 +182,7 @@ extern "C" int pmx_gae(const float *rewards_dev, const float *values_dev, const 
     else
         hipLaunchKernelGGL(pmx_gae_wave_kernel, dim3(n), dim3(64), 0, st, rewards_dev, values_dev, dones_dev, last_value_dev, T, n,
                            gamma, lam, adv_dev, ret_dev);
-    return hipGetLastError() == hipSuccess ? PMX_OK : PMX_ERR_HIP;
+    return pmx_launch_rc();
 }
 
 // forced variants for tests / benchmarks: mode 0 = lane-per-series, 1 = wave-per-series
@@ -196,7 +197,7 @@ extern "C" int pmx_gae_mode(const float *rewards_dev, const float *values_dev, c
     else
         hipLaunchKernelGGL(pmx_gae_wave_kernel, dim3(n), dim3(64), 0, st, rewards_dev, values_dev, dones_dev, last_value_dev, T, n,
                            gamma, lam, adv_dev, ret_dev);
-    return hipGetLastError() == hipSuccess ? PMX_OK : PMX_ERR_HIP;
+    return pmx_launch_rc();
 }
 
 extern "C" int pmx_canonicalize_obs(const void *in_dev, void *out_dev, int32_t n, int32_t H, int32_t W, int32_t obs_dtype,
@@ -213,7 +214,7 @@ extern "C" int pmx_canonicalize_obs(const void *in_dev, void *out_dev, int32_t n
     case PMX_OBS_U8: hipLaunchKernelGGL(pmx_canon_kernel<uint8_t>, grid, block, 0, st, (const uint8_t *)in_dev, (uint8_t *)out_dev, total, H, W); break;
     default: return PMX_ERR_INVALID;
     }
-    return hipGetLastError() == hipSuccess ? PMX_OK : PMX_ERR_HIP;
+    return pmx_launch_rc();
 }
 
 extern "C" int pmx_merge_obs(const void *a_dev, const void *b_dev, void *out_dev, int32_t n, int32_t H, int32_t W, int32_t obs_dtype,
@@ -230,7 +231,7 @@ extern "C" int pmx_merge_obs(const void *a_dev, const void *b_dev, void *out_dev
     case PMX_OBS_U8: hipLaunchKernelGGL(pmx_merge_kernel<uint8_t>, grid, block, 0, st, (const uint8_t *)a_dev, (const uint8_t *)b_dev, (uint8_t *)out_dev, total, H * W); break;
     default: return PMX_ERR_INVALID;
     }
-    return hipGetLastError() == hipSuccess ? PMX_OK : PMX_ERR_HIP;
+    return pmx_launch_rc();
 }
 
 
@@ -274,7 +275,7 @@ extern "C" int pmx_colsum_bf16(const void *x_dev, int64_t rows, int32_t C, float
     const int RP = 256 / (C >> 3);
     hipLaunchKernelGGL(pmx_colsum_bf16_kernel, dim3(PMX_COLSUM_BLOCKS), dim3(256), (size_t)RP * C * sizeof(float), st,
                        (const __hip_bfloat16 *)x_dev, (long)rows, C, partial_dev);
-    return hipGetLastError() == hipSuccess ? PMX_OK : PMX_ERR_HIP;
+    return pmx_launch_rc();
 }
 
 
@@ -407,7 +408,7 @@ extern "C" int pmx_ln32_forward(const void *x, const void *a, const float *w, co
     else
         hipLaunchKernelGGL(pmx_ln32_fwd_kernel<__hip_bfloat16>, dim3(grid), dim3(256), 0, st, (const __hip_bfloat16 *)x, (const __hip_bfloat16 *)a, w, b,
                            (__hip_bfloat16 *)y, mean, rstd, (long)rows, eps);
-    return hipGetLastError() == hipSuccess ? PMX_OK : PMX_ERR_HIP;
+    return pmx_launch_rc();
 }
 
 // partial: [PMX_LN32_PARTIAL_ROWS][64] float32, fully overwritten: row k holds one wavefront's sums of dw (first 32) and db
@@ -424,7 +425,7 @@ extern "C" int pmx_ln32_backward(const void *x, const void *a, const void *dy, c
     else
         hipLaunchKernelGGL(pmx_ln32_bwd_kernel<__hip_bfloat16>, dim3(grid), dim3(256), 0, st, (const __hip_bfloat16 *)x, (const __hip_bfloat16 *)a,
                            (const __hip_bfloat16 *)dy, w, mean, rstd, (__hip_bfloat16 *)dz, partial, (long)rows);
-    return hipGetLastError() == hipSuccess ? PMX_OK : PMX_ERR_HIP;
+    return pmx_launch_rc();
 }
 
 
@@ -442,18 +443,6 @@ template <> __device__ __forceinline__ float gn_ld<__hip_bfloat16>(const __hip_b
 template <typename T> __device__ __forceinline__ void gn_st(T *p, float v);
 template <> __device__ __forceinline__ void gn_st<float>(float *p, float v) { *p = v; }
 template <> __device__ __forceinline__ void gn_st<__hip_bfloat16>(__hip_bfloat16 *p, float v) { *p = __float2bfloat16(v); }
-
-__device__ __forceinline__ float wave_sum(float v)
-{
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o);
-    return v;
-}
-__device__ __forceinline__ float gelu_f(float z) { return 0.5f * z * (1.0f + erff(z * 0.70710678118654752f)); }
-__device__ __forceinline__ float gelu_grad_f(float z)
-{
-    return 0.5f * (1.0f + erff(z * 0.70710678118654752f)) + z * 0.39894228040143268f * __expf(-0.5f * z * z);
-}
 
 template <typename T, int KMAX>
 __global__ __launch_bounds__(256) void pmx_gn8_gelu_fwd_kernel(const T *__restrict__ h, const T *__restrict__ res, const float *__restrict__ w,
@@ -498,7 +487,7 @@ __global__ __launch_bounds__(256) void pmx_gn8_gelu_fwd_kernel(const T *__restri
                 const size_t idx = base + (size_t)c * HW + e;
                 float z = (v[c][k] - mean) * wc + bc;
                 if (res) z += gn_ld<T>(res + idx);
-                gn_st<T>(y + idx, gelu_f(z));
+                gn_st<T>(y + idx, gelu_exact(z));
             }
         }
     }
@@ -534,7 +523,7 @@ __global__ __launch_bounds__(256) void pmx_gn8_gelu_bwd_kernel(const T *__restri
                 const float x = (gn_ld<T>(h + idx) - mean) * rstd;
                 float z = x * wc + bc;
                 if (res) z += gn_ld<T>(res + idx);
-                const float dz = gn_ld<T>(dy + idx) * gelu_grad_f(z);
+                const float dz = gn_ld<T>(dy + idx) * gelu_grad(z);
                 if (dres) gn_st<T>(dres + idx, dz);
                 sw += dz * x; sb += dz;
                 const float gg = dz * wc;
@@ -568,7 +557,7 @@ extern "C" int pmx_gn8_gelu_forward(const void *h, const void *res, const float 
 #define PMX_GN_FWD(T, K) hipLaunchKernelGGL((pmx_gn8_gelu_fwd_kernel<T, K>), dim3(grid), dim3(256), 0, st, (const T *)h, (const T *)res, w, b, (T *)y, mean, rstd, rows, groups, HW, eps)
     if (dtype == 0) { if (HW <= 192) PMX_GN_FWD(float, 3); else if (HW <= 448) PMX_GN_FWD(float, 7); else PMX_GN_FWD(float, 16); }
     else { if (HW <= 192) PMX_GN_FWD(__hip_bfloat16, 3); else if (HW <= 448) PMX_GN_FWD(__hip_bfloat16, 7); else PMX_GN_FWD(__hip_bfloat16, 16); }
-    return hipGetLastError() == hipSuccess ? PMX_OK : PMX_ERR_HIP;
+    return pmx_launch_rc();
 }
 
 // dh (and dres when res_dev is given) are written in full; partial [B * groups][8][2] float32 receives, per (sample, group)
@@ -586,7 +575,7 @@ extern "C" int pmx_gn8_gelu_backward(const void *h, const void *res, const void 
 #define PMX_GN_BWD(T, K) hipLaunchKernelGGL((pmx_gn8_gelu_bwd_kernel<T, K>), dim3(grid), dim3(256), 0, st, (const T *)h, (const T *)res, (const T *)dy, w, b, mean, rstd, (T *)dh, (T *)dres, partial, rows, groups, HW)
     if (dtype == 0) { if (HW <= 192) PMX_GN_BWD(float, 3); else if (HW <= 448) PMX_GN_BWD(float, 7); else PMX_GN_BWD(float, 16); }
     else { if (HW <= 192) PMX_GN_BWD(__hip_bfloat16, 3); else if (HW <= 448) PMX_GN_BWD(__hip_bfloat16, 7); else PMX_GN_BWD(__hip_bfloat16, 16); }
-    return hipGetLastError() == hipSuccess ? PMX_OK : PMX_ERR_HIP;
+    return pmx_launch_rc();
 }
 
 
@@ -601,11 +590,6 @@ extern "C" int pmx_gn8_gelu_backward(const void *h, const void *res, const void 
 //                                     contraction index (keys) may be enumerated in any order as long as the A operand
 //                                     (V^T, staged transposed in LDS) uses the same one -- no LDS round trip for P.
 // ---------------------------------------------------------------------------------------------------------------
-typedef __attribute__((ext_vector_type(8))) short pmx_bf16x8;
-typedef __attribute__((ext_vector_type(4))) float pmx_f32x4;
-typedef __attribute__((ext_vector_type(2))) float pmx_f32x2;
-typedef __attribute__((ext_vector_type(4))) short pmx_bf16x4;
-
 __device__ __forceinline__ short pmx_f2bf(float f)
 {
     const __hip_bfloat16 h = __float2bfloat16(f);
@@ -686,34 +670,34 @@ __global__ __launch_bounds__(512) void pmx_attn8_fwd2_kernel(const __hip_bfloat1
     const float bound = __builtin_sqrtf(fmaxf(knorm[2 * h], knorm[2 * h + 8]) * fmaxf(knorm[2 * h + 1], knorm[2 * h + 9])) * 1.0001f;
 
     const int g = lane >> 4, c = lane & 15;
-    const pmx_bf16x8 zero8 = { 0, 0, 0, 0, 0, 0, 0, 0 };
-    const pmx_f32x4 z4 = { 0.f, 0.f, 0.f, 0.f };
+    const bf16x8 zero8 = { 0, 0, 0, 0, 0, 0, 0, 0 };
+    const f32x4 z4 = { 0.f, 0.f, 0.f, 0.f };
     const int n_qt = (S + 15) >> 4, n_kp = S_pad >> 5;
     const float c2 = scale * 1.44269504088896341f;                  // raw score -> base-2 exponent
     const short *krow = Ks + (size_t)c * D;                                              // + kp * 32 * D (+ 16 * D)
     const short *vrow = Vt + (size_t)(c < D ? c : D) * S_pad + g * 4;                    // + kp * 32 (+ 16); rows >= 9 of the result are unused
     const int last_lo = S - (n_kp - 1) * 32 - g * 4;               // key index r (resp. 16 + r) of the last pair is real iff r < last_lo (- 16)
     const bool exact = bound * c2 > 44.0f;                          // (uniform over the head's two waves)
-    pmx_f32x2 real[4];                                              // 1 for the lane's real keys of the last pair, 0 for its padded ones
+    f32x2 real[4];                                              // 1 for the lane's real keys of the last pair, 0 for its padded ones
 #pragma unroll
     for (int i = 0; i < 4; ++i) {
         const int r0 = (i & 1) * 2 + (i >> 1) * 16;                 // e[2 i], e[2 i + 1] are keys r0, r0 + 1 (+ 4 g) of the pair
-        real[i] = pmx_f32x2{ r0 < last_lo ? 1.f : 0.f, r0 + 1 < last_lo ? 1.f : 0.f };
+        real[i] = f32x2{ r0 < last_lo ? 1.f : 0.f, r0 + 1 < last_lo ? 1.f : 0.f };
     }
     for (int qt = role; qt < n_qt; qt += 2) {
         const int q_row = qt * 16 + c;
-        pmx_bf16x8 qf = zero8;
-        if (g == 0 && q_row < S) qf = *reinterpret_cast<const pmx_bf16x8 *>(base + (size_t)q_row * row_stride + head_off);
+        bf16x8 qf = zero8;
+        if (g == 0 && q_row < S) qf = *reinterpret_cast<const bf16x8 *>(base + (size_t)q_row * row_stride + head_off);
         float mx = bound;
         if (exact) {
         // ---- exact path, pass 1: the largest raw score of each query ------------------------------------------------------
         mx = -3.0e38f;
 #pragma unroll 2
         for (int kp = 0; kp < n_kp - 1; ++kp) {
-            const pmx_bf16x8 k0 = *reinterpret_cast<const pmx_bf16x8 *>(krow + (size_t)kp * 32 * D);
-            const pmx_bf16x8 k1 = *reinterpret_cast<const pmx_bf16x8 *>(krow + (size_t)(kp * 32 + 16) * D);
-            const pmx_f32x4 s0 = __builtin_amdgcn_mfma_f32_16x16x32_bf16(k0, qf, z4, 0, 0, 0);
-            const pmx_f32x4 s1 = __builtin_amdgcn_mfma_f32_16x16x32_bf16(k1, qf, z4, 0, 0, 0);
+            const bf16x8 k0 = *reinterpret_cast<const bf16x8 *>(krow + (size_t)kp * 32 * D);
+            const bf16x8 k1 = *reinterpret_cast<const bf16x8 *>(krow + (size_t)(kp * 32 + 16) * D);
+            const f32x4 s0 = __builtin_amdgcn_mfma_f32_16x16x32_bf16(k0, qf, z4, 0, 0, 0);
+            const f32x4 s1 = __builtin_amdgcn_mfma_f32_16x16x32_bf16(k1, qf, z4, 0, 0, 0);
             mx = __builtin_elementwise_maximum(__builtin_elementwise_maximum(s0[0], s0[1]), mx);
             mx = __builtin_elementwise_maximum(__builtin_elementwise_maximum(s0[2], s0[3]), mx);
             mx = __builtin_elementwise_maximum(__builtin_elementwise_maximum(s1[0], s1[1]), mx);
@@ -721,10 +705,10 @@ __global__ __launch_bounds__(512) void pmx_attn8_fwd2_kernel(const __hip_bfloat1
         }
         {   // the last pair may hold padded keys (zero K rows: score 0): they must not raise the reference
             const int kp = n_kp - 1;
-            const pmx_bf16x8 k0 = *reinterpret_cast<const pmx_bf16x8 *>(krow + (size_t)kp * 32 * D);
-            const pmx_bf16x8 k1 = *reinterpret_cast<const pmx_bf16x8 *>(krow + (size_t)(kp * 32 + 16) * D);
-            const pmx_f32x4 s0 = __builtin_amdgcn_mfma_f32_16x16x32_bf16(k0, qf, z4, 0, 0, 0);
-            const pmx_f32x4 s1 = __builtin_amdgcn_mfma_f32_16x16x32_bf16(k1, qf, z4, 0, 0, 0);
+            const bf16x8 k0 = *reinterpret_cast<const bf16x8 *>(krow + (size_t)kp * 32 * D);
+            const bf16x8 k1 = *reinterpret_cast<const bf16x8 *>(krow + (size_t)(kp * 32 + 16) * D);
+            const f32x4 s0 = __builtin_amdgcn_mfma_f32_16x16x32_bf16(k0, qf, z4, 0, 0, 0);
+            const f32x4 s1 = __builtin_amdgcn_mfma_f32_16x16x32_bf16(k1, qf, z4, 0, 0, 0);
 #pragma unroll
             for (int r = 0; r < 4; ++r) {
                 mx = __builtin_elementwise_maximum(r < last_lo ? s0[r] : -3.0e38f, mx);
@@ -735,9 +719,9 @@ __global__ __launch_bounds__(512) void pmx_attn8_fwd2_kernel(const __hip_bfloat1
         mx = __builtin_elementwise_maximum(mx, __shfl_xor(mx, 32));
         }
         // ---- pass 2: O^T (+ the row sums in row 8) against the fixed reference ---------------------------------------------
-        const pmx_f32x4 negm = { -mx, -mx, -mx, -mx };
-        pmx_f32x4 o = z4;
-        pmx_f32x2 ls[2] = { { 0.f, 0.f }, { 0.f, 0.f } };          // the lane's sum of UNROUNDED probabilities, for the log-sum-exp
+        const f32x4 negm = { -mx, -mx, -mx, -mx };
+        f32x4 o = z4;
+        f32x2 ls[2] = { { 0.f, 0.f }, { 0.f, 0.f } };          // the lane's sum of UNROUNDED probabilities, for the log-sum-exp
         // mode 0: a pair of key tiles without padding.  The last pair may hold padded keys (zero K rows, zero V^T columns INCLUDING the
         // row of ones: whatever their probability, they add nothing to O or to its normaliser).  Mode 2 (reference = the bound, so
         // the padded keys' exponent -bound c is <= 0): only the exact row sum must leave them out -- a multiply-add with the lane's 0 / 1
@@ -745,13 +729,13 @@ __global__ __launch_bounds__(512) void pmx_attn8_fwd2_kernel(const __hip_bfloat1
         // probabilities are set to zero by compares, as everywhere before.
         auto tile = [&](int kp, auto mode_c) {
             constexpr int mode = decltype(mode_c)::value;
-            const pmx_bf16x8 k0 = *reinterpret_cast<const pmx_bf16x8 *>(krow + (size_t)kp * 32 * D);
-            const pmx_bf16x8 k1 = *reinterpret_cast<const pmx_bf16x8 *>(krow + (size_t)(kp * 32 + 16) * D);
-            const pmx_f32x4 s0 = __builtin_amdgcn_mfma_f32_16x16x32_bf16(k0, qf, negm, 0, 0, 0);     // s - m
-            const pmx_f32x4 s1 = __builtin_amdgcn_mfma_f32_16x16x32_bf16(k1, qf, negm, 0, 0, 0);
-            const pmx_f32x2 cc = { c2, c2 };
-            const pmx_f32x2 x[4] = { pmx_f32x2{ s0[0], s0[1] } * cc, pmx_f32x2{ s0[2], s0[3] } * cc, pmx_f32x2{ s1[0], s1[1] } * cc,
-                                     pmx_f32x2{ s1[2], s1[3] } * cc };                            // (packed multiplies)
+            const bf16x8 k0 = *reinterpret_cast<const bf16x8 *>(krow + (size_t)kp * 32 * D);
+            const bf16x8 k1 = *reinterpret_cast<const bf16x8 *>(krow + (size_t)(kp * 32 + 16) * D);
+            const f32x4 s0 = __builtin_amdgcn_mfma_f32_16x16x32_bf16(k0, qf, negm, 0, 0, 0);     // s - m
+            const f32x4 s1 = __builtin_amdgcn_mfma_f32_16x16x32_bf16(k1, qf, negm, 0, 0, 0);
+            const f32x2 cc = { c2, c2 };
+            const f32x2 x[4] = { f32x2{ s0[0], s0[1] } * cc, f32x2{ s0[2], s0[3] } * cc, f32x2{ s1[0], s1[1] } * cc,
+                                     f32x2{ s1[2], s1[3] } * cc };                            // (packed multiplies)
             float e[8];
 #pragma unroll
             for (int r = 0; r < 8; ++r) e[r] = __builtin_amdgcn_exp2f(x[r >> 1][r & 1]);
@@ -764,19 +748,19 @@ __global__ __launch_bounds__(512) void pmx_attn8_fwd2_kernel(const __hip_bfloat1
             }
             if constexpr (mode == 2) {
 #pragma unroll
-                for (int i = 0; i < 4; ++i) ls[i & 1] = __builtin_elementwise_fma(pmx_f32x2{ e[2 * i], e[2 * i + 1] }, real[i], ls[i & 1]);
+                for (int i = 0; i < 4; ++i) ls[i & 1] = __builtin_elementwise_fma(f32x2{ e[2 * i], e[2 * i + 1] }, real[i], ls[i & 1]);
             } else {
 #pragma unroll
-                for (int i = 0; i < 4; ++i) ls[i & 1] += pmx_f32x2{ e[2 * i], e[2 * i + 1] };
+                for (int i = 0; i < 4; ++i) ls[i & 1] += f32x2{ e[2 * i], e[2 * i + 1] };
             }
-            pmx_bf16x8 pf;
+            bf16x8 pf;
 #pragma unroll
             for (int r = 0; r < 8; ++r) pf[r] = pmx_f2bf(e[r]);
             // A = V^T (+ ones): row c, k-slot j -> key kp*32 + 4g + j (j < 4), kp*32 + 16 + 4g + (j-4): the order of pf's slots
             const uint2 lo = *reinterpret_cast<const uint2 *>(vrow + kp * 32);
             const uint2 hi = *reinterpret_cast<const uint2 *>(vrow + kp * 32 + 16);
             const uint4 both = make_uint4(lo.x, lo.y, hi.x, hi.y);
-            o = __builtin_amdgcn_mfma_f32_16x16x32_bf16(*reinterpret_cast<const pmx_bf16x8 *>(&both), pf, o, 0, 0, 0);
+            o = __builtin_amdgcn_mfma_f32_16x16x32_bf16(*reinterpret_cast<const bf16x8 *>(&both), pf, o, 0, 0, 0);
         };
 #pragma unroll 2
         for (int kp = 0; kp < n_kp - 1; ++kp) tile(kp, std::integral_constant<int, 0>{});
@@ -813,18 +797,12 @@ extern "C" int pmx_attn8_forward_layout(const void *qkv_dev, void *out_dev, floa
     if (B == 0) return PMX_OK;
     hipStream_t st = reinterpret_cast<hipStream_t>(stream);
     const int S_pad = (S + 31) & ~31;
-    int cur_dev = 0;
-    if (hipGetDevice(&cur_dev) != hipSuccess || cur_dev < 0 || cur_dev >= 64) return PMX_ERR_HIP;
     const size_t lds = (size_t)4 * (8 + 9) * S_pad * sizeof(short) + 16 * sizeof(float);
-    static bool attr_set_dev[64] = {};          // the attribute belongs to the function ON THE CURRENT DEVICE
-    if (lds > 65536 && !attr_set_dev[cur_dev]) {
-        if (hipFuncSetAttribute(reinterpret_cast<const void *>(pmx_attn8_fwd2_kernel), hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024) != hipSuccess)
-            return PMX_ERR_HIP;
-        attr_set_dev[cur_dev] = true;
-    }
+    int rc = pmx_allow_lds(reinterpret_cast<const void *>(pmx_attn8_fwd2_kernel), lds, PMX_LDS_PER_CU);
+    if (rc) return rc;
     hipLaunchKernelGGL(pmx_attn8_fwd2_kernel, dim3(B), dim3(512), lds, st, (const __hip_bfloat16 *)qkv_dev, (__hip_bfloat16 *)out_dev, lse_dev, S, B,
                        0.35355339059327379f /* 1/sqrt(8) */, batch_major ? 1 : 0);
-    return hipGetLastError() == hipSuccess ? PMX_OK : PMX_ERR_HIP;
+    return pmx_launch_rc();
 }
 
 
@@ -900,38 +878,38 @@ __global__ __launch_bounds__(512) void pmx_attn8_bwd_kernel(const __hip_bfloat16
     __syncthreads();
 
     const int g = lane >> 4, c = lane & 15;
-    const pmx_bf16x8 zero8 = { 0, 0, 0, 0, 0, 0, 0, 0 };
-    const pmx_f32x4 z4 = { 0.f, 0.f, 0.f, 0.f };
+    const bf16x8 zero8 = { 0, 0, 0, 0, 0, 0, 0, 0 };
+    const f32x4 z4 = { 0.f, 0.f, 0.f, 0.f };
     const int n_t = (S + 15) >> 4, n_p = S_pad >> 5;
     const float c2 = scale * 1.44269504088896341f;     // scores -> base-2 exponents with one fma: exp2(s * c2 - lse2)
     short *dbase = reinterpret_cast<short *>(dqkv);
 
-    auto row8 = [&](const short *src, size_t stride, size_t off, int r) -> pmx_bf16x8 {   // 8 bf16 of row r for lanes of group 0
-        pmx_bf16x8 v = zero8;
-        if (g == 0 && r < S) v = *reinterpret_cast<const pmx_bf16x8 *>(src + (size_t)r * stride + off);
+    auto row8 = [&](const short *src, size_t stride, size_t off, int r) -> bf16x8 {   // 8 bf16 of row r for lanes of group 0
+        bf16x8 v = zero8;
+        if (g == 0 && r < S) v = *reinterpret_cast<const bf16x8 *>(src + (size_t)r * stride + off);
         return v;
     };
     // the two operands of a score product, with the key mask in k-slot 8 (see above)
     // (lane group 1 never loads: its constant does not wait for the row that group 0 requested a tile ahead)
-    auto qry8 = [&](int r) -> pmx_bf16x8 {
-        pmx_bf16x8 v = zero8;
+    auto qry8 = [&](int r) -> bf16x8 {
+        bf16x8 v = zero8;
         if (g == 1) v[0] = PMX_BF16_ONE;
-        if (g == 0 && r < S) v = *reinterpret_cast<const pmx_bf16x8 *>(base + (size_t)r * row_stride + head_off);
+        if (g == 0 && r < S) v = *reinterpret_cast<const bf16x8 *>(base + (size_t)r * row_stride + head_off);
         return v;
     };
-    auto key8 = [&](int r) -> pmx_bf16x8 {
-        pmx_bf16x8 v = zero8;
+    auto key8 = [&](int r) -> bf16x8 {
+        bf16x8 v = zero8;
         if (g == 1 && r >= S) v[0] = PMX_BF16_KEY_OFF;
-        if (g == 0 && r < S) v = *reinterpret_cast<const pmx_bf16x8 *>(base + (size_t)r * row_stride + head_off + E);
+        if (g == 0 && r < S) v = *reinterpret_cast<const bf16x8 *>(base + (size_t)r * row_stride + head_off + E);
         return v;
     };
-    auto tfrag = [&](const short *T, int pair) -> pmx_bf16x8 {       // A fragment [row d = c][k-slot j]: index 32*pair + 4g + j / + 16
-        pmx_bf16x8 v = zero8;
+    auto tfrag = [&](const short *T, int pair) -> bf16x8 {       // A fragment [row d = c][k-slot j]: index 32*pair + 4g + j / + 16
+        bf16x8 v = zero8;
         if (c < D) {
             const short *p = T + (size_t)c * S_pad + pair * 32 + g * 4;
             const uint2 lo = *reinterpret_cast<const uint2 *>(p), hi = *reinterpret_cast<const uint2 *>(p + 16);
             const uint4 both = make_uint4(lo.x, lo.y, hi.x, hi.y);
-            v = *reinterpret_cast<const pmx_bf16x8 *>(&both);
+            v = *reinterpret_cast<const bf16x8 *>(&both);
         }
         return v;
     };
@@ -940,26 +918,26 @@ __global__ __launch_bounds__(512) void pmx_attn8_bwd_kernel(const __hip_bfloat16
     if (role == 0)
     for (int qt = 0; qt < n_t; ++qt) {
         const int q_row = qt * 16 + c;
-        const pmx_bf16x8 qf = qry8(q_row);
-        const pmx_bf16x8 dof = row8(dobase, orow, ohead, q_row);
+        const bf16x8 qf = qry8(q_row);
+        const bf16x8 dof = row8(dobase, orow, ohead, q_row);
         const float ls = lse_s[q_row < S_pad ? q_row : 0], dl = delta_s[q_row < S_pad ? q_row : 0];
-        pmx_f32x4 dq = z4;
+        f32x4 dq = z4;
         // software pipeline: the row fragments of key pair kp + 1 are requested before pair kp is consumed (the loads are
         // L2 hits several hundred cycles away and the compiler does not hoist them across the loop by itself)
-        pmx_bf16x8 k0n = key8(c), k1n = key8(16 + c);
-        pmx_bf16x8 v0n = row8(base, row_stride, head_off + 2 * E, c), v1n = row8(base, row_stride, head_off + 2 * E, 16 + c);
+        bf16x8 k0n = key8(c), k1n = key8(16 + c);
+        bf16x8 v0n = row8(base, row_stride, head_off + 2 * E, c), v1n = row8(base, row_stride, head_off + 2 * E, 16 + c);
         for (int kp = 0; kp < n_p; ++kp) {
-            const pmx_bf16x8 k0 = k0n, k1 = k1n, v0 = v0n, v1 = v1n;
+            const bf16x8 k0 = k0n, k1 = k1n, v0 = v0n, v1 = v1n;
             if (kp + 1 < n_p) {
                 k0n = key8(kp * 32 + 32 + c); k1n = key8(kp * 32 + 48 + c);
                 v0n = row8(base, row_stride, head_off + 2 * E, kp * 32 + 32 + c); v1n = row8(base, row_stride, head_off + 2 * E, kp * 32 + 48 + c);
             }
-            const pmx_f32x4 s0 = __builtin_amdgcn_mfma_f32_16x16x32_bf16(k0, qf, z4, 0, 0, 0);
-            const pmx_f32x4 s1 = __builtin_amdgcn_mfma_f32_16x16x32_bf16(k1, qf, z4, 0, 0, 0);
-            const pmx_f32x4 p0 = __builtin_amdgcn_mfma_f32_16x16x32_bf16(v0, dof, z4, 0, 0, 0);
-            const pmx_f32x4 p1 = __builtin_amdgcn_mfma_f32_16x16x32_bf16(v1, dof, z4, 0, 0, 0);
+            const f32x4 s0 = __builtin_amdgcn_mfma_f32_16x16x32_bf16(k0, qf, z4, 0, 0, 0);
+            const f32x4 s1 = __builtin_amdgcn_mfma_f32_16x16x32_bf16(k1, qf, z4, 0, 0, 0);
+            const f32x4 p0 = __builtin_amdgcn_mfma_f32_16x16x32_bf16(v0, dof, z4, 0, 0, 0);
+            const f32x4 p1 = __builtin_amdgcn_mfma_f32_16x16x32_bf16(v1, dof, z4, 0, 0, 0);
             // (a padded key -- accumulator row 4g + r of the last pair -- has score -2^100: e and its dS are 0)
-            pmx_bf16x8 dsf;
+            bf16x8 dsf;
 #pragma unroll
             for (int r = 0; r < 4; ++r) {
                 const float e0 = __builtin_amdgcn_exp2f(__builtin_fmaf(s0[r], c2, -ls));
@@ -980,23 +958,23 @@ __global__ __launch_bounds__(512) void pmx_attn8_bwd_kernel(const __hip_bfloat16
     if (role == 1)
     for (int kt = 0; kt < n_t; ++kt) {
         const int k_row = kt * 16 + c;
-        const pmx_bf16x8 kf = key8(k_row);
-        const pmx_bf16x8 vf = row8(base, row_stride, head_off + 2 * E, k_row);
-        pmx_f32x4 dk = z4, dv = z4;
-        pmx_bf16x8 q0n = qry8(c), q1n = qry8(16 + c);
-        pmx_bf16x8 d0n = row8(dobase, orow, ohead, c), d1n = row8(dobase, orow, ohead, 16 + c);
+        const bf16x8 kf = key8(k_row);
+        const bf16x8 vf = row8(base, row_stride, head_off + 2 * E, k_row);
+        f32x4 dk = z4, dv = z4;
+        bf16x8 q0n = qry8(c), q1n = qry8(16 + c);
+        bf16x8 d0n = row8(dobase, orow, ohead, c), d1n = row8(dobase, orow, ohead, 16 + c);
         for (int qp = 0; qp < n_p; ++qp) {
-            const pmx_bf16x8 q0 = q0n, q1 = q1n, d0 = d0n, d1 = d1n;
+            const bf16x8 q0 = q0n, q1 = q1n, d0 = d0n, d1 = d1n;
             if (qp + 1 < n_p) {
                 q0n = qry8(qp * 32 + 32 + c); q1n = qry8(qp * 32 + 48 + c);
                 d0n = row8(dobase, orow, ohead, qp * 32 + 32 + c); d1n = row8(dobase, orow, ohead, qp * 32 + 48 + c);
             }
             // S = Q . K^T: rows = queries (4g + r), column = key c
-            const pmx_f32x4 s0 = __builtin_amdgcn_mfma_f32_16x16x32_bf16(q0, kf, z4, 0, 0, 0);
-            const pmx_f32x4 s1 = __builtin_amdgcn_mfma_f32_16x16x32_bf16(q1, kf, z4, 0, 0, 0);
-            const pmx_f32x4 p0 = __builtin_amdgcn_mfma_f32_16x16x32_bf16(d0, vf, z4, 0, 0, 0);
-            const pmx_f32x4 p1 = __builtin_amdgcn_mfma_f32_16x16x32_bf16(d1, vf, z4, 0, 0, 0);
-            pmx_bf16x8 pf, dsf;
+            const f32x4 s0 = __builtin_amdgcn_mfma_f32_16x16x32_bf16(q0, kf, z4, 0, 0, 0);
+            const f32x4 s1 = __builtin_amdgcn_mfma_f32_16x16x32_bf16(q1, kf, z4, 0, 0, 0);
+            const f32x4 p0 = __builtin_amdgcn_mfma_f32_16x16x32_bf16(d0, vf, z4, 0, 0, 0);
+            const f32x4 p1 = __builtin_amdgcn_mfma_f32_16x16x32_bf16(d1, vf, z4, 0, 0, 0);
+            bf16x8 pf, dsf;
 #pragma unroll
             for (int r = 0; r < 4; ++r) {
                 const int qa = qp * 32 + g * 4 + r, qb = qa + 16;
@@ -1098,33 +1076,27 @@ __global__ __launch_bounds__(256 * QS) void pmx_attn8_bwd_fused_kernel(const __h
     }
 
     const int g = lane >> 4, c = lane & 15;
-    const pmx_bf16x8 zero8 = { 0, 0, 0, 0, 0, 0, 0, 0 };
-    const pmx_f32x4 z4 = { 0.f, 0.f, 0.f, 0.f };
+    const bf16x8 zero8 = { 0, 0, 0, 0, 0, 0, 0, 0 };
+    const f32x4 z4 = { 0.f, 0.f, 0.f, 0.f };
     const int n_t = (S + 15) >> 4;
     const float c2 = scale * 1.44269504088896341f;
     short *dbase = reinterpret_cast<short *>(dqkv);
-    auto row8 = [&](const short *src, size_t stride, size_t off, int r) -> pmx_bf16x8 {
-        pmx_bf16x8 v = zero8;
-        if (g == 0 && r < S) v = *reinterpret_cast<const pmx_bf16x8 *>(src + (size_t)r * stride + off);
+    auto row8 = [&](const short *src, size_t stride, size_t off, int r) -> bf16x8 {
+        bf16x8 v = zero8;
+        if (g == 0 && r < S) v = *reinterpret_cast<const bf16x8 *>(src + (size_t)r * stride + off);
         return v;
     };
     // A fragment [row d][k-slot j] of a transposed array: rows 8..15 of the operand only feed rows 8..15 of the product, which
     // nobody reads, so those lanes simply repeat rows 0..7 (no exec mask, no zero fill in the loop)
-    auto tfrag = [&](const short *T, int pair) -> pmx_bf16x8 {
+    auto tfrag = [&](const short *T, int pair) -> bf16x8 {
         const short *p = T + (size_t)(c & (D - 1)) * S_pad + pair * 32 + g * 4;
         const uint2 lo = *reinterpret_cast<const uint2 *>(p), hi = *reinterpret_cast<const uint2 *>(p + 16);
         const uint4 both = make_uint4(lo.x, lo.y, hi.x, hi.y);
-        return *reinterpret_cast<const pmx_bf16x8 *>(&both);
-    };
-    auto pack2bf = [](float x, float y) -> uint32_t {             // one v_cvt_pk_bf16_f32
-        typedef __attribute__((ext_vector_type(2))) float f2;
-        typedef __attribute__((ext_vector_type(2))) __bf16 b2;
-        const f2 f = {x, y};
-        return __builtin_bit_cast(uint32_t, __builtin_convertvector(f, b2));
+        return *reinterpret_cast<const bf16x8 *>(&both);
     };
     const int qp0 = role * NQP;                                     // this wave's query pairs: qp0 .. qp0 + NQP - 1 (those < NPF)
-    pmx_bf16x8 qr[2 * NQP], dr[QS > 1 ? 1 : 2 * NQP];
-    pmx_f32x4 dq[2 * NQP];
+    bf16x8 qr[2 * NQP], dr[QS > 1 ? 1 : 2 * NQP];
+    f32x4 dq[2 * NQP];
 #pragma unroll
     for (int t = 0; t < 2 * NQP; ++t) {
         qr[t] = row8(base, row_stride, head_off, (2 * qp0 + t) * 16 + c);       // (rows past the sequence read as zero)
@@ -1138,21 +1110,21 @@ __global__ __launch_bounds__(256 * QS) void pmx_attn8_bwd_fused_kernel(const __h
     // The K / V rows of a key tile come from global memory and its dK / dV rows go back there; loads and stores share one in-order
     // counter, so rows requested at the top of a tile would wait behind the previous tile's stores (a full write round trip per
     // tile).  They are requested one tile AHEAD, in front of those stores.
-    pmx_bf16x8 kf_n = row8(base, row_stride, head_off + E, c), vf_n = row8(base, row_stride, head_off + 2 * E, c);
+    bf16x8 kf_n = row8(base, row_stride, head_off + E, c), vf_n = row8(base, row_stride, head_off + 2 * E, c);
     for (int kt = 0; kt < n_t; ++kt) {
         const int k_row = kt * 16 + c;
         // The lane's key column.  A padded key (zero K row: S' = -lse / c, whose exponential overflows for lse < -88 nats) gets
         // -2^100 added to every exponent by the multiply-add that scales the score: p = 0 and dS = 0 * -delta = 0 exactly.
         const float koff = k_row < S ? 0.f : PMX_KEY_OFF;
-        const pmx_bf16x8 kf = kf_n, vf = vf_n;
+        const bf16x8 kf = kf_n, vf = vf_n;
         if (kt + 1 < n_t) {
             kf_n = row8(base, row_stride, head_off + E, k_row + 16);
             vf_n = row8(base, row_stride, head_off + 2 * E, k_row + 16);
         }
         // A operand of dQ^T += K^T . dS^T for this key tile: row d = c, k-slot (g, j) = key 16 kt + 8 g + j (groups 2, 3: none)
-        pmx_bf16x8 ka = zero8;
-        if (c < D && g < 2) ka = *reinterpret_cast<const pmx_bf16x8 *>(Kt + (size_t)c * S_pad + kt * 16 + 8 * g);
-        pmx_f32x4 dk = z4, dv = z4;
+        bf16x8 ka = zero8;
+        if (c < D && g < 2) ka = *reinterpret_cast<const bf16x8 *>(Kt + (size_t)c * S_pad + kt * 16 + 8 * g);
+        f32x4 dk = z4, dv = z4;
         // The pairs of a key tile as a SOFTWARE PIPELINE.  One pair is a chain  operand reads -> score products -> exponentials ->
         // dV / dK products, dS to the staging rows -> transposing reads -> dQ products, and with two waves per SIMD nothing else
         // covers its three LDS round trips (the kernel sat at ~50 % vector-ALU issue).  So the steps of consecutive pairs are
@@ -1160,19 +1132,19 @@ __global__ __launch_bounds__(256 * QS) void pmx_attn8_bwd_fused_kernel(const __h
         // compiler from re-serialising them:
         //   [reads j+1 | fragment reads j] [exponentials j] [dV, dK products j; dS j -> staging; transposing reads j]
         //   [score products j+1] [dQ products j]
-        struct Ops { pmx_f32x4 nl0, nl1, nd0, nd1; pmx_bf16x8 d0, d1; };
-        struct Sc { pmx_f32x4 s0, s1, p0, p1; };
+        struct Ops { f32x4 nl0, nl1, nd0, nd1; bf16x8 d0, d1; };
+        struct Sc { f32x4 s0, s1, p0, p1; };
         auto pair_live = [&](int j) { return !(QS > 1 && NQP * QS > NPF && j == NQP - 1 && qp0 + j >= NPF); };   // wave-uniform: the last
                                                                           // wave owns one pair less (run-time only for j = NQP - 1)
         auto read_ops = [&](int j) -> Ops {
             const int qp = qp0 + j;
             Ops o;
             // (accumulator row r of lane group g is query 32 qp + 4 g + r, resp. + 16: four consecutive floats each)
-            o.nl0 = *reinterpret_cast<const pmx_f32x4 *>(lse_s + qp * 32 + g * 4), o.nl1 = *reinterpret_cast<const pmx_f32x4 *>(lse_s + qp * 32 + 16 + g * 4);
-            o.nd0 = *reinterpret_cast<const pmx_f32x4 *>(delta_s + qp * 32 + g * 4), o.nd1 = *reinterpret_cast<const pmx_f32x4 *>(delta_s + qp * 32 + 16 + g * 4);
+            o.nl0 = *reinterpret_cast<const f32x4 *>(lse_s + qp * 32 + g * 4), o.nl1 = *reinterpret_cast<const f32x4 *>(lse_s + qp * 32 + 16 + g * 4);
+            o.nd0 = *reinterpret_cast<const f32x4 *>(delta_s + qp * 32 + g * 4), o.nd1 = *reinterpret_cast<const f32x4 *>(delta_s + qp * 32 + 16 + g * 4);
             if (QS > 1) {
-                o.d0 = *reinterpret_cast<const pmx_bf16x8 *>(dOr_lane + (size_t)(qp * 32) * D);
-                o.d1 = *reinterpret_cast<const pmx_bf16x8 *>(dOr_lane + (size_t)(qp * 32 + 16) * D);
+                o.d0 = *reinterpret_cast<const bf16x8 *>(dOr_lane + (size_t)(qp * 32) * D);
+                o.d1 = *reinterpret_cast<const bf16x8 *>(dOr_lane + (size_t)(qp * 32 + 16) * D);
             } else {
                 o.d0 = dr[QS > 1 ? 0 : 2 * j], o.d1 = dr[QS > 1 ? 0 : 2 * j + 1];
             }
@@ -1195,7 +1167,7 @@ __global__ __launch_bounds__(256 * QS) void pmx_attn8_bwd_fused_kernel(const __h
             // ---- reads for the next pair's score products and this pair's transposed fragments, then this pair's exponentials
             Ops nxt_ops;
             if (more) nxt_ops = read_ops(j + 1);
-            const pmx_bf16x8 fo = tfrag(dOt, qp), fq = tfrag(Qt, qp);
+            const bf16x8 fo = tfrag(dOt, qp), fq = tfrag(Qt, qp);
             float e0[4], e1[4];
 #pragma unroll
             for (int r = 0; r < 4; ++r) {
@@ -1203,10 +1175,10 @@ __global__ __launch_bounds__(256 * QS) void pmx_attn8_bwd_fused_kernel(const __h
                 e1[r] = __builtin_amdgcn_exp2f(__builtin_fmaf(cur.s1[r], c2, koff));
             }
             // probabilities and dS as bf16 pairs: slots 0..3 = queries 4g + r of the first tile of the pair, 4..7 = of the second
-            const uint4 pw = make_uint4(pack2bf(e0[0], e0[1]), pack2bf(e0[2], e0[3]), pack2bf(e1[0], e1[1]), pack2bf(e1[2], e1[3]));
-            const uint4 dw = make_uint4(pack2bf(e0[0] * cur.p0[0], e0[1] * cur.p0[1]), pack2bf(e0[2] * cur.p0[2], e0[3] * cur.p0[3]),
-                                        pack2bf(e1[0] * cur.p1[0], e1[1] * cur.p1[1]), pack2bf(e1[2] * cur.p1[2], e1[3] * cur.p1[3]));
-            const pmx_bf16x8 pf = *reinterpret_cast<const pmx_bf16x8 *>(&pw), dsf = *reinterpret_cast<const pmx_bf16x8 *>(&dw);
+            const uint4 pw = make_uint4(bf_pack(e0[0], e0[1]), bf_pack(e0[2], e0[3]), bf_pack(e1[0], e1[1]), bf_pack(e1[2], e1[3]));
+            const uint4 dw = make_uint4(bf_pack(e0[0] * cur.p0[0], e0[1] * cur.p0[1]), bf_pack(e0[2] * cur.p0[2], e0[3] * cur.p0[3]),
+                                        bf_pack(e1[0] * cur.p1[0], e1[1] * cur.p1[1]), bf_pack(e1[2] * cur.p1[2], e1[3] * cur.p1[3]));
+            const bf16x8 pf = *reinterpret_cast<const bf16x8 *>(&pw), dsf = *reinterpret_cast<const bf16x8 *>(&dw);
             __builtin_amdgcn_sched_barrier(0);
             // ---- dV / dK products; dS of the tile as [key c][queries 4g .. 4g+3 | 16 + 4g ..] -> staging rows 0..15 (a padded key's
             // column is exactly 0, see koff); the transposing reads are issued right behind the write.  Write, reads and the next
@@ -1216,13 +1188,13 @@ __global__ __launch_bounds__(256 * QS) void pmx_attn8_bwd_fused_kernel(const __h
             dk = __builtin_amdgcn_mfma_f32_16x16x32_bf16(fq, dsf, dk, 0, 0, 0);
             *reinterpret_cast<uint2 *>(stg + c * TROW + (4 * g) * 2) = make_uint2(dw.x, dw.y);
             *reinterpret_cast<uint2 *>(stg + c * TROW + (16 + 4 * g) * 2) = make_uint2(dw.z, dw.w);
-            pmx_bf16x8 bT[2];
+            bf16x8 bT[2];
 #pragma unroll
             for (int half = 0; half < 2; ++half) {
                 const char *a0 = stg + (8 * g + tr_row) * TROW + half * 32 + tr_pc * 8;
-                const pmx_bf16x4 lo = __builtin_amdgcn_ds_read_tr16_b64_v4i16((pmx_bf16x4 __attribute__((address_space(3))) *)(a0));
-                const pmx_bf16x4 hi = __builtin_amdgcn_ds_read_tr16_b64_v4i16((pmx_bf16x4 __attribute__((address_space(3))) *)(a0 + 4 * TROW));
-                bT[half] = pmx_bf16x8{ lo[0], lo[1], lo[2], lo[3], hi[0], hi[1], hi[2], hi[3] };
+                const bf16x4 lo = __builtin_amdgcn_ds_read_tr16_b64_v4i16((bf16x4 __attribute__((address_space(3))) *)(a0));
+                const bf16x4 hi = __builtin_amdgcn_ds_read_tr16_b64_v4i16((bf16x4 __attribute__((address_space(3))) *)(a0 + 4 * TROW));
+                bT[half] = bf16x8{ lo[0], lo[1], lo[2], lo[3], hi[0], hi[1], hi[2], hi[3] };
             }
             __builtin_amdgcn_sched_barrier(0);
             // ---- the next pair's score products run while the transposing reads come back
@@ -1239,13 +1211,13 @@ __global__ __launch_bounds__(256 * QS) void pmx_attn8_bwd_fused_kernel(const __h
             // tile kt + 2 is written only after barrier kt + 1, which the reader reaches after its reads of tile kt.
             float *slot = reinterpret_cast<float *>(xch + (size_t)(kt & 1) * XCH);
             if (role == 1 && g < 2) {
-                *reinterpret_cast<pmx_f32x4 *>(slot + ((0 * 2 + g) * 16 + c) * 4) = dk;
-                *reinterpret_cast<pmx_f32x4 *>(slot + ((1 * 2 + g) * 16 + c) * 4) = dv;
+                *reinterpret_cast<f32x4 *>(slot + ((0 * 2 + g) * 16 + c) * 4) = dk;
+                *reinterpret_cast<f32x4 *>(slot + ((1 * 2 + g) * 16 + c) * 4) = dv;
             }
             __syncthreads();
             if (role == 0 && g < 2) {
-                const pmx_f32x4 a = *reinterpret_cast<const pmx_f32x4 *>(slot + ((0 * 2 + g) * 16 + c) * 4);
-                const pmx_f32x4 e = *reinterpret_cast<const pmx_f32x4 *>(slot + ((1 * 2 + g) * 16 + c) * 4);
+                const f32x4 a = *reinterpret_cast<const f32x4 *>(slot + ((0 * 2 + g) * 16 + c) * 4);
+                const f32x4 e = *reinterpret_cast<const f32x4 *>(slot + ((1 * 2 + g) * 16 + c) * 4);
 #pragma unroll
                 for (int r = 0; r < 4; ++r) { dk[r] += a[r]; dv[r] += e[r]; }
             }
@@ -1284,39 +1256,28 @@ extern "C" int pmx_attn8_backward_layout(const void *qkv_dev, const void *out_de
     hipStream_t st = reinterpret_cast<hipStream_t>(stream);
     const int S_pad = (S + 31) & ~31;
     const size_t lds = (size_t)4 * ((size_t)3 * 8 * S_pad * sizeof(short) + (size_t)2 * S_pad * sizeof(float));
-    static bool attr_set_dev[64] = {};          // the attribute belongs to the function ON THE CURRENT DEVICE
-    int cur_dev = 0;
-    if (hipGetDevice(&cur_dev) != hipSuccess || cur_dev < 0 || cur_dev >= 64) return PMX_ERR_HIP;
-    bool &attr_set = attr_set_dev[cur_dev];
-    if (lds > 65536 && !attr_set) {
-        if (hipFuncSetAttribute(reinterpret_cast<const void *>(pmx_attn8_bwd_kernel), hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024) != hipSuccess)
-            return PMX_ERR_HIP;
-        attr_set = true;
-    }
+    int rc = pmx_allow_lds(reinterpret_cast<const void *>(pmx_attn8_bwd_kernel), lds, PMX_LDS_PER_CU);
+    if (rc) return rc;
     if (S_pad == 160) {
         // one pass, one wavefront per (sample, head): 4 x (3 x 8 x 160 x 2 + 2 x 160 x 4 + 32 x 80) = 45 KB of LDS
         constexpr size_t lds_f = (size_t)4 * ((size_t)3 * 8 * 160 * sizeof(short) + (size_t)2 * 160 * sizeof(float) + 32 * 80);
         hipLaunchKernelGGL((pmx_attn8_bwd_fused_kernel<5, 1>), dim3(B), dim3(256), lds_f, st, (const __hip_bfloat16 *)qkv_dev, (const __hip_bfloat16 *)out_dev,
                            (const __hip_bfloat16 *)dout_dev, lse_dev, (__hip_bfloat16 *)dqkv_dev, S, B, 0.35355339059327379f, batch_major ? 1 : 0);
-        return hipGetLastError() == hipSuccess ? PMX_OK : PMX_ERR_HIP;
+        return pmx_launch_rc();
     }
     if (S_pad == 416) {
         // one pass, two wavefronts per (sample, head) splitting the query pairs (the 20 x 20 boards: 400 tokens):
         // 4 x (4 x 8 x 416 x 2 + 2 x 416 x 4 + 2 x 32 x 80 + 2 x 1 024) = 145 KB of LDS, one block of eight waves per CU
         constexpr size_t lds_f = (size_t)4 * ((size_t)4 * 8 * 416 * sizeof(short) + (size_t)2 * 416 * sizeof(float) + 2 * 32 * 80 + 2 * 1024);
-        static bool attr2_dev[64] = {};
-        if (!attr2_dev[cur_dev]) {
-            if (hipFuncSetAttribute(reinterpret_cast<const void *>(pmx_attn8_bwd_fused_kernel<13, 2>), hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024) != hipSuccess)
-                return PMX_ERR_HIP;
-            attr2_dev[cur_dev] = true;
-        }
+        rc = pmx_allow_lds(reinterpret_cast<const void *>(pmx_attn8_bwd_fused_kernel<13, 2>), lds_f, PMX_LDS_PER_CU);
+        if (rc) return rc;
         hipLaunchKernelGGL((pmx_attn8_bwd_fused_kernel<13, 2>), dim3(B), dim3(512), lds_f, st, (const __hip_bfloat16 *)qkv_dev, (const __hip_bfloat16 *)out_dev,
                            (const __hip_bfloat16 *)dout_dev, lse_dev, (__hip_bfloat16 *)dqkv_dev, S, B, 0.35355339059327379f, batch_major ? 1 : 0);
-        return hipGetLastError() == hipSuccess ? PMX_OK : PMX_ERR_HIP;
+        return pmx_launch_rc();
     }
     hipLaunchKernelGGL(pmx_attn8_bwd_kernel, dim3(B), dim3(512), lds, st, (const __hip_bfloat16 *)qkv_dev, (const __hip_bfloat16 *)out_dev,
                        (const __hip_bfloat16 *)dout_dev, lse_dev, (__hip_bfloat16 *)dqkv_dev, S, B, 0.35355339059327379f, batch_major ? 1 : 0);
-    return hipGetLastError() == hipSuccess ? PMX_OK : PMX_ERR_HIP;
+    return pmx_launch_rc();
 }
 
 
@@ -1392,7 +1353,7 @@ __global__ __launch_bounds__(256) void pmx_gn8cl_gelu_fwd_kernel(const __hip_bfl
             for (int c = 0; c < CPG; ++c) {
                 float z = (v[k][c] - mean) * wc[c] + bc[c];
                 if (res) z += r8[c];
-                o8[c] = gelu_f(z);
+                o8[c] = gelu_exact(z);
             }
             cl_store8(y + base + (size_t)pos * C, o8);
         }
@@ -1437,7 +1398,7 @@ __global__ __launch_bounds__(256) void pmx_gn8cl_gelu_bwd_kernel(const __hip_bfl
                 const float x = (h8[c] - mean) * rstd;
                 float z = x * wc[c] + bc[c];
                 if (res) z += r8[c];
-                const float dz = d8[c] * gelu_grad_f(z);
+                const float dz = d8[c] * gelu_grad(z);
                 dz8[c] = dz;
                 sw[c] += dz * x; sb[c] += dz;
                 const float gg = dz * wc[c];
@@ -1477,7 +1438,7 @@ extern "C" int pmx_gn8cl_gelu_forward(const void *h, const void *res, const floa
     const unsigned grid = (unsigned)((rows + 3) / 4);
 #define PMX_GNCL_FWD(K) hipLaunchKernelGGL((pmx_gn8cl_gelu_fwd_kernel<K>), dim3(grid), dim3(256), 0, st, (const __hip_bfloat16 *)h, (const __hip_bfloat16 *)res, w, b, (__hip_bfloat16 *)y, mean, rstd, rows, groups, HW, eps)
     if (HW <= 192) PMX_GNCL_FWD(3); else if (HW <= 448) PMX_GNCL_FWD(7); else PMX_GNCL_FWD(16);
-    return hipGetLastError() == hipSuccess ? PMX_OK : PMX_ERR_HIP;
+    return pmx_launch_rc();
 }
 
 extern "C" int pmx_gn8cl_gelu_backward(const void *h, const void *res, const void *dy, const float *w, const float *b, const float *mean,
@@ -1492,7 +1453,7 @@ extern "C" int pmx_gn8cl_gelu_backward(const void *h, const void *res, const voi
     const unsigned grid = (unsigned)((rows + 3) / 4);
 #define PMX_GNCL_BWD(K) hipLaunchKernelGGL((pmx_gn8cl_gelu_bwd_kernel<K>), dim3(grid), dim3(256), 0, st, (const __hip_bfloat16 *)h, (const __hip_bfloat16 *)res, (const __hip_bfloat16 *)dy, w, b, mean, rstd, (__hip_bfloat16 *)dh, (__hip_bfloat16 *)dres, partial, rows, groups, HW)
     if (HW <= 192) PMX_GNCL_BWD(3); else if (HW <= 448) PMX_GNCL_BWD(7); else PMX_GNCL_BWD(16);
-    return hipGetLastError() == hipSuccess ? PMX_OK : PMX_ERR_HIP;
+    return pmx_launch_rc();
 }
 
 // ---------------------------------------------------------------------------------------------------------------
@@ -1625,7 +1586,7 @@ extern "C" int pmx_ppo_loss(const void *logits_dev, int32_t logits_bf16, const f
         hipLaunchKernelGGL(pmx_ppo_loss_kernel<float>, dim3(1), dim3(1024), 0, st, (const float *)logits_dev, values_dev, act_dev, old_logp_dev,
                            adv_dev, ret_dev, (int)B, (int)BV, clip_eps_dev, ent_coef_dev, clip_eps, ent_coef, vf_coef, stats_dev,
                            (float *)dlogits_dev, dvalues_dev);
-    return hipGetLastError() == hipSuccess ? PMX_OK : PMX_ERR_HIP;
+    return pmx_launch_rc();
 }
 
 // ---------------------------------------------------------------------------------------------------------------
@@ -1703,7 +1664,7 @@ extern "C" int pmx_gather_rows_set_floats(int32_t n, const void *const *src_dev,
     if (blocks < 1) blocks = 1;
     if (blocks > 2048) blocks = 2048;
     hipLaunchKernelGGL(pmx_gather_rows_kernel, dim3((unsigned)blocks, (unsigned)n), dim3(256), 0, reinterpret_cast<hipStream_t>(stream), a);
-    return hipGetLastError() == hipSuccess ? PMX_OK : PMX_ERR_HIP;
+    return pmx_launch_rc();
 }
 
 // up to 8 float32 values written to consecutive device words in one launch (the scalars a replayed graph reads: they travel
@@ -1719,7 +1680,7 @@ extern "C" int pmx_set_floats(float *dst_dev, const float *values, int32_t n, vo
     PmxFloats8 f;
     for (int i = 0; i < 8; ++i) f.v[i] = i < n ? values[i] : 0.f;
     hipLaunchKernelGGL(pmx_set_floats_kernel, dim3(1), dim3(64), 0, reinterpret_cast<hipStream_t>(stream), dst_dev, f, (int)n);
-    return hipGetLastError() == hipSuccess ? PMX_OK : PMX_ERR_HIP;
+    return pmx_launch_rc();
 }
 
 // ---------------------------------------------------------------------------------------------------------------
@@ -1815,7 +1776,7 @@ extern "C" int pmx_clip_adam_ema_tail(float *grad_dev, float *param_dev, float *
     hipLaunchKernelGGL(pmx_adam_ema_kernel, dim3((unsigned)b2k), dim3(256), 0, st, grad_dev, param_dev, exp_avg_dev, exp_avg_sq_dev, ema_dev, (long)n,
                        (const double *)scratch_dev, (int)blocks, scalars_dev, lr_over_bc1, rsqrt_bc2, beta1, beta2, eps, max_norm, ema_decay,
                        norm_out_dev, (uint16_t *)param_bf16_dev, reports5_dev, report_sums6_dev);
-    return hipGetLastError() == hipSuccess ? PMX_OK : PMX_ERR_HIP;
+    return pmx_launch_rc();
 }
 
 // ---------------------------------------------------------------------------------------------------------------
@@ -1906,5 +1867,5 @@ extern "C" int pmx_flatten_sum_to_f32(int32_t n, const void *const *src_dev, con
         if (blocks > 512) blocks = 512;
         hipLaunchKernelGGL(pmx_flatten_f32_kernel, dim3((unsigned)blocks, (unsigned)m), dim3(256), 0, st, a, dst_dev);
     }
-    return hipGetLastError() == hipSuccess ? PMX_OK : PMX_ERR_HIP;
+    return pmx_launch_rc();
 }

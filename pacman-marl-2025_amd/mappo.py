@@ -42,52 +42,80 @@ def layer_norm_small(x, ln):
     return ((xf - mean) * torch.rsqrt(var + ln.eps) * ln.weight + ln.bias).to(x.dtype)
 
 
-_PENDING_ROWS = {}          # data_ptr of a partial-row gradient buffer -> (rows still to be added, floats per row, the buffer)
-_DEFER_ROW_SUMS = [False]  # True only while PPOLearner._backward_group runs autograd: its gradient gather adds the rows; any other
-                           # caller of these autograd functions gets the summed row from the backward call itself
+class _PartialRows:
+    """Owner of the deferred row sums.  The backward calls of the pmx_ffn / tok96 / tok32ln / *_tail families end with a small
+    second-stage kernel that adds the partial rows of the parameter gradients into row 0 -- a launch on the critic's chain of the
+    launch-bound 512-sample step between every two backward kernels, although nothing before the gradient gather reads its result.
+    While `enabled` (PPOLearner._backward_group around autograd) the library skips that kernel, the buffer is remembered here with
+    the (offset, numel) slices of row 0 it hands out, and the gather (pmx_flatten_sum_to_f32) adds the rows while it copies.  A
+    gradient is matched to its buffer EXACTLY -- storage, offset and size -- and `settle` raises unless every slice handed out came
+    back: a sum of two unsummed row-0 views, or whatever a hook returned, is wrong before the learner sees it."""
+
+    def __init__(self):
+        self.on = False          # True only inside `enabled`; any other caller of the autograd functions gets the summed row 0
+        self.pending = []        # [lib, buffer, partial rows, floats per row, family, {(offset, numel): claimed}]
+
+    @contextlib.contextmanager
+    def enabled(self, on=True):
+        """Deferral on (or off) for the autograd call inside; nothing of an earlier, failed call stays pending."""
+        prev, self.on = self.on, bool(on)
+        self.pending = []
+        try:
+            yield self
+        finally:
+            self.on = prev
+
+    @contextlib.contextmanager
+    def defer(self, lib, grad, floats, slices, plain=True, family="partial rows"):
+        """Context for ONE backward call.  slices: (offset, numel) of every parameter gradient handed out as a view of row 0 of grad
+        and wanted (ctx.needs_input_grad); plain: those views leave as they are, float32 (no cast copies)."""
+        on = self.on and plain
+        if on:
+            lib.pmx_defer_row_sums(1)
+        try:
+            yield
+        finally:
+            if on:
+                lib.pmx_defer_row_sums(0)
+        rows = lib.pmx_last_partial_rows() if on else 0
+        if rows > 0:
+            self.pending.append([lib, grad, rows, floats, family, {tuple(sl): False for sl in slices}])
+
+    def claim(self, g):
+        """(rows, floats per row) if g is one of the pending slices -- still partial rows, to be summed by the gather -- else (0, 0)."""
+        if self.pending and g.dtype == torch.float32 and g.is_contiguous():
+            base, key = g.untyped_storage().data_ptr(), (g.storage_offset(), g.numel())
+            for _, buf, rows, floats, _, slices in self.pending:
+                if key in slices and buf.untyped_storage().data_ptr() == base:
+                    slices[key] = True
+                    return rows, floats
+        return 0, 0
+
+    def settle(self):
+        """After every gradient was offered to `claim`, before the gather is launched: forgets the buffers; raises if a slice is left."""
+        pending, self.pending = self.pending, []
+        for _, _, _, _, family, slices in pending:
+            for (off, n), claimed in slices.items():
+                if not claimed:
+                    raise RuntimeError(
+                        f"deferred row sums: the {family} gradient at row-0 offset {off} ({n} floats) did not come back from autograd as "
+                        "the view its backward returned; a parameter was reached twice in one loss, has a tensor hook, or is no target "
+                        "of this call under PPOLearner._backward_group (set PPOLearner.defer_row_sums = False for such a model)")
+
+    def flush(self):
+        """Adds whatever partial rows are pending with the dedicated kernel (a consumer other than the learner's gather)."""
+        pending, self.pending = self.pending, []
+        for lib, buf, rows, floats, _, _ in pending:
+            st = C.c_void_p(torch.cuda.current_stream(buf.device).cuda_stream)
+            _lib.check(lib.pmx_sum_partial_rows(buf.data_ptr(), rows, floats, st), "pmx_sum_partial_rows")
 
 
-class _row_sums_deferred:
-    """Context for ONE backward call of the pmx_ffn / tok96 / tok32ln / *_tail families.  Those end with a small second-stage kernel
-    that adds the partial rows of the parameter gradients into row 0 -- a launch on the critic's chain of the launch-bound
-    512-sample step between every two backward kernels, although nothing before the gradient gather reads its result.  Under
-    PPOLearner._backward_group the library skips that kernel and the buffer is remembered here; the gather (pmx_flatten_sum_to_f32)
-    adds the rows while it copies.  `plain`: the parameter gradients are handed out as float32 views of row 0 (no cast copies)."""
-
-    def __init__(self, lib, grad, floats, plain=True):
-        self.lib, self.grad, self.floats = lib, grad, floats
-        self.on = _DEFER_ROW_SUMS[0] and grad.is_cuda and plain
-
-    def __enter__(self):
-        if self.on:
-            self.lib.pmx_defer_row_sums(1)
-        return self
-
-    def __exit__(self, *exc):
-        if not self.on:
-            return False
-        self.lib.pmx_defer_row_sums(0)
-        n = self.lib.pmx_last_partial_rows()
-        if exc[0] is None and n > 0:
-            _PENDING_ROWS[self.grad.data_ptr()] = (n, self.floats, self.grad)
-        return False
+_PARTIAL_ROWS = _PartialRows()
 
 
-def pending_rows_of(ptr):
-    """(rows, floats per row) if the device address lies in row 0 of a buffer whose partial rows are still to be added, else (0, 0)."""
-    for base, (n, floats, _) in _PENDING_ROWS.items():
-        if base <= ptr < base + 4 * floats:
-            return n, floats
-    return 0, 0
-
-
-def flush_pending_rows():
-    """Adds whatever partial rows are still pending with the dedicated kernel (a consumer other than the learner's gather)."""
-    lib = _lib.load() if _PENDING_ROWS else None
-    for base, (n, floats, buf) in list(_PENDING_ROWS.items()):
-        st = C.c_void_p(torch.cuda.current_stream(buf.device).cuda_stream)
-        _lib.check(lib.pmx_sum_partial_rows(base, n, floats, st), "pmx_sum_partial_rows")
-    _PENDING_ROWS.clear()
+def _row0(grad, slices, needs):
+    """-> (the views of row 0 of a partial-row buffer at `slices`, the slices whose input wants a gradient)."""
+    return [grad[o:o + n] for o, n in slices], [sl for sl, need in zip(slices, needs) if need]
 
 
 class _LN32Residual(torch.autograd.Function):
@@ -160,12 +188,12 @@ class _FFNLayerNorm(torch.autograd.Function):
         dy = dy.to(torch.bfloat16).contiguous()
         dx = torch.empty_like(x)
         grad = torch.empty((1 + _lib.GRAD_PARTIAL_ROWS) * _lib.FFN_GRAD_FLOATS, dtype=torch.float32, device=dev)   # row 0 = the result
-        with _row_sums_deferred(lib, grad, _lib.FFN_GRAD_FLOATS, all(dt == torch.float32 for dt in ctx.dtypes)):
+        # dw1, db1, dw2, db2, dgamma, dbeta in the buffer
+        outs, wanted = _row0(grad, ((4096, 4096), (8192, 128), (0, 4096), (8320, 32), (8352, 32), (8384, 32)), ctx.needs_input_grad[1:7])
+        with _PARTIAL_ROWS.defer(lib, grad, _lib.FFN_GRAD_FLOATS, wanted, all(dt == torch.float32 for dt in ctx.dtypes), "pmx_ffn"):
             _lib.check(lib.pmx_ffn_backward(x.data_ptr(), dy.data_ptr(), pack.data_ptr(), dx.data_ptr(), grad.data_ptr(), x.numel() // 32,
                                             ctx.eps, st), "pmx_ffn_backward")
-        dw2, dw1 = grad[:4096].view(32, 128), grad[4096:8192].view(128, 32)
-        db1, db2, dg, dbeta = grad[8192:8320], grad[8320:8352], grad[8352:8384], grad[8384:8416]
-        outs = (dw1, db1, dw2, db2, dg, dbeta)
+        outs[0], outs[2] = outs[0].view(128, 32), outs[2].view(32, 128)
         return (dx,) + tuple(o.to(dt) for o, dt in zip(outs, ctx.dtypes)) + (None, None)
 
 
@@ -247,10 +275,11 @@ class _InProj96(torch.autograd.Function):
         dy = dy.to(torch.bfloat16).contiguous()
         da = torch.empty_like(a)
         grad = torch.empty((1 + _lib.GRAD_PARTIAL_ROWS) * _lib.TOK96_GRAD_FLOATS, dtype=torch.float32, device=a.device)
-        with _row_sums_deferred(lib, grad, _lib.TOK96_GRAD_FLOATS, all(dt == torch.float32 for dt in ctx.dtypes)):
+        (dw, db), wanted = _row0(grad, ((0, 3072), (3072, 96)), ctx.needs_input_grad[1:3])
+        with _PARTIAL_ROWS.defer(lib, grad, _lib.TOK96_GRAD_FLOATS, wanted, all(dt == torch.float32 for dt in ctx.dtypes), "pmx_tok96"):
             _lib.check(lib.pmx_tok96_backward(a.data_ptr(), dy.data_ptr(), pack.data_ptr(), da.data_ptr(), grad.data_ptr(), a.numel() // 32, st),
                        "pmx_tok96_backward")
-        return da, grad[:3072].view(96, 32).to(ctx.dtypes[0]), grad[3072:3168].to(ctx.dtypes[1]), None
+        return da, dw.view(96, 32).to(ctx.dtypes[0]), db.to(ctx.dtypes[1]), None
 
 
 class _InProj96Res(torch.autograd.Function):
@@ -277,16 +306,17 @@ class _InProj96Res(torch.autograd.Function):
         a, pack = ctx.saved_tensors
         st = C.c_void_p(torch.cuda.current_stream(a.device).cuda_stream)
         grad = torch.empty((1 + _lib.GRAD_PARTIAL_ROWS) * _lib.TOK96_GRAD_FLOATS, dtype=torch.float32, device=a.device)
+        (dw, db), wanted = _row0(grad, ((0, 3072), (3072, 96)), ctx.needs_input_grad[1:3])
         if dy is None:                                  # only the residual output was used
             grad.zero_()
-            return dres, grad[:3072].view(96, 32).to(ctx.dtypes[0]), grad[3072:3168].to(ctx.dtypes[1]), None
+            return dres, dw.view(96, 32).to(ctx.dtypes[0]), db.to(ctx.dtypes[1]), None
         dy = dy.to(torch.bfloat16).contiguous()
         res = None if dres is None else dres.to(torch.bfloat16).contiguous()
         da = torch.empty_like(a)
-        with _row_sums_deferred(lib, grad, _lib.TOK96_GRAD_FLOATS, all(dt == torch.float32 for dt in ctx.dtypes)):
+        with _PARTIAL_ROWS.defer(lib, grad, _lib.TOK96_GRAD_FLOATS, wanted, all(dt == torch.float32 for dt in ctx.dtypes), "pmx_tok96"):
             _lib.check(lib.pmx_tok96_backward_res(a.data_ptr(), dy.data_ptr(), pack.data_ptr(), None if res is None else res.data_ptr(),
                                                   da.data_ptr(), grad.data_ptr(), a.numel() // 32, st), "pmx_tok96_backward_res")
-        return da, grad[:3072].view(96, 32).to(ctx.dtypes[0]), grad[3072:3168].to(ctx.dtypes[1]), None
+        return da, dw.view(96, 32).to(ctx.dtypes[0]), db.to(ctx.dtypes[1]), None
 
 
 class _OutProjAddLN(torch.autograd.Function):
@@ -315,10 +345,11 @@ class _OutProjAddLN(torch.autograd.Function):
         dy = dy.to(torch.bfloat16).contiguous()
         dx, da = torch.empty_like(x), torch.empty_like(a)
         grad = torch.empty((1 + _lib.GRAD_PARTIAL_ROWS) * _lib.TOK32_GRAD_FLOATS, dtype=torch.float32, device=a.device)
-        with _row_sums_deferred(lib, grad, _lib.TOK32_GRAD_FLOATS, all(dt == torch.float32 for dt in ctx.dtypes)):
+        outs, wanted = _row0(grad, ((0, 1024), (1024, 32), (1056, 32), (1088, 32)), ctx.needs_input_grad[2:6])      # dw, db, dgamma, dbeta
+        with _PARTIAL_ROWS.defer(lib, grad, _lib.TOK32_GRAD_FLOATS, wanted, all(dt == torch.float32 for dt in ctx.dtypes), "pmx_tok32ln"):
             _lib.check(lib.pmx_tok32ln_backward(x.data_ptr(), a.data_ptr(), dy.data_ptr(), pack.data_ptr(), dx.data_ptr(), da.data_ptr(),
                                                 grad.data_ptr(), x.numel() // 32, ctx.eps, st), "pmx_tok32ln_backward")
-        outs = (grad[:1024].view(32, 32), grad[1024:1056], grad[1056:1088], grad[1088:1120])
+        outs[0] = outs[0].view(32, 32)
         return (dx, da) + tuple(o.to(dt) for o, dt in zip(outs, ctx.dtypes)) + (None, None)
 
 
@@ -527,10 +558,11 @@ class _ActorTail(torch.autograd.Function):
         G = _lib.ACTOR_TAIL_GRAD_FLOATS
         grad = torch.empty((1 + _lib.HEADS_PARTIAL_ROWS) * G, dtype=torch.float32, device=h.device)
         st = C.c_void_p(torch.cuda.current_stream(h.device).cuda_stream)
-        with _row_sums_deferred(lib, grad, G):
+        (dlnw, dlnb, dw2, db2), wanted = _row0(grad, ((2568, 512), (3080, 512), (0, 2560), (2560, 5)), ctx.needs_input_grad[1:5])
+        with _PARTIAL_ROWS.defer(lib, grad, G, wanted, family="pmx_actor_tail"):
             _lib.check(lib.pmx_actor_tail_backward(h.data_ptr(), 1 if h.dtype == torch.bfloat16 else 0, stats.data_ptr(), dlogits.data_ptr(),
                                                    lnw.data_ptr(), lnb.data_ptr(), w2.data_ptr(), dh.data_ptr(), grad.data_ptr(), B, st), "pmx_actor_tail_backward")
-        return dh, grad[2568:3080], grad[3080:3592], grad[:2560].view(5, 512), grad[2560:2565], None
+        return dh, dlnw, dlnb, dw2.view(5, 512), db2, None
 
 
 class _CriticTail(torch.autograd.Function):
@@ -561,10 +593,11 @@ class _CriticTail(torch.autograd.Function):
         scratch = torch.empty(2 * B * 512, dtype=torch.bfloat16, device=dev)
         grad = torch.empty((1 + _lib.HEADS_PARTIAL_ROWS) * _lib.CRITIC_TAIL_GRAD_FLOATS, dtype=torch.float32, device=dev)
         st = C.c_void_p(torch.cuda.current_stream(dev).cuda_stream)
-        with _row_sums_deferred(lib, grad, _lib.CRITIC_TAIL_GRAD_FLOATS):
+        (dw1, db1, dw2, db2), wanted = _row0(grad, ((0, 16384), (16384, 512), (16896, 512), (17408, 1)), ctx.needs_input_grad[1:5])
+        with _PARTIAL_ROWS.defer(lib, grad, _lib.CRITIC_TAIL_GRAD_FLOATS, wanted, family="pmx_critic_tail"):
             _lib.check(lib.pmx_critic_tail_backward(pooled.data_ptr(), dvalue.data_ptr(), w1.data_ptr(), b1.data_ptr(), w2.data_ptr(), dtok.data_ptr(),
                                                     scratch.data_ptr(), grad.data_ptr(), B, S, st), "pmx_critic_tail_backward")
-        return dtok, grad[:16384].view(512, 32), grad[16384:16896], grad[16896:17408].view(1, 512), grad[17408:17409]
+        return dtok, dw1.view(512, 32), db1, dw2.view(1, 512), db2
 
 
 def column_sums(t):
@@ -1157,7 +1190,7 @@ class PPOLearner:
         self._graph = self._graphs = self._g_groups = None
         self._g_in = self._g_sc = self._g_stats = self._g_acc = self._g_acc_keys = self._g_batch = None
 
-    # the second-stage row sums of the gradient reductions folded into the gradient gather (mappo._row_sums_deferred): eight small
+    # the second-stage row sums of the gradient reductions folded into the gradient gather (mappo._PartialRows): eight small
     # launches less on the chains of the 512-sample step.  (A first version ran them on a third stream beside the next backward kernel
     # and LOST -- 1 380 against 1 995 steps/s: six fork / join pairs cost the captured graph more than the kernels cost the chain.)
     defer_row_sums = True
@@ -1171,22 +1204,23 @@ class PPOLearner:
 
     def _gather_grads(self, flat, first):
         """pmx_flatten_sum_to_f32: the float32 / bfloat16 gradients `flat` into the float32 bucket from element `first` on, in one
-        launch; gradients that are still partial rows (mappo._row_sums_deferred) are summed on the way."""
+        launch; gradients that are still partial rows (mappo._PartialRows) are summed on the way."""
         lib = _lib.load()
         n = len(flat)
         if any(not g.is_contiguous() for g in flat):
-            flush_pending_rows()                             # (a copy would read rows that have not been added yet)
+            _PARTIAL_ROWS.flush()                            # (a copy would read rows that have not been added yet)
             flat = [g.contiguous() for g in flat]
         src = (C.c_void_p * n)(*[g.data_ptr() for g in flat])
         isb = (C.c_uint8 * n)(*[1 if g.dtype == torch.bfloat16 else 0 for g in flat])
         cnt = (C.c_int32 * n)(*[g.numel() for g in flat])
-        pend = [pending_rows_of(g.data_ptr()) if g.dtype == torch.float32 else (0, 0) for g in flat]
+        pend = [_PARTIAL_ROWS.claim(g) for g in flat]
         rows = (C.c_int32 * n)(*[r for r, _ in pend])
         stride = (C.c_int32 * n)(*[f for _, f in pend])
         offs, o = [], first
         for g in flat:
             offs.append(o); o += g.numel()
         off = (C.c_int64 * n)(*offs)
+        _PARTIAL_ROWS.settle()                               # (raises before anything reads a row 0 that nobody will sum)
         st = C.c_void_p(torch.cuda.current_stream(self.bucket.grad.device).cuda_stream)
         _lib.check(lib.pmx_flatten_sum_to_f32(n, src, isb, rows, stride, off, cnt, self.bucket.grad.data_ptr(), st), "pmx_flatten_sum_to_f32")
 
@@ -1204,20 +1238,15 @@ class PPOLearner:
         # the gathering kernel applies: a float32 bucket on the GPU, gradients float32 or bfloat16 (autograd hands every gradient
         # out in its target's type).  Only then may the backward kernels leave partial rows behind for it.
         gather = grad.is_cuda and grad.dtype == torch.float32 and all(t.dtype in (torch.float32, torch.bfloat16) for t in targets)
-        prev, _DEFER_ROW_SUMS[0] = _DEFER_ROW_SUMS[0], bool(self.defer_row_sums and gather)
-        _PENDING_ROWS.clear()                                # (nothing of an earlier, failed call may match this one's addresses)
         root, unit = loss_root(loss)
-        try:
+        with _PARTIAL_ROWS.enabled(self.defer_row_sums and gather):
             grads = torch.autograd.grad(root, targets, grad_outputs=unit, allow_unused=True, retain_graph=retain)
-        finally:
-            _DEFER_ROW_SUMS[0] = prev
         flat = [g.reshape(-1) if g is not None else torch.zeros(p.numel(), dtype=grad.dtype, device=grad.device)
                 for g, p in zip(grads, params)]
         if gather:
             self._gather_grads(flat, self._offsets[lo])
-            _PENDING_ROWS.clear()
         else:
-            flush_pending_rows()
+            _PARTIAL_ROWS.flush()
             torch.cat([g.to(grad.dtype) for g in flat], out=grad[self._offsets[lo]:self._offsets[hi]])
 
     def _reduce_slice(self, lo, hi):

@@ -1163,9 +1163,77 @@ def test_learner_gradient_with_and_without_the_folded_row_sums_and_the_unit_root
         L.bucket.grad.zero_()
         L._backward_into_bucket(loss)
         grads[folded] = L.bucket.grad.clone()
-        assert not mappo._PENDING_ROWS
+        assert not mappo._PARTIAL_ROWS.pending
     rel = float((grads[True] - grads[False]).norm() / grads[False].norm())
     assert 0.0 < float(grads[False].norm()) and rel <= 2e-3, rel
+
+
+def _encoder_layer_and_tokens():
+    """One CriticEncoderLayer (d_model 32, 4 heads, feed-forward 128) and the tokens of three 5 x 6 boards."""
+    from pmx import mappo
+    torch.manual_seed(21)
+    layer = mappo.CriticEncoderLayer(d_model=32, nhead=4, dim_feedforward=128, dropout=0.0, batch_first=False).cuda()
+    x = torch.randn(3, 30, 32, device="cuda").to(torch.bfloat16).requires_grad_()
+    return mappo, layer, x, list(layer.parameters())
+
+
+def test_partial_rows_of_a_layer_used_once_are_all_claimed_and_summed_by_the_gather():
+    """mappo._PartialRows as PPOLearner._backward_group drives it: with deferral on every one of the layer's twelve parameter
+    gradients is claimed, settle() passes, and pmx_flatten_sum_to_f32 delivers the gradients the non-deferred path computes (same
+    bound as the learner test above: the two differ in the order of the float32 row sums only)."""
+    import ctypes as C
+    from pmx import _lib
+    mappo, layer, x, params = _encoder_layer_and_tokens()
+    lib, pr = _lib.load(), mappo._PARTIAL_ROWS
+    assert len(params) == 12
+
+    def loss():
+        return layer.forward_batch_major(x).float().square().sum()
+
+    ref = torch.cat([g.reshape(-1) for g in torch.autograd.grad(loss(), params)])
+    assert not pr.pending
+    with pr.enabled(True):
+        grads = torch.autograd.grad(loss(), params)
+    assert not pr.on and len(pr.pending) == 3                          # in-projection, out-projection + norm1, feed-forward + norm2
+    flat = [g.reshape(-1) for g in grads]
+    pend = [pr.claim(g) for g in flat]
+    assert all(rows >= 1 and floats > 0 for rows, floats in pend), pend
+    pr.settle()
+    assert not pr.pending
+    n, offs, o = len(flat), [], 0
+    for g in flat:
+        offs.append(o); o += g.numel()
+    dst = torch.full((o,), float("nan"), device="cuda")
+    rc = lib.pmx_flatten_sum_to_f32(n, (C.c_void_p * n)(*[g.data_ptr() for g in flat]), (C.c_uint8 * n)(*[0] * n),
+                                    (C.c_int32 * n)(*[r for r, _ in pend]), (C.c_int32 * n)(*[f for _, f in pend]), (C.c_int64 * n)(*offs),
+                                    (C.c_int32 * n)(*[g.numel() for g in flat]), dst.data_ptr(), C.c_void_p(torch.cuda.current_stream().cuda_stream))
+    assert rc == 0
+    assert not bool(torch.isnan(dst).any())
+    rel = float((dst - ref).norm() / ref.norm())
+    print("used once: |ref| %.6g, relative L2 %.3g" % (float(ref.norm()), rel))
+    assert 0.0 < float(ref.norm()) and rel <= 2e-3, rel
+
+
+def test_partial_rows_of_a_layer_used_twice_raise_instead_of_gathering_unsummed_rows():
+    """A layer applied twice in one loss: autograd adds the two row-0 views of every parameter before anyone has summed their rows,
+    so nothing it hands back is a pending slice -- settle() raises (an ordinary Python error, before any launch reads the buffers).
+    With deferral off the same loss has finite gradients."""
+    mappo, layer, x, params = _encoder_layer_and_tokens()
+    pr = mappo._PARTIAL_ROWS
+
+    def loss():
+        return layer.forward_batch_major(layer.forward_batch_major(x)).float().square().sum()
+
+    with pr.enabled(True):
+        grads = torch.autograd.grad(loss(), params)
+    assert len(pr.pending) == 6
+    assert [pr.claim(g.reshape(-1)) for g in grads] == [(0, 0)] * 12
+    with pytest.raises(RuntimeError, match="reached twice"):
+        pr.settle()
+    assert not pr.pending and not pr.on
+    grads = torch.autograd.grad(loss(), params)
+    assert not pr.pending
+    assert all(bool(torch.isfinite(g).all()) for g in grads) and any(float(g.abs().max()) > 0 for g in grads)
 
 
 def test_bf16_shadow_weights_give_the_autocast_step():
