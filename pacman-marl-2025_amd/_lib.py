@@ -4,6 +4,8 @@ There is no CPU fallback: if the HIP library is missing or does not load, import
 import ctypes as C
 import os
 
+import torch
+
 from . import build as _build
 
 PMX_MAX_DIM = 32
@@ -186,3 +188,13 @@ def check(rc, what=""):
     if rc != 0:
         msg = load().pmx_last_error()
         raise PmxError(f"{what} failed with code {rc}: {msg.decode() if msg else ''}")
+
+
+def call(name, *args):
+    """The exported function `name` with `args`; a non-zero return code raises PmxError labelled with that name."""
+    check(getattr(load(), name)(*args), name)
+
+
+def stream(dev):
+    """torch's current stream on `dev`, as the `void *stream` argument of the C ABI."""
+    return C.c_void_p(torch.cuda.current_stream(dev).cuda_stream)

@@ -23,7 +23,14 @@ import torch.nn as nn
 import torch.nn.functional as F
 from torch.nn.utils import stateless
 
-from . import _lib, actor_tower
+from . import _lib, actor_tower, partial_rows
+from .actor_head import _ActorHead, _ActorTail
+from .actor_tower import group_norm_gelu
+from .critic_kernels import (_CriticTail, _Projector, add_layer_norm_small, attention8, attention8_forward, encoder_packs, ffn_layer_norm,
+                             in_proj96, in_proj96_res, out_proj_add_layer_norm, pack_ffn, pack_in_proj, pack_out_proj, token_linear)
+# not called by the model: the trainer, tests and tools reach these two as mappo.<name>, like the functions above
+from .actor_head import pack_actor_head  # noqa: F401
+from .critic_kernels import column_sums  # noqa: F401
 
 GAMMA, GAE_LAMBDA = 0.99, 0.95                     # pacman_mappo_resnet.py:19-20
 CLIP_EPS, VF_COEF, MAX_GRAD_NORM = 0.15, 0.5, 0.5  # :21-23
@@ -31,616 +38,6 @@ LR_START, LR_END = 2e-4, 4e-5                      # :27-28
 ENT_COEF_START, ENT_COEF_END = 0.02, 0.004         # :29-30
 EMA_DECAY = 0.995                                  # :38
 SHAPING_SCALE = 0.1                                # :34
-
-
-def layer_norm_small(x, ln):
-    """nn.LayerNorm over a SMALL last dimension as var_mean + elementwise ops.  torch's native kernel launches one
-    workgroup per row (RowwiseMomentsCUDAKernel): for the critic's [H*W*B, 32] token matrix that is 630 k tiny
-    workgroups and 1.7 ms per call on MI355X (45 % of the optimizer step at batch 4096)."""
-    xf = x.float()
-    var, mean = torch.var_mean(xf, dim=-1, unbiased=False, keepdim=True)
-    return ((xf - mean) * torch.rsqrt(var + ln.eps) * ln.weight + ln.bias).to(x.dtype)
-
-
-class _PartialRows:
-    """Owner of the deferred row sums.  The backward calls of the pmx_ffn / tok96 / tok32ln / *_tail families end with a small
-    second-stage kernel that adds the partial rows of the parameter gradients into row 0 -- a launch on the critic's chain of the
-    launch-bound 512-sample step between every two backward kernels, although nothing before the gradient gather reads its result.
-    While `enabled` (PPOLearner._backward_group around autograd) the library skips that kernel, the buffer is remembered here with
-    the (offset, numel) slices of row 0 it hands out, and the gather (pmx_flatten_sum_to_f32) adds the rows while it copies.  A
-    gradient is matched to its buffer EXACTLY -- storage, offset and size -- and `settle` raises unless every slice handed out came
-    back: a sum of two unsummed row-0 views, or whatever a hook returned, is wrong before the learner sees it."""
-
-    def __init__(self):
-        self.on = False          # True only inside `enabled`; any other caller of the autograd functions gets the summed row 0
-        self.pending = []        # [lib, buffer, partial rows, floats per row, family, {(offset, numel): claimed}]
-
-    @contextlib.contextmanager
-    def enabled(self, on=True):
-        """Deferral on (or off) for the autograd call inside; nothing of an earlier, failed call stays pending."""
-        prev, self.on = self.on, bool(on)
-        self.pending = []
-        try:
-            yield self
-        finally:
-            self.on = prev
-
-    @contextlib.contextmanager
-    def defer(self, lib, grad, floats, slices, plain=True, family="partial rows"):
-        """Context for ONE backward call.  slices: (offset, numel) of every parameter gradient handed out as a view of row 0 of grad
-        and wanted (ctx.needs_input_grad); plain: those views leave as they are, float32 (no cast copies)."""
-        on = self.on and plain
-        if on:
-            lib.pmx_defer_row_sums(1)
-        try:
-            yield
-        finally:
-            if on:
-                lib.pmx_defer_row_sums(0)
-        rows = lib.pmx_last_partial_rows() if on else 0
-        if rows > 0:
-            self.pending.append([lib, grad, rows, floats, family, {tuple(sl): False for sl in slices}])
-
-    def claim(self, g):
-        """(rows, floats per row) if g is one of the pending slices -- still partial rows, to be summed by the gather -- else (0, 0)."""
-        if self.pending and g.dtype == torch.float32 and g.is_contiguous():
-            base, key = g.untyped_storage().data_ptr(), (g.storage_offset(), g.numel())
-            for _, buf, rows, floats, _, slices in self.pending:
-                if key in slices and buf.untyped_storage().data_ptr() == base:
-                    slices[key] = True
-                    return rows, floats
-        return 0, 0
-
-    def settle(self):
-        """After every gradient was offered to `claim`, before the gather is launched: forgets the buffers; raises if a slice is left."""
-        pending, self.pending = self.pending, []
-        for _, _, _, _, family, slices in pending:
-            for (off, n), claimed in slices.items():
-                if not claimed:
-                    raise RuntimeError(
-                        f"deferred row sums: the {family} gradient at row-0 offset {off} ({n} floats) did not come back from autograd as "
-                        "the view its backward returned; a parameter was reached twice in one loss, has a tensor hook, or is no target "
-                        "of this call under PPOLearner._backward_group (set PPOLearner.defer_row_sums = False for such a model)")
-
-    def flush(self):
-        """Adds whatever partial rows are pending with the dedicated kernel (a consumer other than the learner's gather)."""
-        pending, self.pending = self.pending, []
-        for lib, buf, rows, floats, _, _ in pending:
-            st = C.c_void_p(torch.cuda.current_stream(buf.device).cuda_stream)
-            _lib.check(lib.pmx_sum_partial_rows(buf.data_ptr(), rows, floats, st), "pmx_sum_partial_rows")
-
-
-_PARTIAL_ROWS = _PartialRows()
-
-
-def _row0(grad, slices, needs):
-    """-> (the views of row 0 of a partial-row buffer at `slices`, the slices whose input wants a gradient)."""
-    return [grad[o:o + n] for o, n in slices], [sl for sl, need in zip(slices, needs) if need]
-
-
-class _LN32Residual(torch.autograd.Function):
-    """LayerNorm(x + a) over a 32-wide feature dimension through the fused HIP kernels pmx_ln32_forward/backward."""
-
-    @staticmethod
-    def forward(ctx, x, a, w, b, eps):
-        lib = _lib.load()
-        x, a = x.contiguous(), a.contiguous()
-        rows = x.numel() // 32
-        y = torch.empty_like(x)
-        mean = torch.empty(rows, dtype=torch.float32, device=x.device)
-        rstd = torch.empty(rows, dtype=torch.float32, device=x.device)
-        wf, bf = w.float().contiguous(), b.float().contiguous()
-        st = C.c_void_p(torch.cuda.current_stream(x.device).cuda_stream)
-        _lib.check(lib.pmx_ln32_forward(x.data_ptr(), a.data_ptr(), wf.data_ptr(), bf.data_ptr(), y.data_ptr(), mean.data_ptr(),
-                                        rstd.data_ptr(), rows, float(eps), 0 if x.dtype == torch.float32 else 1, st), "pmx_ln32_forward")
-        ctx.save_for_backward(x, a, wf, mean, rstd)
-        ctx.wdtype = w.dtype
-        return y
-
-    @staticmethod
-    def backward(ctx, gy):
-        lib = _lib.load()
-        x, a, wf, mean, rstd = ctx.saved_tensors
-        gy = gy.contiguous()
-        dz = torch.empty_like(x)
-        partial = torch.empty(_lib.LN32_PARTIAL_ROWS, 64, dtype=torch.float32, device=x.device)
-        st = C.c_void_p(torch.cuda.current_stream(x.device).cuda_stream)
-        _lib.check(lib.pmx_ln32_backward(x.data_ptr(), a.data_ptr(), gy.data_ptr(), wf.data_ptr(), mean.data_ptr(), rstd.data_ptr(),
-                                         dz.data_ptr(), partial.data_ptr(), x.numel() // 32,
-                                         0 if x.dtype == torch.float32 else 1, st), "pmx_ln32_backward")
-        dwb = partial.sum(0).to(ctx.wdtype)          # gradients carry the dtype of the parameters they belong to
-        return dz, dz, dwb[:32], dwb[32:], None
-
-
-def add_layer_norm_small(x, a, ln):
-    """LayerNorm(x + a) for the critic tokens: the fused HIP kernel on the GPU (feature dimension 32, float32 or
-    bfloat16), the reduce + elementwise formulation otherwise."""
-    if x.is_cuda and x.shape[-1] == 32 and x.dtype == a.dtype and x.dtype in (torch.float32, torch.bfloat16):
-        return _LN32Residual.apply(x, a, ln.weight, ln.bias, ln.eps)
-    return layer_norm_small(x + a, ln)
-
-
-class _FFNLayerNorm(torch.autograd.Function):
-    """LayerNorm(x + linear2(relu(linear1(x)))) on [..., 32] bfloat16 tokens through pmx_ffn_forward / pmx_ffn_backward
-    (csrc/pmx_critic.hip): one kernel each way, the 128-wide hidden activations never reach memory, backward recomputes."""
-
-    @staticmethod
-    def forward(ctx, x, w1, b1, w2, b2, gamma, beta, eps, pack=None):
-        lib = _lib.load()
-        x = x.contiguous()
-        dev = x.device
-        st = C.c_void_p(torch.cuda.current_stream(dev).cuda_stream)
-        if pack is None:
-            pack = pack_ffn(w1, b1, w2, b2, gamma, beta)
-        y = torch.empty_like(x)
-        _lib.check(lib.pmx_ffn_forward(x.data_ptr(), pack.data_ptr(), y.data_ptr(), x.numel() // 32, float(eps), st), "pmx_ffn_forward")
-        ctx.save_for_backward(x, pack)
-        ctx.eps = float(eps)
-        ctx.dtypes = [t.dtype for t in (w1, b1, w2, b2, gamma, beta)]
-        return y
-
-    @staticmethod
-    def backward(ctx, dy):
-        lib = _lib.load()
-        x, pack = ctx.saved_tensors
-        dev = x.device
-        st = C.c_void_p(torch.cuda.current_stream(dev).cuda_stream)
-        dy = dy.to(torch.bfloat16).contiguous()
-        dx = torch.empty_like(x)
-        grad = torch.empty((1 + _lib.GRAD_PARTIAL_ROWS) * _lib.FFN_GRAD_FLOATS, dtype=torch.float32, device=dev)   # row 0 = the result
-        # dw1, db1, dw2, db2, dgamma, dbeta in the buffer
-        outs, wanted = _row0(grad, ((4096, 4096), (8192, 128), (0, 4096), (8320, 32), (8352, 32), (8384, 32)), ctx.needs_input_grad[1:7])
-        with _PARTIAL_ROWS.defer(lib, grad, _lib.FFN_GRAD_FLOATS, wanted, all(dt == torch.float32 for dt in ctx.dtypes), "pmx_ffn"):
-            _lib.check(lib.pmx_ffn_backward(x.data_ptr(), dy.data_ptr(), pack.data_ptr(), dx.data_ptr(), grad.data_ptr(), x.numel() // 32,
-                                            ctx.eps, st), "pmx_ffn_backward")
-        outs[0], outs[2] = outs[0].view(128, 32), outs[2].view(32, 128)
-        return (dx,) + tuple(o.to(dt) for o, dt in zip(outs, ctx.dtypes)) + (None, None)
-
-
-def pack_ffn(w1, b1, w2, b2, gamma, beta):
-    """The feed-forward half's parameters in the kernels' operand layout (pmx_ffn_pack), on the current stream."""
-    lib = _lib.load()
-    ps = [t.detach().float().contiguous() for t in (w1, b1, w2, b2, gamma, beta)]
-    pack = torch.empty(_lib.FFN_PACK_BYTES, dtype=torch.uint8, device=ps[0].device)
-    st = C.c_void_p(torch.cuda.current_stream(ps[0].device).cuda_stream)
-    _lib.check(lib.pmx_ffn_pack(*[t.data_ptr() for t in ps], pack.data_ptr(), st), "pmx_ffn_pack")
-    return pack
-
-
-def pack_in_proj(w, b):
-    lib = _lib.load()
-    wf, bf = w.detach().float().contiguous(), b.detach().float().contiguous()
-    pack = torch.empty(_lib.TOK96_PACK_BYTES, dtype=torch.uint8, device=wf.device)
-    st = C.c_void_p(torch.cuda.current_stream(wf.device).cuda_stream)
-    _lib.check(lib.pmx_tok96_pack(wf.data_ptr(), bf.data_ptr(), pack.data_ptr(), st), "pmx_tok96_pack")
-    return pack
-
-
-def pack_out_proj(w, b, gamma, beta):
-    lib = _lib.load()
-    ps = [t.detach().float().contiguous() for t in (w, b, gamma, beta)]
-    pack = torch.empty(_lib.TOK32_PACK_BYTES, dtype=torch.uint8, device=ps[0].device)
-    st = C.c_void_p(torch.cuda.current_stream(ps[0].device).cuda_stream)
-    _lib.check(lib.pmx_tok32ln_pack(*[t.data_ptr() for t in ps], pack.data_ptr(), st), "pmx_tok32ln_pack")
-    return pack
-
-
-def encoder_packs(layers):
-    """The three parameter packs (in-projection, out-projection + norm1, feed-forward + norm2) of every given CriticEncoderLayer in
-    ONE launch (pmx_encoder_pack) on the current stream -> [(pack_in, pack_out, pack_ffn), ...]."""
-    lib = _lib.load()
-    n = len(layers)
-    arr = (_lib.EncoderLayerParams * n)()
-    keep, out = [], []
-    dev = layers[0].linear1.weight.device
-    for i, l in enumerate(layers):
-        mha = l.self_attn
-        ps = [t.detach().float().contiguous() for t in (mha.in_proj_weight, mha.in_proj_bias, mha.out_proj.weight, mha.out_proj.bias,
-                                                        l.norm1.weight, l.norm1.bias, l.linear1.weight, l.linear1.bias, l.linear2.weight,
-                                                        l.linear2.bias, l.norm2.weight, l.norm2.bias)]
-        keep.append(ps)
-        packs = (torch.empty(_lib.TOK96_PACK_BYTES, dtype=torch.uint8, device=dev), torch.empty(_lib.TOK32_PACK_BYTES, dtype=torch.uint8, device=dev),
-                 torch.empty(_lib.FFN_PACK_BYTES, dtype=torch.uint8, device=dev))
-        for name, t in zip(("in_proj_w", "in_proj_b", "out_proj_w", "out_proj_b", "norm1_w", "norm1_b", "lin1_w", "lin1_b", "lin2_w", "lin2_b",
-                            "norm2_w", "norm2_b"), ps):
-            setattr(arr[i], name, t.data_ptr())
-        arr[i].pack_in, arr[i].pack_out, arr[i].pack_ffn = (p.data_ptr() for p in packs)
-        out.append(packs)
-    st = C.c_void_p(torch.cuda.current_stream(dev).cuda_stream)
-    _lib.check(lib.pmx_encoder_pack(n, arr, st), "pmx_encoder_pack")
-    return out
-
-
-class _InProj96(torch.autograd.Function):
-    """qkv = in_proj_weight a + in_proj_bias on [..., 32] bfloat16 tokens (pmx_tok96_forward / _backward)."""
-
-    @staticmethod
-    def forward(ctx, a, w, b, pack=None):
-        lib = _lib.load()
-        a = a.contiguous()
-        st = C.c_void_p(torch.cuda.current_stream(a.device).cuda_stream)
-        if pack is None:
-            pack = pack_in_proj(w, b)
-        y = torch.empty(a.shape[:-1] + (96,), dtype=torch.bfloat16, device=a.device)
-        _lib.check(lib.pmx_tok96_forward(a.data_ptr(), pack.data_ptr(), y.data_ptr(), a.numel() // 32, st), "pmx_tok96_forward")
-        ctx.save_for_backward(a, pack)
-        ctx.dtypes = (w.dtype, b.dtype)
-        return y
-
-    @staticmethod
-    def backward(ctx, dy):
-        lib = _lib.load()
-        a, pack = ctx.saved_tensors
-        st = C.c_void_p(torch.cuda.current_stream(a.device).cuda_stream)
-        dy = dy.to(torch.bfloat16).contiguous()
-        da = torch.empty_like(a)
-        grad = torch.empty((1 + _lib.GRAD_PARTIAL_ROWS) * _lib.TOK96_GRAD_FLOATS, dtype=torch.float32, device=a.device)
-        (dw, db), wanted = _row0(grad, ((0, 3072), (3072, 96)), ctx.needs_input_grad[1:3])
-        with _PARTIAL_ROWS.defer(lib, grad, _lib.TOK96_GRAD_FLOATS, wanted, all(dt == torch.float32 for dt in ctx.dtypes), "pmx_tok96"):
-            _lib.check(lib.pmx_tok96_backward(a.data_ptr(), dy.data_ptr(), pack.data_ptr(), da.data_ptr(), grad.data_ptr(), a.numel() // 32, st),
-                       "pmx_tok96_backward")
-        return da, dw.view(96, 32).to(ctx.dtypes[0]), db.to(ctx.dtypes[1]), None
-
-
-class _InProj96Res(torch.autograd.Function):
-    """_InProj96 that also hands its input back as a second output, `a_res`, for the layer's residual connection: the gradient of
-    the residual branch then arrives HERE, and pmx_tok96_backward_res adds it to W^T dy inside the kernel (float32, rounded once)
-    instead of autograd adding the two bfloat16 tensors with a launch of its own (one per encoder layer and optimizer step)."""
-
-    @staticmethod
-    def forward(ctx, a, w, b, pack=None):
-        lib = _lib.load()
-        a = a.contiguous()
-        st = C.c_void_p(torch.cuda.current_stream(a.device).cuda_stream)
-        if pack is None:
-            pack = pack_in_proj(w, b)
-        y = torch.empty(a.shape[:-1] + (96,), dtype=torch.bfloat16, device=a.device)
-        _lib.check(lib.pmx_tok96_forward(a.data_ptr(), pack.data_ptr(), y.data_ptr(), a.numel() // 32, st), "pmx_tok96_forward")
-        ctx.save_for_backward(a, pack)
-        ctx.dtypes = (w.dtype, b.dtype)
-        return y, a.view_as(a)
-
-    @staticmethod
-    def backward(ctx, dy, dres):
-        lib = _lib.load()
-        a, pack = ctx.saved_tensors
-        st = C.c_void_p(torch.cuda.current_stream(a.device).cuda_stream)
-        grad = torch.empty((1 + _lib.GRAD_PARTIAL_ROWS) * _lib.TOK96_GRAD_FLOATS, dtype=torch.float32, device=a.device)
-        (dw, db), wanted = _row0(grad, ((0, 3072), (3072, 96)), ctx.needs_input_grad[1:3])
-        if dy is None:                                  # only the residual output was used
-            grad.zero_()
-            return dres, dw.view(96, 32).to(ctx.dtypes[0]), db.to(ctx.dtypes[1]), None
-        dy = dy.to(torch.bfloat16).contiguous()
-        res = None if dres is None else dres.to(torch.bfloat16).contiguous()
-        da = torch.empty_like(a)
-        with _PARTIAL_ROWS.defer(lib, grad, _lib.TOK96_GRAD_FLOATS, wanted, all(dt == torch.float32 for dt in ctx.dtypes), "pmx_tok96"):
-            _lib.check(lib.pmx_tok96_backward_res(a.data_ptr(), dy.data_ptr(), pack.data_ptr(), None if res is None else res.data_ptr(),
-                                                  da.data_ptr(), grad.data_ptr(), a.numel() // 32, st), "pmx_tok96_backward_res")
-        return da, dw.view(96, 32).to(ctx.dtypes[0]), db.to(ctx.dtypes[1]), None
-
-
-class _OutProjAddLN(torch.autograd.Function):
-    """LayerNorm(x + out_proj.weight a + out_proj.bias) on [..., 32] bfloat16 tokens (pmx_tok32ln_forward / _backward)."""
-
-    @staticmethod
-    def forward(ctx, x, a, w, b, gamma, beta, eps, pack=None):
-        lib = _lib.load()
-        x, a = x.contiguous(), a.contiguous()
-        st = C.c_void_p(torch.cuda.current_stream(a.device).cuda_stream)
-        if pack is None:
-            pack = pack_out_proj(w, b, gamma, beta)
-        y = torch.empty_like(x)
-        _lib.check(lib.pmx_tok32ln_forward(x.data_ptr(), a.data_ptr(), pack.data_ptr(), y.data_ptr(), x.numel() // 32, float(eps), st),
-                   "pmx_tok32ln_forward")
-        ctx.save_for_backward(x, a, pack)
-        ctx.eps = float(eps)
-        ctx.dtypes = [t.dtype for t in (w, b, gamma, beta)]
-        return y
-
-    @staticmethod
-    def backward(ctx, dy):
-        lib = _lib.load()
-        x, a, pack = ctx.saved_tensors
-        st = C.c_void_p(torch.cuda.current_stream(a.device).cuda_stream)
-        dy = dy.to(torch.bfloat16).contiguous()
-        dx, da = torch.empty_like(x), torch.empty_like(a)
-        grad = torch.empty((1 + _lib.GRAD_PARTIAL_ROWS) * _lib.TOK32_GRAD_FLOATS, dtype=torch.float32, device=a.device)
-        outs, wanted = _row0(grad, ((0, 1024), (1024, 32), (1056, 32), (1088, 32)), ctx.needs_input_grad[2:6])      # dw, db, dgamma, dbeta
-        with _PARTIAL_ROWS.defer(lib, grad, _lib.TOK32_GRAD_FLOATS, wanted, all(dt == torch.float32 for dt in ctx.dtypes), "pmx_tok32ln"):
-            _lib.check(lib.pmx_tok32ln_backward(x.data_ptr(), a.data_ptr(), dy.data_ptr(), pack.data_ptr(), dx.data_ptr(), da.data_ptr(),
-                                                grad.data_ptr(), x.numel() // 32, ctx.eps, st), "pmx_tok32ln_backward")
-        outs[0] = outs[0].view(32, 32)
-        return (dx, da) + tuple(o.to(dt) for o, dt in zip(outs, ctx.dtypes)) + (None, None)
-
-
-def _fused_tokens_ok(x, *weights):
-    return (x.is_cuda and x.dtype == torch.bfloat16 and x.shape[-1] == 32
-            and all(w.dtype == torch.float32 for w in weights))
-
-
-def in_proj96(x, mha, pack=None):
-    if _fused_tokens_ok(x, mha.in_proj_weight) and tuple(mha.in_proj_weight.shape) == (96, 32):
-        return _InProj96.apply(x, mha.in_proj_weight, mha.in_proj_bias, pack)
-    return token_linear(x, mha.in_proj_weight, mha.in_proj_bias)
-
-
-def in_proj96_res(x, mha, pack=None):
-    """-> (qkv, x_res): x_res is x, to be used for the layer's residual connection (see _InProj96Res)."""
-    if _fused_tokens_ok(x, mha.in_proj_weight) and tuple(mha.in_proj_weight.shape) == (96, 32):
-        return _InProj96Res.apply(x, mha.in_proj_weight, mha.in_proj_bias, pack)
-    return token_linear(x, mha.in_proj_weight, mha.in_proj_bias), x
-
-
-def out_proj_add_layer_norm(x, a, proj, ln, pack=None):
-    if _fused_tokens_ok(x, proj.weight) and a.dtype == torch.bfloat16 and tuple(proj.weight.shape) == (32, 32):
-        return _OutProjAddLN.apply(x, a, proj.weight, proj.bias, ln.weight, ln.bias, ln.eps, pack)
-    return add_layer_norm_small(x, token_linear(a, proj.weight, proj.bias), ln)
-
-
-def ffn_layer_norm(x, lin1, lin2, ln, pack=None):
-    """The feed-forward half of the post-LN encoder layer: the fused HIP kernels for bf16 tokens of width 32 with a 128-wide
-    hidden layer on the GPU, the separate ops otherwise."""
-    if (x.is_cuda and x.dtype == torch.bfloat16 and x.shape[-1] == 32 and tuple(lin1.weight.shape) == (128, 32)
-            and tuple(lin2.weight.shape) == (32, 128) and lin1.weight.dtype == torch.float32):
-        return _FFNLayerNorm.apply(x, lin1.weight, lin1.bias, lin2.weight, lin2.bias, ln.weight, ln.bias, ln.eps, pack)
-    f = token_linear(F.relu(token_linear(x, lin1.weight, lin1.bias)), lin2.weight, lin2.bias)
-    return add_layer_norm_small(x, f, ln)
-
-
-def attention8_forward(qkv, want_lse=False, batch_major=False):
-    """softmax(q k^T / sqrt(8)) v for 4 heads of 8 on the matrix cores (pmx_attn8_forward_layout): qkv [S, B, 96] bfloat16 ->
-    [S, B, 32] bfloat16 (+ log-sum-exp [B, 4, S] float32); with batch_major qkv is [B, S, 96] and the result [B, S, 32]."""
-    lib = _lib.load()
-    (B, S, _) = qkv.shape if batch_major else (qkv.shape[1], qkv.shape[0], 0)
-    qkv = qkv.contiguous()
-    out = torch.empty(qkv.shape[0], qkv.shape[1], 32, dtype=torch.bfloat16, device=qkv.device)
-    lse = torch.empty(B, 4, S, dtype=torch.float32, device=qkv.device) if want_lse else None
-    st = C.c_void_p(torch.cuda.current_stream(qkv.device).cuda_stream)
-    _lib.check(lib.pmx_attn8_forward_layout(qkv.data_ptr(), out.data_ptr(), lse.data_ptr() if want_lse else None, S, B,
-                                            1 if batch_major else 0, st), "pmx_attn8_forward")
-    return (out, lse) if want_lse else out
-
-
-class _Attention8(torch.autograd.Function):
-    """Differentiable wrapper of the MFMA attention kernels (pmx_attn8_forward_layout / pmx_attn8_backward_layout)."""
-
-    @staticmethod
-    def forward(ctx, qkv, batch_major):
-        out, lse = attention8_forward(qkv, want_lse=True, batch_major=batch_major)
-        ctx.save_for_backward(qkv.contiguous(), out, lse)
-        ctx.batch_major = batch_major
-        return out
-
-    @staticmethod
-    def backward(ctx, gout):
-        lib = _lib.load()
-        qkv, out, lse = ctx.saved_tensors
-        B, S = lse.shape[0], lse.shape[2]
-        gout = gout.contiguous().to(torch.bfloat16)
-        dqkv = torch.empty_like(qkv)
-        st = C.c_void_p(torch.cuda.current_stream(qkv.device).cuda_stream)
-        _lib.check(lib.pmx_attn8_backward_layout(qkv.data_ptr(), out.data_ptr(), gout.data_ptr(), lse.data_ptr(), dqkv.data_ptr(), S, B,
-                                                 1 if ctx.batch_major else 0, st), "pmx_attn8_backward")
-        return dqkv, None
-
-
-def attention8(qkv, batch_major=False):
-    return _Attention8.apply(qkv, batch_major)
-
-
-def pack_projector(w, b):
-    lib = _lib.load()
-    wf, bf = w.detach().float().contiguous(), b.detach().float().contiguous()
-    pack = torch.empty(_lib.PROJ_PACK_BYTES, dtype=torch.uint8, device=wf.device)
-    st = C.c_void_p(torch.cuda.current_stream(wf.device).cuda_stream)
-    _lib.check(lib.pmx_proj_pack(wf.data_ptr(), bf.data_ptr(), pack.data_ptr(), st), "pmx_proj_pack")
-    return pack
-
-
-class _Projector(torch.autograd.Function):
-    """tokens [B, H*W, 32] bf16 = conv3x3(8 -> 32)(obs) + bias + positional table, batch-major, through pmx_proj_forward / _backward
-    (csrc/pmx_actor.hip): the observation planes are read as they are (bytes), no cast, no layout copy, no library convolution."""
-
-    @staticmethod
-    def forward(ctx, obs, w, b, pe):
-        lib = _lib.load()
-        obs = obs.contiguous()
-        B, _, H, W = obs.shape
-        pack = pack_projector(w, b)
-        tok = torch.empty(B, H * W, 32, dtype=torch.bfloat16, device=obs.device)
-        st = C.c_void_p(torch.cuda.current_stream(obs.device).cuda_stream)
-        _lib.check(lib.pmx_proj_forward(obs.data_ptr(), actor_tower._OBS_CODE[obs.dtype], pack.data_ptr(), pe.data_ptr(), tok.data_ptr(), B, H, W, st),
-                   "pmx_proj_forward")
-        ctx.save_for_backward(obs)
-        ctx.dtypes = (w.dtype, b.dtype)
-        return tok
-
-    @staticmethod
-    def backward(ctx, dtok):
-        lib = _lib.load()
-        (obs,) = ctx.saved_tensors
-        B, _, H, W = obs.shape
-        dev = obs.device
-        dtok = dtok.to(torch.bfloat16).contiguous()
-        part = torch.empty(_lib.PROJ_PARTIAL_ROWS * _lib.PROJ_GRAD_ROW_FLOATS, dtype=torch.float32, device=dev)
-        dw = torch.empty(32, 8, 3, 3, dtype=torch.float32, device=dev)
-        db = torch.empty(32, dtype=torch.float32, device=dev)
-        st = C.c_void_p(torch.cuda.current_stream(dev).cuda_stream)
-        _lib.check(lib.pmx_proj_backward(obs.data_ptr(), actor_tower._OBS_CODE[obs.dtype], dtok.data_ptr(), part.data_ptr(), dw.data_ptr(), db.data_ptr(),
-                                         B, H, W, st), "pmx_proj_backward")
-        return None, dw.to(ctx.dtypes[0]), db.to(ctx.dtypes[1]), None
-
-
-def actor_head_sizes(H, W, B):
-    """-> (pack bytes, scratch bytes) of the first actor-head layer's kernels for B samples (pmx_actor_head_sizes)"""
-    pk, sc = C.c_int64(), C.c_int64()
-    _lib.check(_lib.load().pmx_actor_head_sizes(int(H), int(W), int(B), C.byref(pk), C.byref(sc)), "pmx_actor_head_sizes")
-    return pk.value, sc.value
-
-
-def pack_actor_head(w, H, W):
-    """The bfloat16 operand images of actor_head[0].weight (float32 [512, 32 H W], nn.Linear's own order): one kernel, one rounding."""
-    lib = _lib.load()
-    wf = w.detach().contiguous()
-    pack = torch.empty(actor_head_sizes(H, W, 0)[0], dtype=torch.uint8, device=wf.device)
-    st = C.c_void_p(torch.cuda.current_stream(wf.device).cuda_stream)
-    _lib.check(lib.pmx_actor_head_pack(wf.data_ptr(), pack.data_ptr(), int(H), int(W), st), "pmx_actor_head_pack")
-    return pack
-
-
-class _ActorHead(torch.autograd.Function):
-    """h [B, 512] bf16 = Linear(32 H W -> 512)(features) on the tower's channels-last features [B, H*W, 32] bf16, through
-    pmx_actor_head_forward / _backward (csrc/pmx_actor_head.hip): the weight is read in nn.Linear's (channel, cell) order and packed
-    cell-major by one kernel (no permuted copy of it or of its gradient), the weight and bias gradients come back float32 in the
-    parameters' own order.  `pack`: the packed weight of a caller that knows it is frozen (inference), else None."""
-
-    @staticmethod
-    def forward(ctx, feat, w, b, H, W, pack):
-        lib = _lib.load()
-        feat = feat.contiguous()
-        B, dev = feat.shape[0], feat.device
-        if pack is None:
-            pack = pack_actor_head(w, H, W)
-        bf = b.detach().contiguous()
-        h = torch.empty(B, 512, dtype=torch.bfloat16, device=dev)
-        # scratch belongs to THIS call (see actor_tower._ActorTower.backward)
-        scratch = torch.empty(actor_head_sizes(H, W, B)[1], dtype=torch.uint8, device=dev)
-        st = C.c_void_p(torch.cuda.current_stream(dev).cuda_stream)
-        _lib.check(lib.pmx_actor_head_forward(feat.data_ptr(), pack.data_ptr(), bf.data_ptr(), h.data_ptr(), scratch.data_ptr(), B, H, W, st),
-                   "pmx_actor_head_forward")
-        ctx.save_for_backward(feat, pack)
-        ctx.board = (H, W)
-        ctx.dtypes = (w.dtype, b.dtype)
-        return h
-
-    @staticmethod
-    def backward(ctx, dh):
-        lib = _lib.load()
-        feat, pack = ctx.saved_tensors
-        H, W = ctx.board
-        B, dev = feat.shape[0], feat.device
-        dh = dh.to(torch.bfloat16).contiguous()
-        dfeat = torch.empty_like(feat)
-        alloc = torch.zeros if B == 0 else torch.empty                    # (an empty batch launches nothing)
-        dw = alloc(512, 32 * H * W, dtype=torch.float32, device=dev)
-        db = alloc(512, dtype=torch.float32, device=dev)
-        scratch = torch.empty(actor_head_sizes(H, W, B)[1], dtype=torch.uint8, device=dev)
-        st = C.c_void_p(torch.cuda.current_stream(dev).cuda_stream)
-        _lib.check(lib.pmx_actor_head_backward(feat.data_ptr(), dh.data_ptr(), pack.data_ptr(), dfeat.data_ptr(), dw.data_ptr(), db.data_ptr(),
-                                               scratch.data_ptr(), B, H, W, st), "pmx_actor_head_backward")
-        return dfeat, dw.to(ctx.dtypes[0]), db.to(ctx.dtypes[1]), None, None, None
-
-
-class _ActorTail(torch.autograd.Function):
-    """logits = Linear_5(gelu(LayerNorm_512(h))) through pmx_actor_tail_forward / _backward (csrc/pmx_heads.hip): one launch each
-    way (+ a row sum) instead of LayerNorm, GELU, a skinny GEMM, their backward kernels, two bias reductions and the casts."""
-
-    @staticmethod
-    def forward(ctx, h, lnw, lnb, w2, b2, eps):
-        lib = _lib.load()
-        h = h.contiguous()
-        B = h.shape[0]
-        logits = torch.empty(B, 5, dtype=torch.float32, device=h.device)
-        stats = torch.empty(B, 2, dtype=torch.float32, device=h.device)
-        st = C.c_void_p(torch.cuda.current_stream(h.device).cuda_stream)
-        _lib.check(lib.pmx_actor_tail_forward(h.data_ptr(), 1 if h.dtype == torch.bfloat16 else 0, lnw.data_ptr(), lnb.data_ptr(), w2.data_ptr(),
-                                              b2.data_ptr(), logits.data_ptr(), stats.data_ptr(), B, float(eps), st), "pmx_actor_tail_forward")
-        ctx.save_for_backward(h, stats, lnw, lnb, w2)
-        return logits
-
-    @staticmethod
-    def backward(ctx, dlogits):
-        lib = _lib.load()
-        h, stats, lnw, lnb, w2 = ctx.saved_tensors
-        B = h.shape[0]
-        dlogits = dlogits.float().contiguous()
-        dh = torch.empty_like(h)
-        G = _lib.ACTOR_TAIL_GRAD_FLOATS
-        grad = torch.empty((1 + _lib.HEADS_PARTIAL_ROWS) * G, dtype=torch.float32, device=h.device)
-        st = C.c_void_p(torch.cuda.current_stream(h.device).cuda_stream)
-        (dlnw, dlnb, dw2, db2), wanted = _row0(grad, ((2568, 512), (3080, 512), (0, 2560), (2560, 5)), ctx.needs_input_grad[1:5])
-        with _PARTIAL_ROWS.defer(lib, grad, G, wanted, family="pmx_actor_tail"):
-            _lib.check(lib.pmx_actor_tail_backward(h.data_ptr(), 1 if h.dtype == torch.bfloat16 else 0, stats.data_ptr(), dlogits.data_ptr(),
-                                                   lnw.data_ptr(), lnb.data_ptr(), w2.data_ptr(), dh.data_ptr(), grad.data_ptr(), B, st), "pmx_actor_tail_backward")
-        return dh, dlnw, dlnb, dw2.view(5, 512), db2, None
-
-
-class _CriticTail(torch.autograd.Function):
-    """value = Linear_1(gelu(Linear_512(mean over tokens))) through pmx_critic_tail_forward / _backward: the mean pool, both
-    linears, the GELU and -- backwards -- the broadcast of the pooled gradient over the tokens and all four parameter gradients."""
-
-    @staticmethod
-    def forward(ctx, tokens, w1, b1, w2, b2):
-        lib = _lib.load()
-        tokens = tokens.contiguous()
-        B, S, _ = tokens.shape
-        value = torch.empty(B, dtype=torch.float32, device=tokens.device)
-        pooled = torch.empty(B, 32, dtype=torch.float32, device=tokens.device)
-        st = C.c_void_p(torch.cuda.current_stream(tokens.device).cuda_stream)
-        _lib.check(lib.pmx_critic_tail_forward(tokens.data_ptr(), w1.data_ptr(), b1.data_ptr(), w2.data_ptr(), b2.data_ptr(), value.data_ptr(),
-                                               pooled.data_ptr(), B, S, st), "pmx_critic_tail_forward")
-        ctx.save_for_backward(pooled, w1, b1, w2)
-        ctx.S = S
-        return value
-
-    @staticmethod
-    def backward(ctx, dvalue):
-        lib = _lib.load()
-        pooled, w1, b1, w2 = ctx.saved_tensors
-        B, S, dev = pooled.shape[0], ctx.S, pooled.device
-        dvalue = dvalue.float().contiguous()
-        dtok = torch.empty(B, S, 32, dtype=torch.bfloat16, device=dev)
-        scratch = torch.empty(2 * B * 512, dtype=torch.bfloat16, device=dev)
-        grad = torch.empty((1 + _lib.HEADS_PARTIAL_ROWS) * _lib.CRITIC_TAIL_GRAD_FLOATS, dtype=torch.float32, device=dev)
-        st = C.c_void_p(torch.cuda.current_stream(dev).cuda_stream)
-        (dw1, db1, dw2, db2), wanted = _row0(grad, ((0, 16384), (16384, 512), (16896, 512), (17408, 1)), ctx.needs_input_grad[1:5])
-        with _PARTIAL_ROWS.defer(lib, grad, _lib.CRITIC_TAIL_GRAD_FLOATS, wanted, family="pmx_critic_tail"):
-            _lib.check(lib.pmx_critic_tail_backward(pooled.data_ptr(), dvalue.data_ptr(), w1.data_ptr(), b1.data_ptr(), w2.data_ptr(), dtok.data_ptr(),
-                                                    scratch.data_ptr(), grad.data_ptr(), B, S, st), "pmx_critic_tail_backward")
-        return dtok, dw1.view(512, 32), db1, dw2.view(1, 512), db2
-
-
-def column_sums(t):
-    """t.sum over all but the last dimension, in float32: the HIP column-sum kernel for a contiguous bfloat16 tensor on the
-    GPU whose last dimension is a multiple of 8 (<= 256), torch's reduction otherwise."""
-    C_ = t.shape[-1]
-    if t.is_cuda and t.dtype == torch.bfloat16 and t.is_contiguous() and C_ % 8 == 0 and 8 <= C_ <= 256 and t.numel() >= C_ * 4096:
-        lib = _lib.load()
-        partial = torch.empty(_lib.COLSUM_BLOCKS, C_, dtype=torch.float32, device=t.device)
-        st = C.c_void_p(torch.cuda.current_stream(t.device).cuda_stream)
-        _lib.check(lib.pmx_colsum_bf16(t.data_ptr(), t.numel() // C_, C_, partial.data_ptr(), st), "pmx_colsum_bf16")
-        return partial.sum(0)
-    if t.dim() == 1:
-        return t.float()
-    return t.sum(dim=tuple(range(t.dim() - 1)), dtype=torch.float32)
-
-
-class _TokenLinear(torch.autograd.Function):
-    """F.linear on a token tensor [S, B, in] with the weight gradient computed as S batched GEMMs of depth B followed by
-    a sum over S.  hipBLASLt's choice for the flat [S*B, in]^T x [S*B, out] product (K = 630 k rows, a 32 x 128 result)
-    is a 16x32x512 tile that takes 0.4-0.6 ms per call on MI355X; eight of them were 12 % of the optimizer step."""
-
-    @staticmethod
-    def forward(ctx, x, weight, bias):
-        ctx.save_for_backward(x, weight)
-        return F.linear(x, weight, bias)
-
-    @staticmethod
-    def backward(ctx, gy):
-        x, weight = ctx.saved_tensors
-        gx = gy.matmul(weight.to(gy.dtype)) if ctx.needs_input_grad[0] else None
-        gw = torch.bmm(gy.transpose(1, 2), x.to(gy.dtype)).sum(0).to(weight.dtype) if ctx.needs_input_grad[1] else None
-        gb = column_sums(gy).to(weight.dtype) if ctx.needs_input_grad[2] else None
-        return gx, gw, gb
-
-
-def token_linear(x, weight, bias):
-    if x.dim() == 3 and torch.is_grad_enabled() and weight.requires_grad:
-        if x.is_cuda and torch.is_autocast_enabled():
-            dt = torch.get_autocast_gpu_dtype()
-            x, weight, bias = x.to(dt), weight.to(dt), bias.to(dt)
-        return _TokenLinear.apply(x, weight, bias)
-    return F.linear(x, weight, bias)
 
 
 class CriticEncoderLayer(nn.TransformerEncoderLayer):
@@ -697,68 +94,6 @@ class CriticEncoderLayer(nn.TransformerEncoderLayer):
         a = attention8(qkv, True) if torch.is_grad_enabled() else attention8_forward(qkv, batch_major=True)
         x = out_proj_add_layer_norm(x, a, mha.out_proj, self.norm1, p_out)
         return ffn_layer_norm(x, self.linear1, self.linear2, self.norm2, p_ffn)
-
-
-class _GN8Gelu(torch.autograd.Function):
-    """GELU(GroupNorm(h) (+ res)) with 8 channels per group through pmx_gn8_gelu_forward/backward."""
-
-    @staticmethod
-    def forward(ctx, h, res, w, b, groups, eps):
-        lib = _lib.load()
-        # channels-last bf16 tensors (what MIOpen's NHWC convolutions produce) take the NHWC kernels, anything else NCHW
-        cl = h.dtype == torch.bfloat16 and h.is_contiguous(memory_format=torch.channels_last) and not h.is_contiguous()
-        fmt = torch.channels_last if cl else torch.contiguous_format
-        h = h.contiguous(memory_format=fmt)
-        res = res.contiguous(memory_format=fmt) if res is not None else None
-        B, Cc = h.shape[0], h.shape[1]
-        HW = h.numel() // (B * Cc)
-        y = torch.empty_like(h)
-        mean = torch.empty(B * groups, dtype=torch.float32, device=h.device)
-        rstd = torch.empty(B * groups, dtype=torch.float32, device=h.device)
-        wf, bf = w.float().contiguous(), b.float().contiguous()
-        st = C.c_void_p(torch.cuda.current_stream(h.device).cuda_stream)
-        rp = res.data_ptr() if res is not None else None
-        if cl:
-            _lib.check(lib.pmx_gn8cl_gelu_forward(h.data_ptr(), rp, wf.data_ptr(), bf.data_ptr(), y.data_ptr(), mean.data_ptr(),
-                                                  rstd.data_ptr(), B, groups, HW, float(eps), st), "pmx_gn8cl_gelu_forward")
-        else:
-            _lib.check(lib.pmx_gn8_gelu_forward(h.data_ptr(), rp, wf.data_ptr(), bf.data_ptr(), y.data_ptr(), mean.data_ptr(),
-                                                rstd.data_ptr(), B, groups, HW, float(eps), 0 if h.dtype == torch.float32 else 1, st),
-                       "pmx_gn8_gelu_forward")
-        ctx.save_for_backward(h, res if res is not None else h.new_empty(0), wf, bf, mean, rstd)
-        ctx.has_res, ctx.groups, ctx.HW, ctx.cl, ctx.wdtype = res is not None, groups, HW, cl, w.dtype
-        return y
-
-    @staticmethod
-    def backward(ctx, gy):
-        lib = _lib.load()
-        h, res, wf, bf, mean, rstd = ctx.saved_tensors
-        gy = gy.contiguous(memory_format=torch.channels_last if ctx.cl else torch.contiguous_format)
-        B, Cc = h.shape[0], h.shape[1]
-        dh = torch.empty_like(h)
-        dres = torch.empty_like(h) if ctx.has_res else None
-        partial = torch.empty(B, Cc, 2, dtype=torch.float32, device=h.device)
-        st = C.c_void_p(torch.cuda.current_stream(h.device).cuda_stream)
-        rp, dp = (res.data_ptr(), dres.data_ptr()) if ctx.has_res else (None, None)
-        if ctx.cl:
-            _lib.check(lib.pmx_gn8cl_gelu_backward(h.data_ptr(), rp, gy.data_ptr(), wf.data_ptr(), bf.data_ptr(), mean.data_ptr(),
-                                                   rstd.data_ptr(), dh.data_ptr(), dp, partial.data_ptr(), B, ctx.groups, ctx.HW, st),
-                       "pmx_gn8cl_gelu_backward")
-        else:
-            _lib.check(lib.pmx_gn8_gelu_backward(h.data_ptr(), rp, gy.data_ptr(), wf.data_ptr(), bf.data_ptr(), mean.data_ptr(),
-                                                 rstd.data_ptr(), dh.data_ptr(), dp, partial.data_ptr(), B, ctx.groups, ctx.HW,
-                                                 0 if h.dtype == torch.float32 else 1, st), "pmx_gn8_gelu_backward")
-        g = partial.sum(0).to(ctx.wdtype)
-        return dh, dres, g[:, 0], g[:, 1], None, None
-
-
-def group_norm_gelu(h, res, gn):
-    """GELU(gn(h) (+ res)): the fused HIP kernels on the GPU when the group has 8 channels, torch ops otherwise."""
-    if (h.is_cuda and h.dim() == 4 and gn.num_channels == 8 * gn.num_groups and h.dtype in (torch.float32, torch.bfloat16)
-            and (res is None or res.dtype == h.dtype) and h.shape[2] * h.shape[3] <= 1024):
-        return _GN8Gelu.apply(h, res, gn.weight, gn.bias, gn.num_groups, gn.eps)
-    z = gn(h)
-    return F.gelu(z if res is None else z + res)
 
 
 class ResidualBlock(nn.Module):
@@ -900,13 +235,10 @@ class MAPPOAgent(nn.Module):
             HW = feat.shape[1]
             if self._fused_head_ok(lin, HW, feat.shape[0]):
                 pack = self.head_pack if not torch.is_grad_enabled() else None
-                h = _ActorHead.apply(feat, lin.weight, lin.bias, obs.shape[2], obs.shape[3], pack)
-                if self._fused_heads_ok(h):
-                    ln, out = self.actor_head[1], self.actor_head[3]
-                    return _ActorTail.apply(h, ln.weight, ln.bias, out.weight, out.bias, ln.eps)
-                return self.actor_head[1:](h)
-            w = lin.weight.view(lin.out_features, 32, HW).permute(0, 2, 1).reshape(lin.out_features, HW * 32)
-            h = F.linear(feat.reshape(feat.shape[0], HW * 32), w, lin.bias)
+                h = _ActorHead.apply(feat, lin.weight, lin.bias, obs.shape[2], obs.shape[3], pack)     # [B, 512] by _fused_head_ok
+            else:
+                w = lin.weight.view(lin.out_features, 32, HW).permute(0, 2, 1).reshape(lin.out_features, HW * 32)
+                h = F.linear(feat.reshape(feat.shape[0], HW * 32), w, lin.bias)
             if self._fused_heads_ok(h) and h.shape[1] == 512:
                 ln, out = self.actor_head[1], self.actor_head[3]
                 return _ActorTail.apply(h, ln.weight, ln.bias, out.weight, out.bias, ln.eps)
@@ -1022,7 +354,6 @@ class _PPOLossFn(torch.autograd.Function):
 
     @staticmethod
     def forward(ctx, logits, values, act, old_logp, adv, ret, clip_eps, ent_coef, vf_coef):
-        lib = _lib.load()
         logits, values = logits.contiguous(), values.contiguous()
         B, BV = logits.shape[0], values.shape[0]
         stats = torch.empty(5, dtype=torch.float32, device=logits.device)
@@ -1035,10 +366,9 @@ class _PPOLossFn(torch.autograd.Function):
             return None, float(v)
         cp, ch = scalar(clip_eps)
         ep, eh = scalar(ent_coef)
-        st = C.c_void_p(torch.cuda.current_stream(logits.device).cuda_stream)
-        _lib.check(lib.pmx_ppo_loss(logits.data_ptr(), 1 if logits.dtype == torch.bfloat16 else 0, values.data_ptr(), act.contiguous().data_ptr(),
-                                    old_logp.contiguous().data_ptr(), adv.contiguous().data_ptr(), ret.contiguous().data_ptr(), B, BV, cp, ep,
-                                    ch, eh, float(vf_coef), stats.data_ptr(), dlogits.data_ptr(), dvalues.data_ptr(), st), "pmx_ppo_loss")
+        _lib.call("pmx_ppo_loss", logits.data_ptr(), 1 if logits.dtype == torch.bfloat16 else 0, values.data_ptr(), act.contiguous().data_ptr(),
+                  old_logp.contiguous().data_ptr(), adv.contiguous().data_ptr(), ret.contiguous().data_ptr(), B, BV, cp, ep,
+                  ch, eh, float(vf_coef), stats.data_ptr(), dlogits.data_ptr(), dvalues.data_ptr(), _lib.stream(logits.device))
         ctx.save_for_backward(dlogits, dvalues)
         return stats
 
@@ -1190,7 +520,7 @@ class PPOLearner:
         self._graph = self._graphs = self._g_groups = None
         self._g_in = self._g_sc = self._g_stats = self._g_acc = self._g_acc_keys = self._g_batch = None
 
-    # the second-stage row sums of the gradient reductions folded into the gradient gather (mappo._PartialRows): eight small
+    # the second-stage row sums of the gradient reductions folded into the gradient gather (partial_rows.OWNER): eight small
     # launches less on the chains of the 512-sample step.  (A first version ran them on a third stream beside the next backward kernel
     # and LOST -- 1 380 against 1 995 steps/s: six fork / join pairs cost the captured graph more than the kernels cost the chain.)
     defer_row_sums = True
@@ -1204,25 +534,24 @@ class PPOLearner:
 
     def _gather_grads(self, flat, first):
         """pmx_flatten_sum_to_f32: the float32 / bfloat16 gradients `flat` into the float32 bucket from element `first` on, in one
-        launch; gradients that are still partial rows (mappo._PartialRows) are summed on the way."""
-        lib = _lib.load()
+        launch; gradients that are still partial rows (partial_rows.OWNER) are summed on the way."""
         n = len(flat)
+        owner = partial_rows.OWNER
         if any(not g.is_contiguous() for g in flat):
-            _PARTIAL_ROWS.flush()                            # (a copy would read rows that have not been added yet)
+            owner.flush()                                    # (a copy would read rows that have not been added yet)
             flat = [g.contiguous() for g in flat]
         src = (C.c_void_p * n)(*[g.data_ptr() for g in flat])
         isb = (C.c_uint8 * n)(*[1 if g.dtype == torch.bfloat16 else 0 for g in flat])
         cnt = (C.c_int32 * n)(*[g.numel() for g in flat])
-        pend = [_PARTIAL_ROWS.claim(g) for g in flat]
+        pend = [owner.claim(g) for g in flat]
         rows = (C.c_int32 * n)(*[r for r, _ in pend])
         stride = (C.c_int32 * n)(*[f for _, f in pend])
         offs, o = [], first
         for g in flat:
             offs.append(o); o += g.numel()
         off = (C.c_int64 * n)(*offs)
-        _PARTIAL_ROWS.settle()                               # (raises before anything reads a row 0 that nobody will sum)
-        st = C.c_void_p(torch.cuda.current_stream(self.bucket.grad.device).cuda_stream)
-        _lib.check(lib.pmx_flatten_sum_to_f32(n, src, isb, rows, stride, off, cnt, self.bucket.grad.data_ptr(), st), "pmx_flatten_sum_to_f32")
+        owner.settle()                                       # (raises before anything reads a row 0 that nobody will sum)
+        _lib.call("pmx_flatten_sum_to_f32", n, src, isb, rows, stride, off, cnt, self.bucket.grad.data_ptr(), _lib.stream(self.bucket.grad.device))
 
     def _backward_group(self, loss, lo, hi, retain):
         """Gradients of bucket.params[lo:hi] into their slice of the flat float32 bucket: one gathering copy instead of
@@ -1239,14 +568,14 @@ class PPOLearner:
         # out in its target's type).  Only then may the backward kernels leave partial rows behind for it.
         gather = grad.is_cuda and grad.dtype == torch.float32 and all(t.dtype in (torch.float32, torch.bfloat16) for t in targets)
         root, unit = loss_root(loss)
-        with _PARTIAL_ROWS.enabled(self.defer_row_sums and gather):
+        with partial_rows.OWNER.enabled(self.defer_row_sums and gather):
             grads = torch.autograd.grad(root, targets, grad_outputs=unit, allow_unused=True, retain_graph=retain)
         flat = [g.reshape(-1) if g is not None else torch.zeros(p.numel(), dtype=grad.dtype, device=grad.device)
                 for g, p in zip(grads, params)]
         if gather:
             self._gather_grads(flat, self._offsets[lo])
         else:
-            _PARTIAL_ROWS.flush()
+            partial_rows.OWNER.flush()
             torch.cat([g.to(grad.dtype) for g in flat], out=grad[self._offsets[lo]:self._offsets[hi]])
 
     def _reduce_slice(self, lo, hi):
@@ -1364,7 +693,6 @@ class PPOLearner:
         scalars_dev the bias-corrected step sizes are read from that device tensor (graph replay), else computed here from
         step_count, which the caller has already advanced.  The same launch refreshes the bfloat16 copy of the parameters (where
         there is one) and, given report_sums6, adds the objective's five scalars and the gradient norm to it."""
-        lib = _lib.load()
         dev = self.bucket.data.device
         if self._opt_scratch is None:
             self._opt_scratch = torch.empty(_lib.OPT_PARTIALS, dtype=torch.float64, device=dev)
@@ -1375,13 +703,12 @@ class PPOLearner:
             sp, a, b = None, self.lr / bc1, 1.0 / math.sqrt(bc2)
         else:
             sp, a, b = scalars_dev.data_ptr(), 0.0, 0.0
-        st = C.c_void_p(torch.cuda.current_stream(dev).cuda_stream)
-        _lib.check(lib.pmx_clip_adam_ema_tail(self.bucket.grad.data_ptr(), self.bucket.data.data_ptr(), self.exp_avg.data_ptr(),
-                                              self.exp_avg_sq.data_ptr(), self.ema.data_ptr(), self.bucket.numel, self._opt_scratch.data_ptr(),
-                                              sp, a, b, b1, b2, self.eps, MAX_GRAD_NORM, EMA_DECAY, self._opt_norm.data_ptr(),
-                                              self._sh16.data_ptr() if self._sh16 is not None else None,
-                                              reports5.data_ptr() if reports5 is not None else None,
-                                              report_sums6.data_ptr() if report_sums6 is not None else None, st), "pmx_clip_adam_ema_tail")
+        _lib.call("pmx_clip_adam_ema_tail", self.bucket.grad.data_ptr(), self.bucket.data.data_ptr(), self.exp_avg.data_ptr(),
+                  self.exp_avg_sq.data_ptr(), self.ema.data_ptr(), self.bucket.numel, self._opt_scratch.data_ptr(),
+                  sp, a, b, b1, b2, self.eps, MAX_GRAD_NORM, EMA_DECAY, self._opt_norm.data_ptr(),
+                  self._sh16.data_ptr() if self._sh16 is not None else None,
+                  reports5.data_ptr() if reports5 is not None else None,
+                  report_sums6.data_ptr() if report_sums6 is not None else None, _lib.stream(dev))
         self._bf16_fresh = self._sh16 is not None
         return self._opt_norm[0]
 
@@ -1533,10 +860,8 @@ class PPOLearner:
     def _set_graph_scalars(self, clip_eps, ent_coef, step):
         """The four values travel as kernel arguments of ONE launch: stream-ordered, no host staging buffer that could be
         recycled while a copy is still in flight."""
-        lib = _lib.load()
         arr = (C.c_float * 4)(*self._graph_scalar_values(clip_eps, ent_coef, step))
-        st = C.c_void_p(torch.cuda.current_stream(self._g_sc.device).cuda_stream)
-        _lib.check(lib.pmx_set_floats(self._g_sc.data_ptr(), arr, 4, st), "pmx_set_floats")
+        _lib.call("pmx_set_floats", self._g_sc.data_ptr(), arr, 4, _lib.stream(self._g_sc.device))
 
     def reset_report_sums(self):
         """Zeroes the running sums that the replayed steps keep of their reports."""
@@ -1561,7 +886,6 @@ class PPOLearner:
         static inputs: sources = the flat rollout tensors {obs, merged, act, logp, adv, ret} (rows = samples; merged rows =
         env-ticks), index = int64 device indices, rows_per_index = {name: m} (2 for the per-learner tensors of a paired
         minibatch whose index names env-tick pairs).  Returns the graph's stats tensors (valid until the next replay)."""
-        lib = _lib.load()
         names = ("obs", "merged", "act", "logp", "adv", "ret")
         n = len(names)
         VP, I32, I64 = C.c_void_p * n, C.c_int32 * n, C.c_int64 * n
@@ -1574,11 +898,10 @@ class PPOLearner:
             rb[k], m[k], nr[k] = row, rows_per_index[name], d_t.shape[0]
             assert index.numel() * rows_per_index[name] == d_t.shape[0], (name, index.numel(), d_t.shape)
         assert index.dtype == torch.int64 and index.is_contiguous()
-        st = C.c_void_p(torch.cuda.current_stream(index.device).cuda_stream)
         self.step_count += 1
         vals = self._graph_scalar_values(clip_eps, ent_coef, self.step_count)        # (they travel with the gather: one launch)
         arr = (C.c_float * 4)(*vals)
-        _lib.check(lib.pmx_gather_rows_set_floats(n, src, dst, idx, rb, m, nr, self._g_sc.data_ptr(), arr, 4, st), "pmx_gather_rows_set_floats")
+        _lib.call("pmx_gather_rows_set_floats", n, src, dst, idx, rb, m, nr, self._g_sc.data_ptr(), arr, 4, _lib.stream(index.device))
         self._replay()
         return self._g_stats
 

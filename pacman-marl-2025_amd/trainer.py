@@ -11,7 +11,6 @@ PMX_ACTION_APPROXQ_*), the current network, or a frozen EMA snapshot from the op
 heuristic teams of the reference's curriculum are wall-clock-bounded searches and out of scope).
 """
 import copy
-import ctypes as C
 from collections import deque
 
 import numpy as np
@@ -54,9 +53,8 @@ def merge_obs(a, b):
     if _plane_kernel_ok(a, b) and a.shape == b.shape:
         a, b = a.contiguous(), b.contiguous()
         out = torch.empty_like(a)
-        st = C.c_void_p(torch.cuda.current_stream(a.device).cuda_stream)
-        _lib.check(_lib.load().pmx_merge_obs(a.data_ptr(), b.data_ptr(), out.data_ptr(), a.shape[0], a.shape[2], a.shape[3],
-                                             _OBS_CODES[a.dtype], st), "pmx_merge_obs")
+        _lib.call("pmx_merge_obs", a.data_ptr(), b.data_ptr(), out.data_ptr(), a.shape[0], a.shape[2], a.shape[3], _OBS_CODES[a.dtype],
+                  _lib.stream(a.device))
         return out
     m = a.clone()
     m[:, 1] = torch.maximum(torch.maximum(a[:, 1], b[:, 1]), torch.zeros_like(a[:, 1]))
@@ -70,9 +68,8 @@ def canonicalize_obs(o):
     if _plane_kernel_ok(o):
         o = o.contiguous()
         out = torch.empty_like(o)
-        st = C.c_void_p(torch.cuda.current_stream(o.device).cuda_stream)
-        _lib.check(_lib.load().pmx_canonicalize_obs(o.data_ptr(), out.data_ptr(), o.shape[0], o.shape[2], o.shape[3],
-                                                    _OBS_CODES[o.dtype], st), "pmx_canonicalize_obs")
+        _lib.call("pmx_canonicalize_obs", o.data_ptr(), out.data_ptr(), o.shape[0], o.shape[2], o.shape[3], _OBS_CODES[o.dtype],
+                  _lib.stream(o.device))
         return out
     return torch.flip(o, dims=[-1])[..., [0, 1, 3, 2, 4, 5, 7, 6], :, :]
 
@@ -293,10 +290,8 @@ class VecMAPPOTrainer:
     def compute_gae(self):
         T, n = self.T, self.N * 2
         last = self.last_value.contiguous()                         # [N, 2]
-        st = C.c_void_p(torch.cuda.current_stream(self.device).cuda_stream)
-        _lib.check(self.env.lib.pmx_gae(self.rew_buf.data_ptr(), self.val_buf.data_ptr(), self.done_buf.data_ptr(),
-                                        last.data_ptr(), T, n, mappo.GAMMA, mappo.GAE_LAMBDA, self.adv_buf.data_ptr(),
-                                        self.ret_buf.data_ptr(), st), "pmx_gae")
+        _lib.call("pmx_gae", self.rew_buf.data_ptr(), self.val_buf.data_ptr(), self.done_buf.data_ptr(), last.data_ptr(), T, n, mappo.GAMMA,
+                  mappo.GAE_LAMBDA, self.adv_buf.data_ptr(), self.ret_buf.data_ptr(), _lib.stream(self.device))
 
     def update(self, max_steps=None):
         """The PPO epochs over the rollout buffers.  max_steps stops after that many optimizer steps (warm-up runs only)."""

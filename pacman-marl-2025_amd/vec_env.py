@@ -82,7 +82,7 @@ class PmxVecEnv:
         cfg.enable_bots = int(bool(bots))          # understand ACTION_BASELINE_* / ACTION_APPROXQ_* (in-kernel bot teams)
         self.handle = C.c_void_p()
         with torch.cuda.device(self.device):
-            _lib.check(self.lib.pmx_create(C.byref(cfg), C.byref(self.handle)), "pmx_create")
+            _lib.call("pmx_create", C.byref(cfg), C.byref(self.handle))
         N, H, W = self.n_envs, layout.height, layout.width
         self.n_emit = len(self.obs_agents)
         self.obs_shape = (8, H, W)
@@ -97,9 +97,6 @@ class PmxVecEnv:
         self._agent_obs = None
 
     # -- plumbing -------------------------------------------------------------------------------------------------
-    def _stream(self):
-        return C.c_void_p(torch.cuda.current_stream(self.device).cuda_stream)
-
     def _out(self, obs=True, obs_tensor=None):
         o = _lib.StepOut()
         t = obs_tensor if obs_tensor is not None else self.obs
@@ -133,8 +130,7 @@ class PmxVecEnv:
             assert m.shape == (self.n_envs,)
         out = self._out(obs=want_obs)
         with torch.cuda.device(self.device):
-            _lib.check(self.lib.pmx_reset(self.handle, m.data_ptr() if m is not None else None, C.byref(out),
-                                          self._stream()), "pmx_reset")
+            _lib.call("pmx_reset", self.handle, m.data_ptr() if m is not None else None, C.byref(out), _lib.stream(self.device))
         return self.obs, self.legal
 
     def step(self, actions, want_obs=True):
@@ -147,7 +143,7 @@ class PmxVecEnv:
         assert a.shape == (self.n_envs, 4)
         out = self._out(obs=want_obs)
         with torch.cuda.device(self.device):
-            _lib.check(self.lib.pmx_step(self.handle, a.data_ptr(), C.byref(out), self._stream()), "pmx_step")
+            _lib.call("pmx_step", self.handle, a.data_ptr(), C.byref(out), _lib.stream(self.device))
         return self.obs, self.reward, self.done, {"legal_actions": self.legal, "score_change": self.score_change,
                                                    "score": self.score, "agent": self.agent}
 
@@ -160,8 +156,7 @@ class PmxVecEnv:
             self._agent_obs = torch.empty((4, self.n_envs) + self.obs_shape, dtype=self.obs_torch_dtype, device=self.device)
         out = self._out(obs=want_obs, obs_tensor=self._agent_obs[agent])
         with torch.cuda.device(self.device):
-            _lib.check(self.lib.pmx_step_agent(self.handle, int(agent), a.data_ptr(), C.byref(out), self._stream()),
-                       "pmx_step_agent")
+            _lib.call("pmx_step_agent", self.handle, int(agent), a.data_ptr(), C.byref(out), _lib.stream(self.device))
         return self._agent_obs[agent] if want_obs else None
 
     def successor(self, agent, actions):
@@ -169,8 +164,7 @@ class PmxVecEnv:
         a = actions.to(device=self.device, dtype=torch.int8).contiguous()
         assert a.shape == (self.n_envs,)
         with torch.cuda.device(self.device):
-            _lib.check(self.lib.pmx_successor(self.handle, int(agent), a.data_ptr(), self.score_change.data_ptr(),
-                                              self._stream()), "pmx_successor")
+            _lib.call("pmx_successor", self.handle, int(agent), a.data_ptr(), self.score_change.data_ptr(), _lib.stream(self.device))
         return self.score_change
 
     def bot_query(self, agent, code, want_values=True):
@@ -183,15 +177,15 @@ class PmxVecEnv:
         action = torch.empty((N,), dtype=torch.int8, device=self.device)
         flags = torch.empty((N,), dtype=torch.uint8, device=self.device)
         with torch.cuda.device(self.device):
-            _lib.check(self.lib.pmx_bot_query(self.handle, int(agent), int(code), values.data_ptr() if want_values else None,
-                                              action.data_ptr(), flags.data_ptr(), self._stream()), "pmx_bot_query")
+            _lib.call("pmx_bot_query", self.handle, int(agent), int(code), values.data_ptr() if want_values else None, action.data_ptr(),
+                      flags.data_ptr(), _lib.stream(self.device))
         return values, action, flags
 
     def observe(self, want_obs=True, want_legal=True):
         """get_Observation of the current state for every emitted agent (gymPacMan.py:195-229) and/or the legal masks."""
         with torch.cuda.device(self.device):
-            _lib.check(self.lib.pmx_observe(self.handle, self.obs.data_ptr() if want_obs else None,
-                                            self.legal.data_ptr() if want_legal else None, self._stream()), "pmx_observe")
+            _lib.call("pmx_observe", self.handle, self.obs.data_ptr() if want_obs else None, self.legal.data_ptr() if want_legal else None,
+                      _lib.stream(self.device))
         return self.obs, self.legal
 
     def emit_team_obs(self, team_red, team_obs, merged=None):
@@ -202,18 +196,18 @@ class PmxVecEnv:
         if merged is not None:
             assert merged.shape == (N,) + self.obs_shape and merged.dtype == self.obs_torch_dtype and merged.is_contiguous()
         with torch.cuda.device(self.device):
-            _lib.check(self.lib.pmx_emit_team_obs(self.handle, int(bool(team_red)), team_obs.data_ptr(),
-                                                  merged.data_ptr() if merged is not None else None, self._stream()), "pmx_emit_team_obs")
+            _lib.call("pmx_emit_team_obs", self.handle, int(bool(team_red)), team_obs.data_ptr(),
+                      merged.data_ptr() if merged is not None else None, _lib.stream(self.device))
         return team_obs, merged
 
     # -- measurement ---------------------------------------------------------------------------------------------
     def profile_begin(self, max_launches):
-        _lib.check(self.lib.pmx_profile_begin(self.handle, int(max_launches)), "pmx_profile_begin")
+        _lib.call("pmx_profile_begin", self.handle, int(max_launches))
 
     def set_tuning(self, key, value):
         """Launch tuning (pmx_set_tuning): "expand_alt" (0 = always the same sweep direction, -1 = the default alternation)
         and "fused_min_envs" (step() runs the tick in one launch from this many envs on, -1 = one workgroup per CU)."""
-        _lib.check(self.lib.pmx_set_tuning(self.handle, key.encode(), int(value)), "pmx_set_tuning")
+        _lib.call("pmx_set_tuning", self.handle, key.encode(), int(value))
 
     def last_step_fused(self):
         """True when the last step() ran the whole tick in one launch (pmx_last_step_fused)."""
@@ -222,7 +216,7 @@ class PmxVecEnv:
     def profile_end(self):
         """-> dict(rule_ms, rule_launches, expand_ms, expand_launches): summed kernel times from HIP events."""
         rm, em, rn, en = C.c_double(), C.c_double(), C.c_int32(), C.c_int32()
-        _lib.check(self.lib.pmx_profile_end(self.handle, C.byref(rm), C.byref(rn), C.byref(em), C.byref(en)), "pmx_profile_end")
+        _lib.call("pmx_profile_end", self.handle, C.byref(rm), C.byref(rn), C.byref(em), C.byref(en))
         return dict(rule_ms=rm.value, rule_launches=rn.value, expand_ms=em.value, expand_launches=en.value)
 
     # -- state exchange ------------------------------------------------------------------------------------------
@@ -230,33 +224,30 @@ class PmxVecEnv:
         count = self.n_envs - first if count is None else count
         arr = (_lib.State * count)()
         with torch.cuda.device(self.device):
-            _lib.check(self.lib.pmx_get_state(self.handle, first, count, arr, self._stream()), "pmx_get_state")
+            _lib.call("pmx_get_state", self.handle, first, count, arr, _lib.stream(self.device))
         return arr
 
     def set_state(self, states, first=0):
         count = len(states)
         arr = states if isinstance(states, C.Array) else (_lib.State * count)(*states)
         with torch.cuda.device(self.device):
-            _lib.check(self.lib.pmx_set_state(self.handle, first, count, arr, self._stream()), "pmx_set_state")
+            _lib.call("pmx_set_state", self.handle, first, count, arr, _lib.stream(self.device))
 
     def layout_indices(self):
         """The layout of the pool each env is on right now (int32 numpy array [n_envs])."""
         out = np.zeros(self.n_envs, np.int32)
         with torch.cuda.device(self.device):
-            _lib.check(self.lib.pmx_get_layout_index(self.handle, out.ctypes.data_as(C.POINTER(C.c_int32)), self._stream()),
-                       "pmx_get_layout_index")
+            _lib.call("pmx_get_layout_index", self.handle, out.ctypes.data_as(C.POINTER(C.c_int32)), _lib.stream(self.device))
         return out
 
     def maze_distances(self, layout=0):
         """distanceCalculator.computeDistances for a layout -> (cells [n,2] int8, dist [n,n] uint8) on the GPU."""
         n = C.c_int32()
         with torch.cuda.device(self.device):
-            _lib.check(self.lib.pmx_maze_distances_layout(self.handle, layout, None, None, C.byref(n), self._stream()),
-                       "pmx_maze_distances")
+            _lib.call("pmx_maze_distances_layout", self.handle, layout, None, None, C.byref(n), _lib.stream(self.device))
             cells = torch.empty((n.value, 2), dtype=torch.int8, device=self.device)
             dist = torch.empty((n.value, n.value), dtype=torch.uint8, device=self.device)
-            _lib.check(self.lib.pmx_maze_distances_layout(self.handle, layout, cells.data_ptr(), dist.data_ptr(), C.byref(n),
-                                                          self._stream()), "pmx_maze_distances")
+            _lib.call("pmx_maze_distances_layout", self.handle, layout, cells.data_ptr(), dist.data_ptr(), C.byref(n), _lib.stream(self.device))
         return cells, dist
 
 

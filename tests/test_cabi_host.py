@@ -47,6 +47,59 @@ def test_argument_errors_without_gpu():
     assert lib.pmx_obs_shape(None, None, None, None, None) == -1
 
 
+def _header_constants():
+    """{NAME: value} of every `#define PMX_<NAME> <integer>` of include/pmx.h (a negative one is written `(-n)`)."""
+    src = open(os.path.join(ROOT, "include", "pmx.h")).read()
+    found = re.findall(r"^[ \t]*#[ \t]*define[ \t]+PMX_([A-Z0-9_]+)[ \t]+(\(-\d+\)|\d+)[ \t]*(?:/\*.*)?$", src, flags=re.M)
+    return {name: int(text.strip("()")) for name, text in found}
+
+
+SIZES = ("MAX_DIM", "COLSUM_BLOCKS", "LN32_PARTIAL_ROWS", "ACTOR_PACK_BYTES", "ACTOR_GRAD_FLOATS", "GRAD_PARTIAL_ROWS", "OPT_PARTIALS",
+         "FFN_PACK_BYTES", "FFN_GRAD_FLOATS", "TOK96_PACK_BYTES", "TOK96_GRAD_FLOATS", "TOK32_PACK_BYTES", "TOK32_GRAD_FLOATS",
+         "HEADS_PARTIAL_ROWS", "ACTOR_TAIL_GRAD_FLOATS", "CRITIC_TAIL_GRAD_FLOATS")
+PROJ = ("PROJ_PACK_BYTES", "PROJ_PARTIAL_ROWS", "PROJ_GRAD_ROW_FLOATS")
+ACTIONS = ("ACTION_RANDOM_LEGAL", "ACTION_BASELINE_OFFENSE", "ACTION_BASELINE_DEFENSE", "ACTION_APPROXQ_OFFENSE", "ACTION_APPROXQ_DEFENSE")
+
+
+def test_binding_constants_match_header():
+    """Every size the binding mirrors by hand is the header's: a smaller one is a buffer that a kernel writes past."""
+    import pmx
+    L = pmx._lib
+    header = _header_constants()
+    covered = set()
+    for name, value in header.items():
+        for attr in (name, "PMX_" + name):              # (_lib keeps the prefix on PMX_MAX_DIM only)
+            if hasattr(L, attr):
+                assert getattr(L, attr) == value, f"_lib.{attr} = {getattr(L, attr)}, include/pmx.h says {value}"
+                covered.add(name)
+    missing = set(SIZES + PROJ + ACTIONS) - covered
+    assert not missing, f"not compared (no such define, or no such _lib attribute): {sorted(missing)}"
+    assert all(header[n] < 0 for n in ACTIONS)
+
+
+def test_call_labels_the_error_with_the_function_name():
+    import pmx
+    with pytest.raises(pmx.PmxError) as e:
+        pmx._lib.call("pmx_obs_shape", None, None, None, None, None)
+    assert "pmx_obs_shape" in str(e.value) and "null env" in str(e.value)
+
+
+def test_one_call_idiom_in_the_package():
+    """The return-code check and torch's stream handle are spelled once, in _lib.py (a text search of the package's own Python)."""
+    pkg = os.path.join(ROOT, "pacman-marl-2025_amd")
+    seen = 0
+    for dp, _, files in os.walk(pkg):
+        for f in files:
+            if f.endswith(".py") and f != "_lib.py":
+                txt = open(os.path.join(dp, f)).read()
+                seen += 1
+                assert "_lib.check(" not in txt, f"{f}: use _lib.call(name, ...)"
+                assert "cuda_stream" not in txt, f"{f}: use _lib.stream(device)"
+    assert seen >= 10
+    own = open(os.path.join(pkg, "_lib.py")).read()
+    assert "def call(" in own and "cuda_stream" in own
+
+
 @pytest.mark.parametrize("name,starts,food", [
     ("tinyCapture", [(8, 1), (12, 1), (9, 1), (13, 1)], 22),
     ("smallCapture", [(5, 1), (8, 9), (5, 9), (8, 1)], 28),

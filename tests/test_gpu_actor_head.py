@@ -1,5 +1,5 @@
 """The first actor-head layer's kernels (csrc/pmx_actor_head.hip: pmx_actor_head_pack / _forward / _backward) through the C ABI,
-per ELEMENT against the float64 reference of tests/_head_ref.py, and the model-level path that uses them (mappo._ActorHead,
+per ELEMENT against the float64 reference of tests/_head_ref.py, and the model-level path that uses them (actor_head._ActorHead,
 MAPPOAgent.fused_head, PPOLearner).
 
 Bounds (derived in tests/_head_ref.py, none tuned): an output that adds n terms a_k b_k in float32 lies within
@@ -211,19 +211,19 @@ def _model(H, W, seed):
 
 
 def _tail(m, h):
-    from pmx import mappo
+    from pmx import actor_head
     ln, out = m.actor_head[1], m.actor_head[3]
-    return mappo._ActorTail.apply(h, ln.weight, ln.bias, out.weight, out.bias, ln.eps)
+    return actor_head._ActorTail.apply(h, ln.weight, ln.bias, out.weight, out.bias, ln.eps)
 
 
 @pytest.mark.parametrize("H,W,B", [(11, 14, 64), (5, 9, 37)])
 def test_wrapper_and_logits_agree_with_the_library_path(H, W, B):
-    """h of mappo._ActorHead against the permuted-weight F.linear it replaces, on the tower's own features: within the project's
+    """h of actor_head._ActorHead against the permuted-weight F.linear it replaces, on the tower's own features: within the project's
     2 bfloat16 ulps of the largest h (2 * 2**-8 max |h|).  MAPPOAgent.logits must then return EXACTLY the tail of that h (the kernels
     are deterministic, so any other operand, pack or tail input shows as a different bit) on each of its kernel branches -- with
     gradients (a pack per call) and without gradients on a frozen head_pack -- and the library path's logits everywhere else:
     fused_head off, no gradients and no frozen pack, a batch above fused_head_max_batch."""
-    from pmx import actor_tower, mappo
+    from pmx import actor_head, actor_tower, mappo
     m = _model(H, W, 3)
     m.fused_head_max_batch = 512         # (the class default keeps the library at every batch: DESIGN.md section 5)
     with torch.no_grad():
@@ -233,7 +233,7 @@ def test_wrapper_and_logits_agree_with_the_library_path(H, W, B):
     with torch.autocast(device_type="cuda", dtype=torch.bfloat16):
         with torch.no_grad():
             feat = actor_tower.actor_tower(m.actor_backbone, obs)
-            h_new = mappo._ActorHead.apply(feat, lin.weight, lin.bias, H, W, None)
+            h_new = actor_head._ActorHead.apply(feat, lin.weight, lin.bias, H, W, None)
             wperm = lin.weight.view(512, 32, HW).permute(0, 2, 1).reshape(512, HW * 32)
             h_lib = torch.nn.functional.linear(feat.reshape(B, HW * 32), wperm, lin.bias)
             want_new, want_lib = _tail(m, h_new), _tail(m, h_lib)

@@ -1143,7 +1143,7 @@ def test_learner_gradient_with_and_without_the_folded_row_sums_and_the_unit_root
     """The learner's gradient path (the fused objective differentiated as a 5-vector against the constant unit gradient, second-stage
     row sums folded into the gather) against the plain one (loss.backward() semantics: `torch.autograd.grad(loss, ...)`, a kernel per
     reduction): same gradients up to the order of the float32 row sums and of the tower's LDS adds."""
-    from pmx import mappo
+    from pmx import mappo, partial_rows
     H, W, B = 11, 14, 256
     torch.manual_seed(4)
     obs = (torch.rand(B, 8, H, W, device="cuda") < 0.2).to(torch.uint8)
@@ -1163,7 +1163,7 @@ def test_learner_gradient_with_and_without_the_folded_row_sums_and_the_unit_root
         L.bucket.grad.zero_()
         L._backward_into_bucket(loss)
         grads[folded] = L.bucket.grad.clone()
-        assert not mappo._PARTIAL_ROWS.pending
+        assert not partial_rows.OWNER.pending
     rel = float((grads[True] - grads[False]).norm() / grads[False].norm())
     assert 0.0 < float(grads[False].norm()) and rel <= 2e-3, rel
 
@@ -1178,13 +1178,13 @@ def _encoder_layer_and_tokens():
 
 
 def test_partial_rows_of_a_layer_used_once_are_all_claimed_and_summed_by_the_gather():
-    """mappo._PartialRows as PPOLearner._backward_group drives it: with deferral on every one of the layer's twelve parameter
+    """partial_rows._PartialRows as PPOLearner._backward_group drives it: with deferral on every one of the layer's twelve parameter
     gradients is claimed, settle() passes, and pmx_flatten_sum_to_f32 delivers the gradients the non-deferred path computes (same
     bound as the learner test above: the two differ in the order of the float32 row sums only)."""
     import ctypes as C
-    from pmx import _lib
+    from pmx import _lib, partial_rows
     mappo, layer, x, params = _encoder_layer_and_tokens()
-    lib, pr = _lib.load(), mappo._PARTIAL_ROWS
+    lib, pr = _lib.load(), partial_rows.OWNER
     assert len(params) == 12
 
     def loss():
@@ -1218,8 +1218,9 @@ def test_partial_rows_of_a_layer_used_twice_raise_instead_of_gathering_unsummed_
     """A layer applied twice in one loss: autograd adds the two row-0 views of every parameter before anyone has summed their rows,
     so nothing it hands back is a pending slice -- settle() raises (an ordinary Python error, before any launch reads the buffers).
     With deferral off the same loss has finite gradients."""
+    from pmx import partial_rows
     mappo, layer, x, params = _encoder_layer_and_tokens()
-    pr = mappo._PARTIAL_ROWS
+    pr = partial_rows.OWNER
 
     def loss():
         return layer.forward_batch_major(layer.forward_batch_major(x)).float().square().sum()
@@ -1270,7 +1271,7 @@ def test_fused_actor_tail_matches_torch(B):
     """pmx_actor_tail_forward / _backward (LayerNorm_512 -> GELU -> Linear_5 of actor_head, pacman_mappo_resnet.py:117-122)
     against torch in float64 on the operands the kernel uses (hidden activations and W2 rounded to bf16): logits within 2e-3
     absolute (bf16 activations of O(1) summed over 512 terms), input and parameter gradients within 2e-2 of their largest entry."""
-    from pmx import mappo
+    from pmx import actor_head, mappo
     torch.manual_seed(B)
     h = (torch.randn(B, 512, device="cuda") * 1.5 + 0.2).to(torch.bfloat16).requires_grad_(True)
     ln = torch.nn.LayerNorm(512).cuda()
@@ -1279,7 +1280,7 @@ def test_fused_actor_tail_matches_torch(B):
         ln.weight.copy_(1.0 + 0.2 * torch.randn(512, device="cuda")); ln.bias.copy_(0.1 * torch.randn(512, device="cuda"))
         out.weight.mul_(3.0)
     dl = torch.randn(B, 5, device="cuda")
-    logits = mappo._ActorTail.apply(h, ln.weight, ln.bias, out.weight, out.bias, ln.eps)
+    logits = actor_head._ActorTail.apply(h, ln.weight, ln.bias, out.weight, out.bias, ln.eps)
     got = torch.autograd.grad((logits * dl).sum(), [h, ln.weight, ln.bias, out.weight, out.bias])
     bf = lambda t: t.to(torch.bfloat16).double()
     h2 = h.detach().double().requires_grad_(True)
@@ -1301,14 +1302,14 @@ def test_fused_actor_tail_matches_torch(B):
 def test_fused_critic_tail_matches_torch(B, S):
     """pmx_critic_tail_forward / _backward (mean over tokens -> Linear_512 -> GELU -> Linear_1, pacman_mappo_resnet.py:143-147, :169)
     against torch in float64 with the kernel's bf16 roundings made explicit."""
-    from pmx import mappo
+    from pmx import critic_kernels, mappo
     torch.manual_seed(B + S)
     tok = (torch.randn(B, S, 32, device="cuda") * 1.2 + 0.3 * torch.randn(B, 1, 32, device="cuda")).to(torch.bfloat16).requires_grad_(True)
     l1, l2 = torch.nn.Linear(32, 512).cuda(), torch.nn.Linear(512, 1).cuda()
     with torch.no_grad():
         l1.weight.mul_(2.0); l1.bias.add_(0.1 * torch.randn(512, device="cuda")); l2.weight.mul_(4.0)
     dv = torch.randn(B, device="cuda")
-    val = mappo._CriticTail.apply(tok, l1.weight, l1.bias, l2.weight, l2.bias)
+    val = critic_kernels._CriticTail.apply(tok, l1.weight, l1.bias, l2.weight, l2.bias)
     got = torch.autograd.grad((val * dv).sum(), [tok, l1.weight, l1.bias, l2.weight, l2.bias])
     ste = lambda t: t + (t.detach().to(torch.bfloat16).double() - t.detach())
     t2 = tok.detach().double().requires_grad_(True)
@@ -1350,7 +1351,7 @@ def test_fused_projector_matches_torch(layout, B, dtype):
     tokens) against torch in float64 with the kernel's roundings made explicit (bf16 weights, the convolution + bias rounded to bf16,
     then the bf16 sum with the bf16 table): tokens within one bf16 ulp of the largest, weight / bias gradients within 1e-2."""
     import pmx
-    from pmx import mappo
+    from pmx import critic_kernels, mappo
     lay = pmx.get_layout(layout)
     H, W = lay.height, lay.width
     torch.manual_seed(B)
@@ -1362,7 +1363,7 @@ def test_fused_projector_matches_torch(layout, B, dtype):
     obs = (torch.rand(B, 8, H, W, device="cuda", generator=g) < 0.25).float()
     obs[:, 1] *= torch.randint(1, 6, (B, 1, 1), device="cuda", generator=g).float()
     pe = m._pe_table(H, W, obs.device)
-    tok = mappo._Projector.apply(obs.to(dtype), conv.weight, conv.bias, pe)
+    tok = critic_kernels._Projector.apply(obs.to(dtype), conv.weight, conv.bias, pe)
     assert tok.shape == (B, H * W, 32) and tok.dtype == torch.bfloat16
     dt = torch.randn(B, H * W, 32, device="cuda", generator=g).to(torch.bfloat16)
     dw, db = torch.autograd.grad((tok.float() * dt.float()).sum(), [conv.weight, conv.bias])

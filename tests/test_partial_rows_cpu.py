@@ -1,10 +1,10 @@
-"""mappo._PartialRows -- the owner of the deferred row sums -- on CPU tensors with a stand-in library: which gradients it takes for
+"""partial_rows._PartialRows -- the owner of the deferred row sums -- on CPU tensors with a stand-in library: which gradients it takes for
 pending slices of a partial-row buffer (exact storage, offset and size), and that settle() raises when a slice handed out by a
 backward did not come back from autograd as that very view (a parameter reached twice, a tensor hook)."""
 import pytest
 import torch
 
-from pmx import mappo
+from pmx import partial_rows
 
 FLOATS = 9                              # floats per row: dw [2][3] at 0, db [3] at 6
 SLICES = ((0, 6), (6, 3))
@@ -28,9 +28,9 @@ class StubLib:
 @pytest.fixture
 def pr():
     """A fresh owner in place of the module's, so that the autograd function below and the test talk to the same one."""
-    old, mappo._PARTIAL_ROWS = mappo._PARTIAL_ROWS, mappo._PartialRows()
-    yield mappo._PARTIAL_ROWS
-    mappo._PARTIAL_ROWS = old
+    old, partial_rows.OWNER = partial_rows.OWNER, partial_rows._PartialRows()
+    yield partial_rows.OWNER
+    partial_rows.OWNER = old
 
 
 class _Affine(torch.autograd.Function):
@@ -48,7 +48,7 @@ class _Affine(torch.autograd.Function):
         (x,) = ctx.saved_tensors
         grad = torch.empty((1 + ROWS) * FLOATS)
         wanted = [sl for sl, need in zip(SLICES, ctx.needs_input_grad[1:3]) if need]
-        with mappo._PARTIAL_ROWS.defer(_Affine.lib, grad, FLOATS, wanted, family="stub_affine"):
+        with partial_rows.OWNER.defer(_Affine.lib, grad, FLOATS, wanted, family="stub_affine"):
             full = torch.cat([(dy * x).reshape(-1), dy.expand(3)])
             rows = grad.view(1 + ROWS, FLOATS)
             rows[1], rows[2] = 0.25 * full, 0.75 * full

@@ -5,7 +5,7 @@ import argparse, json, os, sys, time
 import torch
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 import pmx
-from pmx import mappo
+from pmx import critic_kernels, mappo
 
 ap = argparse.ArgumentParser()
 ap.add_argument("--batch", type=int, default=8192)
@@ -47,11 +47,11 @@ def fwd_bwd():
 res = {"batch": B, "fwd_ms": timeit(fwd), "fwd_bwd_ms": timeit(fwd_bwd)}
 layer = m.critic_transformer.layers[0]
 x = torch.randn(H * W, B, 32, device=dev).to(torch.bfloat16).requires_grad_(True)
-res["ffn_kernel_fwd_ms"] = timeit(lambda: mappo.ffn_layer_norm(x.detach(), layer.linear1, layer.linear2, layer.norm2))
+res["ffn_kernel_fwd_ms"] = timeit(lambda: critic_kernels.ffn_layer_norm(x.detach(), layer.linear1, layer.linear2, layer.norm2))
 
 
 def ffn_fb():
-    y = mappo.ffn_layer_norm(x, layer.linear1, layer.linear2, layer.norm2)
+    y = critic_kernels.ffn_layer_norm(x, layer.linear1, layer.linear2, layer.norm2)
     torch.autograd.grad(y.float().sum(), [x, layer.linear1.weight])
 
 

@@ -1,6 +1,6 @@
 #!/usr/bin/env python3
 """Times the first actor-head layer, Linear(32 H W -> 512), both ways: the library path MAPPOAgent.logits keeps with fused_head off
-(a permuted copy of the bfloat16 shadow weight + F.linear, autograd's backward) against mappo._ActorHead (csrc/pmx_actor_head.hip:
+(a permuted copy of the bfloat16 shadow weight + F.linear, autograd's backward) against actor_head._ActorHead (csrc/pmx_actor_head.hip:
 pack + products), in ONE process with the arms alternating, on device events.  The library arm is timed twice (lib_a, lib_b) so that
 its own run-to-run spread stands beside every comparison.  The entry points of the new kernels are also timed alone through the C ABI
 (pack, forward, backward = the input-gradient and the weight/bias-gradient products together).
@@ -21,7 +21,7 @@ def main():
     args = ap.parse_args()
     import torch
     import torch.nn.functional as F
-    from pmx import _lib, mappo
+    from pmx import _lib, actor_head
     lib = _lib.load()
     dev = torch.device("cuda")
     per_round = 20
@@ -65,7 +65,7 @@ def main():
             return F.linear(feat.reshape(B, K), w, b16)
 
         def new_fwd():
-            return mappo._ActorHead.apply(feat, w32, b32, H, W, None)
+            return actor_head._ActorHead.apply(feat, w32, b32, H, W, None)
 
         def lib_fb():
             return torch.autograd.grad(lib_fwd(), [feat, w16, b16], dh)
@@ -87,7 +87,7 @@ def main():
                 emit({"shape": label, "H": H, "W": W, "B": B, "what": "forward+backward", "us": t,
                       "tflops": {k: 3 * flop / v * 1e-6 for k, v in t.items()}})
         # the entry points alone
-        pk, sc = mappo.actor_head_sizes(H, W, B)
+        pk, sc = actor_head.actor_head_sizes(H, W, B)
         pack = torch.empty(pk, dtype=torch.uint8, device=dev)
         scratch = torch.empty(sc, dtype=torch.uint8, device=dev)
         h = torch.empty(B, 512, dtype=torch.bfloat16, device=dev)
