@@ -319,6 +319,32 @@ int pmx_ppo_loss(const void *logits_dev, int32_t logits_bf16, const float *value
                  const float *clip_eps_dev, const float *ent_coef_dev, float clip_eps, float ent_coef, float vf_coef,
                  float *stats_dev, void *dlogits_dev, float *dvalues_dev, void *stream);
 
+/* Legal-action masks for the policy (opt-in; the default path samples from all five logits, as the reference does).  One int32
+ * word per row: bit a set = action a legal (0 N, 1 E, 2 S, 3 W, 4 Stop; the bits of pmx_step_out.legal_dev, widened from uint8 to
+ * int32 because pmx_gather_rows moves rows in multiples of 4 bytes, and in the learner's canonical frame).  Only the low five bits
+ * are read, a NULL mask pointer means everything is legal, and bit 4 (Stop) is always treated as set.
+ * Stale masks: the env's masks describe the state at the START of a tick.  An agent eaten by an earlier mover of the same tick acts
+ * from its start cell under a mask computed for the cell it stood on; the env's illegal-becomes-Stop rule then applies to what it
+ * chose.  The objective stays consistent because it is evaluated under the stored mask the action was drawn under.
+ *
+ * pmx_policy_sample: one action per row of logits_dev [B][5] (float32, or bfloat16 when logits_bf16 != 0), one thread per row,
+ * float32 arithmetic: z_k = the logit, or -inf where action k is masked out; zmax = max_k z_k; p_k = expf(z_k - zmax);
+ * total = p_0 + ... + p_4 added in that order; logp = (z_a - zmax) - logf(total).  The draw is counter based, like the bots':
+ *     h = lowbias32(seed ^ row * 0x9E3779B1 ^ counter * 0x85EBCA77 ^ 0x6A09E667),  t = (float)(h >> 8) * 0x1p-24f * total;
+ * the action is the first legal k whose running sum p_0 + ... + p_k exceeds t, the last legal k if none does.  greedy != 0: the
+ * legal action with the largest z, the lowest index on ties, no draw.  The same (seed, counter) on the same inputs gives the same
+ * bits.  action_dev [B] int64; logp_dev [B] float32, may be NULL.  A null logits or action pointer or B < 0 is PMX_ERR_INVALID;
+ * B == 0 is PMX_OK, with nothing launched or written. */
+int pmx_policy_sample(const void *logits_dev, int32_t logits_bf16, const int32_t *legal_dev, int64_t B, uint32_t seed,
+                      uint32_t counter, int32_t greedy, int64_t *action_dev, float *logp_dev, void *stream);
+/* pmx_ppo_loss under masks: the effective mask of row i is legal_dev[i] | 1 << act_dev[i] | 0x10 (a stored action is never treated
+ * as illegal).  Illegal logits enter as -inf: out of the log-sum-exp, probability 0, nothing added to the entropy, dlogits exactly
+ * 0.  With every bit set (or legal_dev NULL) the outputs are pmx_ppo_loss's bit for bit. */
+int pmx_ppo_loss_masked(const void *logits_dev, int32_t logits_bf16, const float *values_dev, const int64_t *act_dev,
+                        const int32_t *legal_dev, const float *old_logp_dev, const float *adv_dev, const float *ret_dev, int32_t B,
+                        int32_t BV, const float *clip_eps_dev, const float *ent_coef_dev, float clip_eps, float ent_coef,
+                        float vf_coef, float *stats_dev, void *dlogits_dev, float *dvalues_dev, void *stream);
+
 /* Minibatch assembly in one launch: for t < n (n <= 8), dst[t] row r = src[t] row (idx[t][r / m] * m + r % m), m =
  * rows_per_index[t], rows of row_bytes[t] bytes (a multiple of 4; multiples of 16 need 16-byte aligned bases), n_rows[t] output
  * rows.  The arrays of pointers and sizes are HOST arrays; the pointers in them are device pointers.  (What

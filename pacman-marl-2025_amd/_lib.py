@@ -97,6 +97,9 @@ PROTOTYPES = [
     ("pmx_attn8_forward", C.c_int, [_VP, _VP, _VP, _I32, _I32, _VP]),
     ("pmx_attn8_backward", C.c_int, [_VP, _VP, _VP, _VP, _VP, _I32, _I32, _VP]),
     ("pmx_ppo_loss", C.c_int, [_VP, _I32, _VP, _VP, _VP, _VP, _VP, _I32, _I32, _VP, _VP, C.c_float, C.c_float, C.c_float, _VP, _VP, _VP, _VP]),
+    ("pmx_ppo_loss_masked", C.c_int, [_VP, _I32, _VP, _VP, _VP, _VP, _VP, _VP, _I32, _I32, _VP, _VP, C.c_float, C.c_float, C.c_float, _VP, _VP,
+                                      _VP, _VP]),
+    ("pmx_policy_sample", C.c_int, [_VP, _I32, _VP, C.c_int64, C.c_uint32, C.c_uint32, _I32, _VP, _VP, _VP]),
     ("pmx_clip_adam_ema", C.c_int, [_VP, _VP, _VP, _VP, _VP, C.c_int64, _VP, _VP, C.c_float, C.c_float, C.c_float, C.c_float, C.c_float,
                                     C.c_float, C.c_float, _VP, _VP]),
     ("pmx_clip_adam_ema_tail", C.c_int, [_VP, _VP, _VP, _VP, _VP, C.c_int64, _VP, _VP, C.c_float, C.c_float, C.c_float, C.c_float, C.c_float,

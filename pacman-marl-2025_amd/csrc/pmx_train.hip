@@ -1569,6 +1569,95 @@ __global__ __launch_bounds__(1024) void pmx_ppo_loss_kernel(const LT *__restrict
     }
 }
 
+// pmx_ppo_loss_kernel under legal-action masks (include/pmx.h, "legal-action masks"): `legal` holds one word per row, bit k = action
+// k legal.  An action outside the row's effective mask enters as -inf -- out of the log-sum-exp, probability 0, nothing added to
+// the entropy -- and its dlogits is written as an exact 0 (the general formula would form 0 * inf there).  Everything else is the
+// arithmetic above, statement for statement, so a word with every bit set gives the unmasked kernel's bits.  It is a kernel of its
+// own and not a flag on, or a helper shared with, the one above: both of those changed the unmasked kernel's code (register
+// allocation and operand order; DESIGN.md section 5, "Legal-action masks"), and the default path is to stay instruction for instruction.
+template <typename LT>
+__global__ __launch_bounds__(1024) void pmx_ppo_loss_masked_kernel(const LT *__restrict__ logits, const float *__restrict__ values,
+                                                                  const int64_t *__restrict__ act, const int32_t *__restrict__ legal,
+                                                                  const float *__restrict__ old_logp, const float *__restrict__ adv,
+                                                                  const float *__restrict__ ret, int B, int BV, const float *clip_dev,
+                                                                  const float *ent_dev, float clip_host, float ent_host, float vf_coef,
+                                                                  float *__restrict__ stats, LT *__restrict__ dlogits,
+                                                                  float *__restrict__ dvalues)
+{
+    __shared__ double red[16];
+    const float clip_eps = clip_dev ? *clip_dev : clip_host, ent_coef = ent_dev ? *ent_dev : ent_host;
+    const int tid = threadIdx.x;
+    // advantage statistics: mean, then the unbiased variance around it (two passes, as torch.std)
+    double s = 0.0;
+    for (int i = tid; i < B; i += 1024) s += (double)adv[i];
+    const double mean = block_sum_1024(s, red) / (double)B;
+    double ss = 0.0;
+    for (int i = tid; i < B; i += 1024) { const double d = (double)adv[i] - mean; ss += d * d; }
+    const double var = block_sum_1024(ss, red) / (double)(B > 1 ? B - 1 : 1);
+    const float a_mean = (float)mean, a_den = (float)sqrt(var) + 1e-8f;
+    const float invB = 1.0f / (float)B;
+    const bool paired = BV * 2 == B;
+    double pg_s = 0.0, ent_s = 0.0, clip_s = 0.0, vl_s = 0.0;
+    for (int i = tid; i < B; i += 1024) {
+        float z[5];
+#pragma unroll
+        for (int k = 0; k < 5; ++k) z[k] = logit_load<LT>(logits + (size_t)i * 5 + k);
+        const int mask = (legal[i] | (1 << ((int)act[i] & 7)) | 0x10) & 0x1F;   // a stored action is never illegal; Stop is always legal
+#pragma unroll
+        for (int k = 0; k < 5; ++k) z[k] = ((mask >> k) & 1) ? z[k] : -INFINITY;
+        const float zmax = fmaxf(fmaxf(fmaxf(z[0], z[1]), fmaxf(z[2], z[3])), z[4]);
+        float se = 0.f;
+#pragma unroll
+        for (int k = 0; k < 5; ++k) se += expf(z[k] - zmax);
+        const float lse = zmax + logf(se);
+        float nrm[5], p[5], H = 0.f;
+#pragma unroll
+        for (int k = 0; k < 5; ++k) {
+            nrm[k] = z[k] - lse;
+            p[k] = expf(nrm[k]);
+            H -= fmaxf(nrm[k], -3.4028234663852886e38f) * p[k];
+        }
+        const int a = (int)act[i];
+        const float logp = a == 0 ? nrm[0] : (a == 1 ? nrm[1] : (a == 2 ? nrm[2] : (a == 3 ? nrm[3] : nrm[4])));
+        const float na = (adv[i] - a_mean) / a_den;
+        const float ratio = expf(logp - old_logp[i]);
+        const float rc = fminf(fmaxf(ratio, 1.0f - clip_eps), 1.0f + clip_eps);
+        const float t1 = na * ratio, t2 = na * rc;
+        pg_s += (double)fminf(t1, t2);
+        ent_s += (double)H;
+        clip_s += fabsf(ratio - 1.0f) > clip_eps ? 1.0 : 0.0;
+        // d min(t1, t2) / d ratio
+        const float w1 = t1 < t2 ? 1.0f : (t1 == t2 ? 0.5f : 0.0f), w2 = t2 < t1 ? 1.0f : (t1 == t2 ? 0.5f : 0.0f);
+        const float in_range = (ratio >= 1.0f - clip_eps && ratio <= 1.0f + clip_eps) ? 1.0f : 0.0f;
+        const float dmin_dr = na * (w1 + w2 * in_range);
+        const float dlogp = -invB * dmin_dr * ratio;                      // d loss / d logp_i
+        const float dH = -ent_coef * invB;                                // d loss / d H_i
+#pragma unroll
+        for (int k = 0; k < 5; ++k) {
+            const float g = dlogp * ((k == a ? 1.0f : 0.0f) - p[k]) + dH * (-p[k] * (nrm[k] + H));
+            logit_store<LT>(dlogits + (size_t)i * 5 + k, ((mask >> k) & 1) ? g : 0.0f);
+        }
+        const float v = values[paired ? (i >> 1) : i];
+        const float dv = v - ret[i];
+        vl_s += (double)(dv * dv);
+        if (!paired) dvalues[i] = vf_coef * invB * dv;
+    }
+    if (paired) {
+        for (int j = tid; j < BV; j += 1024) {
+            const float v = values[j];
+            dvalues[j] = vf_coef * invB * ((v - ret[2 * j]) + (v - ret[2 * j + 1]));
+        }
+    }
+    const double pg = -block_sum_1024(pg_s, red) / (double)B;
+    const double ent = block_sum_1024(ent_s, red) / (double)B;
+    const double cf = block_sum_1024(clip_s, red) / (double)B;
+    const double vl = 0.5 * block_sum_1024(vl_s, red) / (double)B;
+    if (tid == 0) {
+        stats[0] = (float)pg; stats[1] = (float)vl; stats[2] = (float)ent; stats[3] = (float)cf;
+        stats[4] = (float)pg + vf_coef * (float)vl - ent_coef * (float)ent;
+    }
+}
+
 extern "C" int pmx_ppo_loss(const void *logits_dev, int32_t logits_bf16, const float *values_dev, const int64_t *act_dev,
                             const float *old_logp_dev, const float *adv_dev, const float *ret_dev, int32_t B, int32_t BV,
                             const float *clip_eps_dev, const float *ent_coef_dev, float clip_eps, float ent_coef, float vf_coef,
@@ -1586,6 +1675,99 @@ extern "C" int pmx_ppo_loss(const void *logits_dev, int32_t logits_bf16, const f
         hipLaunchKernelGGL(pmx_ppo_loss_kernel<float>, dim3(1), dim3(1024), 0, st, (const float *)logits_dev, values_dev, act_dev, old_logp_dev,
                            adv_dev, ret_dev, (int)B, (int)BV, clip_eps_dev, ent_coef_dev, clip_eps, ent_coef, vf_coef, stats_dev,
                            (float *)dlogits_dev, dvalues_dev);
+    return pmx_launch_rc();
+}
+
+extern "C" int pmx_ppo_loss_masked(const void *logits_dev, int32_t logits_bf16, const float *values_dev, const int64_t *act_dev,
+                                   const int32_t *legal_dev, const float *old_logp_dev, const float *adv_dev, const float *ret_dev, int32_t B,
+                                   int32_t BV, const float *clip_eps_dev, const float *ent_coef_dev, float clip_eps, float ent_coef,
+                                   float vf_coef, float *stats_dev, void *dlogits_dev, float *dvalues_dev, void *stream)
+{
+    if (!legal_dev)                                                       // NULL: everything is legal, which is the unmasked objective
+        return pmx_ppo_loss(logits_dev, logits_bf16, values_dev, act_dev, old_logp_dev, adv_dev, ret_dev, B, BV, clip_eps_dev, ent_coef_dev,
+                            clip_eps, ent_coef, vf_coef, stats_dev, dlogits_dev, dvalues_dev, stream);
+    if (!logits_dev || !values_dev || !act_dev || !old_logp_dev || !adv_dev || !ret_dev || !stats_dev || !dlogits_dev || !dvalues_dev)
+        return PMX_ERR_INVALID;
+    if (B < 1 || (BV != B && BV * 2 != B)) return PMX_ERR_INVALID;
+    hipStream_t st = reinterpret_cast<hipStream_t>(stream);
+    if (logits_bf16)
+        hipLaunchKernelGGL(pmx_ppo_loss_masked_kernel<__hip_bfloat16>, dim3(1), dim3(1024), 0, st, (const __hip_bfloat16 *)logits_dev, values_dev,
+                           act_dev, legal_dev, old_logp_dev, adv_dev, ret_dev, (int)B, (int)BV, clip_eps_dev, ent_coef_dev, clip_eps, ent_coef,
+                           vf_coef, stats_dev, (__hip_bfloat16 *)dlogits_dev, dvalues_dev);
+    else
+        hipLaunchKernelGGL(pmx_ppo_loss_masked_kernel<float>, dim3(1), dim3(1024), 0, st, (const float *)logits_dev, values_dev, act_dev,
+                           legal_dev, old_logp_dev, adv_dev, ret_dev, (int)B, (int)BV, clip_eps_dev, ent_coef_dev, clip_eps, ent_coef, vf_coef,
+                           stats_dev, (float *)dlogits_dev, dvalues_dev);
+    return pmx_launch_rc();
+}
+
+// ---------------------------------------------------------------------------------------------------------------
+// Policy sampling under a legal-action mask (include/pmx.h, "legal-action masks"): one thread per row of 5 logits.  float32
+// throughout: z_k = logit or -inf where masked, p_k = expf(z_k - zmax), total = p_0 + ... + p_4 in that order, logp = (z_a - zmax)
+// - logf(total).  The draw is counter based like the bots' (pmx_step.hip random_legal): a lowbias32 hash of (seed, row, counter)
+// gives 24 bits, t = u * total, and the action is the first legal k whose running sum of p exceeds t (the last legal k if rounding
+// leaves none).  Greedy: the first legal k with the largest z, no draw.
+// ---------------------------------------------------------------------------------------------------------------
+template <typename LT>
+__global__ __launch_bounds__(256) void pmx_policy_sample_kernel(const LT *__restrict__ logits, const int32_t *__restrict__ legal, long B,
+                                                                uint32_t seed, uint32_t counter, int greedy, int64_t *__restrict__ action,
+                                                                float *__restrict__ logp)
+{
+    const long row = (long)blockIdx.x * 256 + threadIdx.x;
+    if (row >= B) return;
+    const int mask = ((legal ? legal[row] : 0x1F) | 0x10) & 0x1F;
+    float z[5];
+#pragma unroll
+    for (int k = 0; k < 5; ++k) {
+        const float v = logit_load<LT>(logits + (size_t)row * 5 + k);
+        z[k] = ((mask >> k) & 1) ? v : -INFINITY;
+    }
+    const float zmax = fmaxf(fmaxf(fmaxf(z[0], z[1]), fmaxf(z[2], z[3])), z[4]);
+    float p[5], total = 0.f;
+#pragma unroll
+    for (int k = 0; k < 5; ++k) { p[k] = expf(z[k] - zmax); total += p[k]; }
+    int a = 4;
+    if (greedy) {
+        float best = z[4];
+#pragma unroll
+        for (int k = 3; k >= 0; --k)
+            if (((mask >> k) & 1) && z[k] >= best) { best = z[k]; a = k; }
+    } else {
+        uint32_t x = seed ^ ((uint32_t)row * 0x9E3779B1u) ^ (counter * 0x85EBCA77u) ^ 0x6A09E667u;
+        x ^= x >> 16; x *= 0x7FEB352Du; x ^= x >> 15; x *= 0x846CA68Bu; x ^= x >> 16;
+        const float t = (float)(x >> 8) * 0x1p-24f * total;
+        float run = 0.f;
+        bool found = false;
+#pragma unroll
+        for (int k = 0; k < 5; ++k) {
+            run += p[k];
+            if ((mask >> k) & 1) {
+                if (!found) a = k;                                        // ends as the last legal k if no running sum exceeds t
+                if (run > t) found = true;
+            }
+        }
+    }
+    action[row] = a;
+    if (logp) {
+        const float za = a == 0 ? z[0] : (a == 1 ? z[1] : (a == 2 ? z[2] : (a == 3 ? z[3] : z[4])));
+        logp[row] = (za - zmax) - logf(total);
+    }
+}
+
+extern "C" int pmx_policy_sample(const void *logits_dev, int32_t logits_bf16, const int32_t *legal_dev, int64_t B, uint32_t seed,
+                                 uint32_t counter, int32_t greedy, int64_t *action_dev, float *logp_dev, void *stream)
+{
+    if (!logits_dev || !action_dev || B < 0) return PMX_ERR_INVALID;
+    if (B == 0) return PMX_OK;
+    const int64_t blocks = (B + 255) / 256;
+    if (blocks > 0x7FFFFFFFLL) return PMX_ERR_INVALID;
+    hipStream_t st = reinterpret_cast<hipStream_t>(stream);
+    if (logits_bf16)
+        hipLaunchKernelGGL(pmx_policy_sample_kernel<__hip_bfloat16>, dim3((unsigned)blocks), dim3(256), 0, st,
+                           (const __hip_bfloat16 *)logits_dev, legal_dev, (long)B, seed, counter, (int)greedy, action_dev, logp_dev);
+    else
+        hipLaunchKernelGGL(pmx_policy_sample_kernel<float>, dim3((unsigned)blocks), dim3(256), 0, st, (const float *)logits_dev, legal_dev,
+                           (long)B, seed, counter, (int)greedy, action_dev, logp_dev);
     return pmx_launch_rc();
 }
 

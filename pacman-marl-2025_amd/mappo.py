@@ -313,10 +313,13 @@ class MAPPOAgent(nn.Module):
         x = self.critic_transformer(x).mean(dim=0)
         return self.critic_head(x).squeeze(-1)
 
-    def evaluate(self, obs, merged_obs, action):
-        """-> value, log_prob, entropy  (:196-205)"""
+    def evaluate(self, obs, merged_obs, action, *, legal=None):
+        """-> value, log_prob, entropy  (:196-205).  legal: int32 mask words (canonicalize_legal); actions outside a row's effective
+        mask enter as -inf."""
         # same arithmetic as torch.distributions.Categorical(logits=...): normalise with logsumexp, probs by softmax
         logits = self.logits(obs).float()
+        if legal is not None:
+            logits = logits.masked_fill(~legal_bits(legal, action), float("-inf"))
         norm = logits - logits.logsumexp(dim=-1, keepdim=True)
         probs = F.softmax(norm, dim=-1)
         logp = norm.gather(1, action.view(-1, 1)).squeeze(1)
@@ -326,14 +329,19 @@ class MAPPOAgent(nn.Module):
     forward = evaluate      # torch.func.functional_call(model, params, (obs, merged, act)) == evaluate with those params
 
     @torch.no_grad()
-    def act(self, obs, generator=None):
-        """Sample actions for a batch: -> action [B] int64, log_prob [B] (Categorical(logits).sample, :173-177)."""
+    def act(self, obs, generator=None, *, legal=None, seed=0, counter=0):
+        """Sample actions for a batch: -> action [B] int64, log_prob [B] (Categorical(logits).sample, :173-177).  With `legal` (int32
+        mask words) the draw is sample_actions' counter-based one over the legal actions, keyed by (seed, counter)."""
+        if legal is not None:
+            return sample_actions(self.logits(obs), legal, seed=seed, counter=counter)
         logp_all = F.log_softmax(self.logits(obs).float(), dim=-1)
         a = torch.multinomial(logp_all.exp(), 1, generator=generator).squeeze(1)
         return a, logp_all.gather(1, a.view(-1, 1)).squeeze(1)
 
     @torch.no_grad()
-    def get_deterministic_action(self, obs):                             # :207-211
+    def get_deterministic_action(self, obs, *, legal=None):              # :207-211
+        if legal is not None:
+            return sample_actions(self.logits(obs), legal, greedy=True)[0]
         return self.logits(obs).argmax(dim=-1)
 
 
@@ -346,6 +354,124 @@ def canonicalize_action(action, is_red_agent):
     if isinstance(action, torch.Tensor):
         return torch.tensor(_RED_ACTION_MAP, device=action.device, dtype=action.dtype)[action.long()]
     return _RED_ACTION_MAP[int(action)]
+
+
+# bits 1 (East) and 3 (West) of a legal-action mask swapped: the mask counterpart of _RED_ACTION_MAP, as a 32-entry look-up
+_RED_LEGAL_LUT = tuple((b & 0x15) | ((b & 2) << 2) | ((b & 8) >> 2) for b in range(32))
+_RED_LEGAL_TENSORS = {}
+
+
+def canonicalize_legal(bits, is_red_agent):
+    """Env mask bits (PmxVecEnv.legal: bit a = action a legal, in the env's frame) as the int32 words the policy reads, in the
+    learner's canonical frame: for a red learner East and West swap, as in canonicalize_action."""
+    if isinstance(bits, torch.Tensor):
+        w = bits.to(torch.int32) & 0x1F
+        if not is_red_agent:
+            return w
+        key = _dev_key(bits.device)
+        if key not in _RED_LEGAL_TENSORS:
+            _RED_LEGAL_TENSORS[key] = torch.tensor(_RED_LEGAL_LUT, dtype=torch.int32, device=bits.device)
+        return _RED_LEGAL_TENSORS[key][w.long()]
+    b = int(bits) & 0x1F
+    return _RED_LEGAL_LUT[b] if is_red_agent else b
+
+
+def legal_bits(legal, action=None):
+    """[B, 5] bool of a row's effective mask: the word's low five bits, Stop always, and -- as the objective counts it -- the
+    stored action."""
+    w = legal.long().view(-1) | 0x10
+    if action is not None:
+        w = w | (1 << action.long().view(-1))
+    return ((w[:, None] >> torch.arange(5, device=w.device)) & 1).bool()
+
+
+def _lowbias32(x):
+    """lowbias32 on an int64 tensor holding uint32 values (products wrap in int64; the low 32 bits are exact)."""
+    M = 0xFFFFFFFF
+    x = x ^ (x >> 16)
+    x = (x * 0x7FEB352D) & M
+    x = x ^ (x >> 15)
+    x = (x * 0x846CA68B) & M
+    return x ^ (x >> 16)
+
+
+@torch.no_grad()
+def sample_actions(logits, legal=None, seed=0, counter=0, greedy=False):
+    """One action per row of logits [B, 5] under legal-action masks (int32 words, None = everything legal; include/pmx.h,
+    pmx_policy_sample): -> (action int64 [B], log_prob float32 [B]).  The draw is a hash of (seed, row, counter), so one
+    (seed, counter) on the same inputs gives the same actions.  On the GPU this is the kernel; on the CPU the same specification
+    in torch, float32, with the same hash."""
+    assert logits.dim() == 2 and logits.shape[1] == 5
+    B = logits.shape[0]
+    seed, counter = int(seed) & 0xFFFFFFFF, int(counter) & 0xFFFFFFFF
+    if legal is not None:
+        legal = legal.reshape(-1)
+        assert legal.dtype == torch.int32 and legal.shape[0] == B and legal.device == logits.device
+    if logits.is_cuda:
+        if logits.dtype not in (torch.float32, torch.bfloat16):
+            logits = logits.float()
+        logits = logits.contiguous()
+        action = torch.empty(B, dtype=torch.int64, device=logits.device)
+        logp = torch.empty(B, dtype=torch.float32, device=logits.device)
+        with torch.cuda.device(logits.device):
+            _lib.call("pmx_policy_sample", logits.data_ptr(), 1 if logits.dtype == torch.bfloat16 else 0,
+                      legal.contiguous().data_ptr() if legal is not None else None, B, seed, counter, 1 if greedy else 0,
+                      action.data_ptr(), logp.data_ptr(), _lib.stream(logits.device))
+        return action, logp
+    z = logits.float()
+    ks = torch.arange(5)
+    bit = legal_bits(legal) if legal is not None else torch.ones(B, 5, dtype=torch.bool)
+    z = z.masked_fill(~bit, float("-inf"))
+    zmax = z.max(dim=1).values
+    p = (z - zmax[:, None]).exp()
+    run = [p[:, 0]]
+    for k in range(1, 5):
+        run.append(run[-1] + p[:, k])                     # p_0 + ... + p_k, added in that order
+    total = run[4]
+    if greedy:
+        a = torch.where(bit & (z == zmax[:, None]), ks, 5).min(dim=1).values
+    else:
+        M = 0xFFFFFFFF
+        rows = torch.arange(B, dtype=torch.int64)
+        h = _lowbias32(seed ^ ((rows * 0x9E3779B1) & M) ^ ((counter * 0x85EBCA77) & M) ^ 0x6A09E667)
+        t = (h >> 8).to(torch.float32) * 2.0 ** -24 * total
+        first = torch.where(bit & (torch.stack(run, dim=1) > t[:, None]), ks, 5).min(dim=1).values
+        last = torch.where(bit, ks, -1).max(dim=1).values
+        a = torch.where(first < 5, first, last)
+    logp = (z.gather(1, a.view(-1, 1)).squeeze(1) - zmax) - total.log()
+    return a, logp
+
+
+def _loss_scalar(v):
+    """A clip / entropy coefficient as the (device pointer, host value) pair the objective kernels take."""
+    if isinstance(v, torch.Tensor):
+        assert v.is_cuda and v.dtype == torch.float32 and v.numel() == 1
+        return v.data_ptr(), 0.0
+    return None, float(v)
+
+
+class _PPOLossMaskedFn(torch.autograd.Function):
+    """pmx_ppo_loss_masked: _PPOLossFn with one int32 legal-action word per row behind the actions."""
+
+    @staticmethod
+    def forward(ctx, logits, values, act, legal, old_logp, adv, ret, clip_eps, ent_coef, vf_coef):
+        logits, values = logits.contiguous(), values.contiguous()
+        B, BV = logits.shape[0], values.shape[0]
+        assert legal.is_cuda and legal.dtype == torch.int32 and legal.numel() == B
+        stats = torch.empty(5, dtype=torch.float32, device=logits.device)
+        dlogits, dvalues = torch.empty_like(logits), torch.empty_like(values)
+        cp, ch = _loss_scalar(clip_eps)
+        ep, eh = _loss_scalar(ent_coef)
+        _lib.call("pmx_ppo_loss_masked", logits.data_ptr(), 1 if logits.dtype == torch.bfloat16 else 0, values.data_ptr(),
+                  act.contiguous().data_ptr(), legal.contiguous().data_ptr(), old_logp.contiguous().data_ptr(), adv.contiguous().data_ptr(),
+                  ret.contiguous().data_ptr(), B, BV, cp, ep, ch, eh, float(vf_coef), stats.data_ptr(), dlogits.data_ptr(),
+                  dvalues.data_ptr(), _lib.stream(logits.device))
+        ctx.save_for_backward(dlogits, dvalues)
+        return stats
+
+    @staticmethod
+    def backward(ctx, gstats):
+        return _PPOLossFn.backward(ctx, gstats) + (None,)
 
 
 class _PPOLossFn(torch.autograd.Function):
@@ -422,8 +548,9 @@ def _fused_loss_ok(model, obs, act, old_logp, adv, ret):
             and all(t.dtype == torch.float32 for t in (old_logp, adv, ret)) and act.shape[0] >= 2)
 
 
-def ppo_loss(model, obs, merged, act, old_logp, adv, ret, clip_eps, ent_coef, vf_coef=VF_COEF):
-    """The minibatch objective of pacman_mappo_resnet.py:571-585.  Returns (loss, dict of detached scalars)."""
+def ppo_loss(model, obs, merged, act, old_logp, adv, ret, clip_eps, ent_coef, vf_coef=VF_COEF, legal=None):
+    """The minibatch objective of pacman_mappo_resnet.py:571-585.  Returns (loss, dict of detached scalars).  legal: one int32
+    legal-action word per sample (the mask its action was drawn under); None is the reference's objective over all five logits."""
     if _fused_loss_ok(model, obs, act, old_logp, adv, ret):
         # The actor and the critic share nothing until the loss: the critic's forward runs on a side stream, so autograd
         # runs its backward there too (a node's backward uses its forward's stream) and the two halves of the step overlap.
@@ -439,12 +566,15 @@ def ppo_loss(model, obs, merged, act, old_logp, adv, ret, clip_eps, ent_coef, vf
         vals.record_stream(cur)
         if logits.dtype not in (torch.float32, torch.bfloat16):
             logits = logits.float()
-        stats = _PPOLossFn.apply(logits, vals, act, old_logp, adv, ret, clip_eps, ent_coef, vf_coef)
+        if legal is None:
+            stats = _PPOLossFn.apply(logits, vals, act, old_logp, adv, ret, clip_eps, ent_coef, vf_coef)
+        else:
+            stats = _PPOLossMaskedFn.apply(logits, vals, act, legal, old_logp, adv, ret, clip_eps, ent_coef, vf_coef)
         d = stats.detach()
         loss = stats[4]
         loss._pmx_stats = stats                           # (loss_root: what the learner differentiates instead of the select)
         return loss, {"pg": d[0], "vl": d[1], "entropy": d[2], "clip_frac": d[3], "loss": d[4]}
-    vals, logp, ent = model.evaluate(obs, merged, act)
+    vals, logp, ent = model.evaluate(obs, merged, act) if legal is None else model.evaluate(obs, merged, act, legal=legal)
     if vals.shape[0] != ret.shape[0]:
         # paired minibatch: rows 2k and 2k+1 are the two learners of one env-tick and share ONE merged critic input
         # (merge_obs_for_critic is per env-tick, pacman_mappo_resnet.py:556-557 expands it per agent); the critic ran on
@@ -652,13 +782,13 @@ class PPOLearner:
             pd[n] = v
         return stateless._reparametrize_module(self.model, pd)
 
-    def _loss(self, obs, merged, act, old_logp, adv, ret, clip_eps, ent_coef):
+    def _loss(self, obs, merged, act, old_logp, adv, ret, clip_eps, ent_coef, legal=None):
         """ppo_loss in the learner's precision: under autocast with the bfloat16 shadow weights in place, or in plain float32."""
         if self.autocast_dtype is None:
             self._shadow_views = None
-            return ppo_loss(self.model, obs, merged, act, old_logp, adv, ret, clip_eps, ent_coef)
+            return ppo_loss(self.model, obs, merged, act, old_logp, adv, ret, clip_eps, ent_coef, legal=legal)
         with self._shadow_context(obs.shape[0]), torch.autocast(device_type=self.bucket.data.device.type, dtype=self.autocast_dtype):
-            return ppo_loss(self.model, obs, merged, act, old_logp, adv, ret, clip_eps, ent_coef)
+            return ppo_loss(self.model, obs, merged, act, old_logp, adv, ret, clip_eps, ent_coef, legal=legal)
 
     def set_lr(self, lr):
         self.lr = lr
@@ -716,8 +846,8 @@ class PPOLearner:
         return (self.fused_optimizer and self.bucket.data.is_cuda and self.bucket.data.dtype == torch.float32
                 and self.bucket.grad.is_contiguous() and self.bucket.data.is_contiguous())
 
-    def update_minibatch(self, obs, merged, act, old_logp, adv, ret, clip_eps=CLIP_EPS, ent_coef=ENT_COEF_START):
-        loss, stats = self._loss(obs, merged, act, old_logp, adv, ret, clip_eps, ent_coef)
+    def update_minibatch(self, obs, merged, act, old_logp, adv, ret, clip_eps=CLIP_EPS, ent_coef=ENT_COEF_START, legal=None):
+        loss, stats = self._loss(obs, merged, act, old_logp, adv, ret, clip_eps, ent_coef, legal)
         self._backward_into_bucket(loss)                  # (data parallel: includes the gradient all-reduce)
         if self._use_fused_tail():
             self.step_count += 1
@@ -748,10 +878,11 @@ class PPOLearner:
         pkg = sys.modules.get(__name__.rsplit(".", 1)[0])
         return os.environ.get("DEBUG_CLR_GRAPH_PACKET_CAPTURE") == "0" and bool(getattr(pkg, "GRAPH_REPLAY_OK", False))
 
-    def capture(self, batch, obs_shape, in_dtype, clip_eps=CLIP_EPS, ent_coef=ENT_COEF_START, merged_batch=None):
+    def capture(self, batch, obs_shape, in_dtype, clip_eps=CLIP_EPS, ent_coef=ENT_COEF_START, merged_batch=None, masked=False):
         """Record zero_grad -> forward -> backward -> (all-reduce) -> clip -> Adam -> EMA for a fixed minibatch shape into
         a HIP graph.  Scalars that change between updates (lr, clip, entropy coefficient, Adam bias corrections) live in
-        device tensors that the graph reads, so one capture serves the whole schedule."""
+        device tensors that the graph reads, so one capture serves the whole schedule.  masked: the graph has a seventh static
+        input, `legal` (int32 [batch] legal-action words), and its objective is the masked one."""
         if not self.graph_replay_safe():
             raise RuntimeError("hipGraph replay of the optimizer step needs DEBUG_CLR_GRAPH_PACKET_CAPTURE=0 in the environment "
                                "before HIP initialises (ROCm 7 graph packet-capture bug, DESIGN.md section 5)")
@@ -765,6 +896,8 @@ class PPOLearner:
                               logp=torch.zeros(batch, dtype=torch.float32, device=dev),
                               adv=torch.randn(batch, dtype=torch.float32, device=dev),
                               ret=torch.zeros(batch, dtype=torch.float32, device=dev))
+        if masked:
+            i["legal"] = torch.full((batch,), 0x1F, dtype=torch.int32, device=dev)
         # lr/bc1, 1/sqrt(bc2), clip_eps, ent_coef as device scalars
         self._g_sc = torch.zeros(4, dtype=torch.float32, device=dev)
         self._g_stats = None
@@ -781,7 +914,7 @@ class PPOLearner:
         n = len(self.bucket.params)
 
         def seg_first():
-            loss, stats = self._loss(i["obs"], i["merged"], i["act"], i["logp"], i["adv"], i["ret"], self._g_sc[2], self._g_sc[3])
+            loss, stats = self._loss(i["obs"], i["merged"], i["act"], i["logp"], i["adv"], i["ret"], self._g_sc[2], self._g_sc[3], i.get("legal"))
             self._backward_group(loss, 0, n, retain=False)
             return loss, stats
 
@@ -871,11 +1004,15 @@ class PPOLearner:
         """{report: its sum over the replayed steps since reset_report_sums()} -- 0-dim views of one device tensor."""
         return {k: self._g_acc[j] for j, k in enumerate(self._g_acc_keys)}
 
-    def update_minibatch_graph(self, obs, merged, act, old_logp, adv, ret, clip_eps=CLIP_EPS, ent_coef=ENT_COEF_START):
+    def update_minibatch_graph(self, obs, merged, act, old_logp, adv, ret, clip_eps=CLIP_EPS, ent_coef=ENT_COEF_START, legal=None):
         """Same step as update_minibatch, replayed from the captured graph (inputs are copied into its static buffers)."""
         i = self._g_in
+        if (legal is not None) != ("legal" in i):
+            raise ValueError("legal-action masks go to a graph captured with masked=True, and only to such a graph")
         i["obs"].copy_(obs); i["merged"].copy_(merged); i["act"].copy_(act)
         i["logp"].copy_(old_logp); i["adv"].copy_(adv); i["ret"].copy_(ret)
+        if legal is not None:
+            i["legal"].copy_(legal)
         self.step_count += 1
         self._set_graph_scalars(clip_eps, ent_coef, self.step_count)
         self._replay()
@@ -883,10 +1020,10 @@ class PPOLearner:
 
     def update_minibatch_graph_gather(self, sources, index, rows_per_index, clip_eps=CLIP_EPS, ent_coef=ENT_COEF_START):
         """The replayed step with its minibatch assembled by ONE gather launch (pmx_gather_rows) straight into the graph's
-        static inputs: sources = the flat rollout tensors {obs, merged, act, logp, adv, ret} (rows = samples; merged rows =
-        env-ticks), index = int64 device indices, rows_per_index = {name: m} (2 for the per-learner tensors of a paired
+        static inputs: sources = the flat rollout tensors {obs, merged, act, logp, adv, ret} and, for a graph captured with masks,
+        legal (rows = samples; merged rows = env-ticks), index = int64 device indices, rows_per_index = {name: m} (2 for the per-learner tensors of a paired
         minibatch whose index names env-tick pairs).  Returns the graph's stats tensors (valid until the next replay)."""
-        names = ("obs", "merged", "act", "logp", "adv", "ret")
+        names = ("obs", "merged", "act", "logp", "adv", "ret") + (("legal",) if "legal" in self._g_in else ())
         n = len(names)
         VP, I32, I64 = C.c_void_p * n, C.c_int32 * n, C.c_int64 * n
         src, dst, idx, rb, m, nr = VP(), VP(), VP(), I32(), I32(), I64()

@@ -78,7 +78,7 @@ class VecMAPPOTrainer:
     def __init__(self, layout, n_envs, horizon=32, minibatch=512, epochs=UPDATE_EPOCHS, obs_dtype=None,
                  device="cuda:0", seed=0, rank=0, world_size=1, process_group=None, total_updates=2000, length=300,
                  use_autocast=True, opponent="random", use_graph=False, algorithm="mappo", paired_minibatches=True, curriculum_scale=1.0,
-                 env=None, redraw_layouts=False, force_collectives=False, hard_bots=("baseline",)):
+                 env=None, redraw_layouts=False, force_collectives=False, hard_bots=("baseline",), mask_illegal=False):
         self.device = torch.device(device)
         self.rank, self.world_size = rank, world_size
         # hard_bots: the in-kernel teams the curriculum draws its "hard" opponent from (the reference's hard teams are
@@ -147,6 +147,14 @@ class VecMAPPOTrainer:
         self.val_buf = torch.zeros((T, N, 2), dtype=torch.float32, device=dev)
         self.adv_buf = torch.zeros((T, N, 2), dtype=torch.float32, device=dev)
         self.ret_buf = torch.zeros((T, N, 2), dtype=torch.float32, device=dev)
+        # mask_illegal: the policy samples over the legal actions only (the env's masks of the state it acts on, canonicalised, one
+        # int32 word per learner and tick; mappo.sample_actions keyed by this seed and a counter that advances by one per call) and
+        # the objective sees the same masks.  Off: the reference's path, no mask is read anywhere
+        self.mask_illegal = bool(mask_illegal)
+        if self.mask_illegal:
+            self.legal_buf = torch.zeros((T, N, 2), dtype=torch.int32, device=dev)
+            self.sample_seed = (seed + 0x9E3779B9 * rank) & 0xFFFFFFFF         # the trainer's seed; other ranks draw other streams
+            self.sample_counter = 0
         starts = self.env.layout.starts.astype(np.int64)
         self.start_words = torch.tensor([int(starts[i, 0]) | (int(starts[i, 1]) << 8) for i in range(4)],
                                         dtype=torch.int32, device=dev)
@@ -188,10 +196,15 @@ class VecMAPPOTrainer:
                         and lin.in_features == 32 * H * W and lin.out_features == 512):
                     m.head_pack = mappo.pack_actor_head(lin.weight, H, W)
 
-    def _forward_policy(self, model, obs2, merged, want_value):
+    def _forward_policy(self, model, obs2, merged, want_value, legal=None):
         ctx = torch.autocast(device_type=self.device.type, dtype=self.autocast_dtype) if self.autocast_dtype else _NullCtx()
         with torch.no_grad(), ctx:
-            a, lp = model.act(self._net_in(obs2.reshape((-1,) + self.obs_shape)), generator=self.gen)
+            if legal is None:
+                a, lp = model.act(self._net_in(obs2.reshape((-1,) + self.obs_shape)), generator=self.gen)
+            else:
+                a, lp = model.act(self._net_in(obs2.reshape((-1,) + self.obs_shape)), legal=legal.reshape(-1), seed=self.sample_seed,
+                                  counter=self.sample_counter)
+                self.sample_counter += 1
             v = model.value(self._net_in(merged)).float() if want_value else None
         return a.view(-1, 2), lp.view(-1, 2), v
 
@@ -249,20 +262,29 @@ class VecMAPPOTrainer:
         if mode in BOT_TEAMS:
             acts[:, opp_ids[0]], acts[:, opp_ids[1]] = BOT_TEAMS[mode]
         mappo_alg = self.algorithm == "mappo"
+        masks = self.mask_illegal
+        own, other = (slice(0, 4, 2), slice(1, 4, 2)) if red else (slice(1, 4, 2), slice(0, 4, 2))   # learner_ids / opp_ids of env.legal
+        lg = None
         for t in range(T):
             env.emit_team_obs(red, self.obs_buf[t], self.merged_buf[t] if mappo_alg else None)
+            if masks:
+                # env.legal: the masks of the state this tick acts on (written by the reset, the last step or its auto-reset)
+                self.legal_buf[t].copy_(mappo.canonicalize_legal(env.legal[:, own], red))
+                lg = self.legal_buf[t]
             if mappo_alg:
-                a, lp, v = self._forward_policy(self.model, self.obs_buf[t], self.merged_buf[t], True)
+                a, lp, v = self._forward_policy(self.model, self.obs_buf[t], self.merged_buf[t], True, lg)
                 self.val_buf[t].copy_(v[:, None].expand(N, 2))
             else:
-                a, lp, v = self._forward_policy(self.model, self.obs_buf[t], self.obs_buf[t].view((-1,) + self.obs_shape), True)
+                a, lp, v = self._forward_policy(self.model, self.obs_buf[t], self.obs_buf[t].view((-1,) + self.obs_shape), True, lg)
                 self.val_buf[t].copy_(v.view(N, 2))
             self.act_buf[t].copy_(a)
             self.logp_buf[t].copy_(lp)
             acts[:, learner_ids] = mappo.canonicalize_action(a, red).to(torch.int8)
             if mode in ("self", "pool"):
                 env.emit_team_obs(not red, self._opp_obs, None)      # the opponent is red when the learner is blue
-                oa, _, _ = self._forward_policy(self.opponent_model, self._opp_obs, None, False)
+                # (under masks the opponent, a copy of a policy trained under masks, samples the same way under its own ids' masks)
+                oa, _, _ = self._forward_policy(self.opponent_model, self._opp_obs, None, False,
+                                                mappo.canonicalize_legal(env.legal[:, other], not red) if masks else None)
                 acts[:, opp_ids] = mappo.canonicalize_action(oa, not red).to(torch.int8)
             _, rew, done, info = env.step(acts, want_obs=False)
             cur_agent = info["agent"]
@@ -302,6 +324,7 @@ class VecMAPPOTrainer:
         merged = self.merged_buf.view((self.T * self.N,) + self.obs_shape)
         act, logp = self.act_buf.view(S), self.logp_buf.view(S)
         adv, ret = self.adv_buf.view(S), self.ret_buf.view(S)
+        legal = self.legal_buf.view(S) if self.mask_illegal else None
         agg = None
         steps = 0
         snap = None
@@ -322,15 +345,18 @@ class VecMAPPOTrainer:
                     mb = perm[s0:s0 + self.minibatch]
                 if self.use_graph and not self._graph_ready:
                     self.learner.capture(self.minibatch, self.obs_shape, self._net_in(obs[:1]).dtype,
-                                         clip_eps, ent_coef, merged_batch=self.minibatch // 2 if self.paired else None)
+                                         clip_eps, ent_coef, merged_batch=self.minibatch // 2 if self.paired else None,
+                                         **({"masked": True} if legal is not None else {}))
                     self._graph_ready = True
                 if gather:
                     # replayed step, paired minibatch: one gather launch into the graph's inputs, reports summed inside the graph
                     if steps == 0:
                         self.learner.reset_report_sums()
-                    self.learner.update_minibatch_graph_gather(
-                        {"obs": obs, "merged": merged, "act": act, "logp": logp, "adv": adv, "ret": ret}, pr,
-                        {"obs": 2, "merged": 1, "act": 2, "logp": 2, "adv": 2, "ret": 2}, clip_eps, ent_coef)
+                    src = {"obs": obs, "merged": merged, "act": act, "logp": logp, "adv": adv, "ret": ret}
+                    rows = {"obs": 2, "merged": 1, "act": 2, "logp": 2, "adv": 2, "ret": 2}
+                    if legal is not None:
+                        src["legal"], rows["legal"] = legal, 2
+                    self.learner.update_minibatch_graph_gather(src, pr, rows, clip_eps, ent_coef)
                     steps += 1
                     if max_steps is not None and steps >= max_steps:
                         break
@@ -338,7 +364,8 @@ class VecMAPPOTrainer:
                 mb = torch.stack((2 * pr, 2 * pr + 1), dim=1).reshape(-1) if self.paired else mb   # rows 2k, 2k+1 = the two learners of pair k
                 step = self.learner.update_minibatch_graph if self.use_graph else self.learner.update_minibatch
                 critic_in = merged[pr] if self.paired else (merged[mb // 2] if self.algorithm == "mappo" else obs[mb])
-                st = step(self._net_in(obs[mb]), self._net_in(critic_in), act[mb], logp[mb], adv[mb], ret[mb], clip_eps, ent_coef)
+                st = step(self._net_in(obs[mb]), self._net_in(critic_in), act[mb], logp[mb], adv[mb], ret[mb], clip_eps, ent_coef,
+                          **({"legal": legal[mb]} if legal is not None else {}))
                 steps += 1
                 agg = {k: v.clone() for k, v in st.items()} if agg is None else {k: agg[k] + st[k] for k in agg}
                 if max_steps is not None and steps >= max_steps:
@@ -372,7 +399,10 @@ class VecMAPPOTrainer:
         counters and both random streams -- tensors, numbers and strings only, so that it loads with weights_only=True.
         The games themselves are not saved: a resumed run starts its envs from fresh episodes."""
         kind, keys, pos, has_gauss, cached = self.np_rng.get_state()
-        torch.save({"data": self.learner.bucket.data, "ema": self.learner.ema, "exp_avg": self.learner.exp_avg,
+        # (the mask flag and the sampler's counter are written only when the flag is on: a file of the default path is the one
+        # earlier versions wrote)
+        extra = {"mask_illegal": 1, "sample_counter": int(self.sample_counter)} if self.mask_illegal else {}
+        torch.save({**extra, "data": self.learner.bucket.data, "ema": self.learner.ema, "exp_avg": self.learner.exp_avg,
                     "exp_avg_sq": self.learner.exp_avg_sq, "step": int(self.learner.step_count), "update": int(self.update_idx),
                     "total_updates": int(self.total_updates), "pool": list(self.opponent_pool), "gen": self.gen.get_state(),
                     "hard_bots": list(self.hard_bots),
@@ -385,6 +415,9 @@ class VecMAPPOTrainer:
         if not isinstance(ck, dict) or any(k not in ck for k in need) or not isinstance(ck["np_rng"], dict) or "keys" not in ck["np_rng"]:
             raise ValueError(f"{path}: not a full-resume checkpoint of this version (save_full writes the keys {', '.join(need)}; "
                              "checkpoints written before `total_updates` and the tensor-valued `np_rng` were added are not supported)")
+        if bool(ck.get("mask_illegal", 0)) != self.mask_illegal:          # (no key: written with the flag off)
+            raise ValueError(f"checkpoint was written with mask_illegal={bool(ck.get('mask_illegal', 0))}, this trainer has "
+                             f"mask_illegal={self.mask_illegal}: a policy trained under masks is sampled under masks")
         if int(ck["total_updates"]) != int(self.total_updates):
             raise ValueError(f"checkpoint was written for a schedule of {ck['total_updates']} updates, this trainer has {self.total_updates}")
         self.learner.restore(ck)                                         # (weights, Adam moments, EMA and step count: the same keys)
@@ -392,6 +425,8 @@ class VecMAPPOTrainer:
         self.opponent_pool = deque(ck["pool"], maxlen=OPPONENT_POOL_SIZE)
         self.gen.set_state(ck["gen"].cpu())
         self.hard_bots = tuple(ck.get("hard_bots", ("baseline",)))       # files written before hard_bots existed: the default
+        if self.mask_illegal:
+            self.sample_counter = int(ck["sample_counter"])
         r = ck["np_rng"]
         self.np_rng.set_state((r["kind"], r["keys"].cpu().numpy().astype(np.uint32), int(r["pos"]), int(r["has_gauss"]),
                                float(r["cached_gaussian"])))
@@ -429,14 +464,15 @@ def evaluate_vs_bots(model, num_episodes=20, layout_file="bloxCapture", teams=("
 
 @torch.no_grad()
 def evaluate_vectorized(model, layout="bloxCapture", n_envs=1024, opponent="baseline", length=300, device="cuda:0", seed=0,
-                        autocast=True):
+                        autocast=True, mask_illegal=False):
     """evaluate_vs_bots (pacman_mappo_resnet.py:293-337) for n_envs episodes at once: the learner plays blue with argmax
     actions against the in-kernel randomTeam / baselineTeam / approxQTeam (opponent "random" / "baseline" / "approxq"), one episode per env (an env stops counting at its first done).
-    Returns (mean episode return of the learner team as the reference sums it, std, win rate = share with final score < 0)."""
+    Returns (mean episode return of the learner team as the reference sums it, std, win rate = share with final score < 0).
+    mask_illegal: the argmax runs over the legal actions only (a policy trained with the trainer's mask_illegal)."""
     dev = torch.device(device)
     env = PmxVecEnv(layout, n_envs, length=length, auto_reset=True, obs_dtype="bfloat16" if autocast else "float32", device=dev,
                     seed=seed, bots=opponent in BOT_TEAMS)
-    obs, _ = env.reset()
+    obs, legal = env.reset()
     was_training = model.training
     model.eval()
     alive = torch.ones(n_envs, dtype=torch.bool, device=dev)
@@ -447,11 +483,16 @@ def evaluate_vectorized(model, layout="bloxCapture", n_envs=1024, opponent="base
     for _ in range(length + 1):
         lo = obs[:, [1, 3]].reshape((-1,) + tuple(obs.shape[2:]))
         with ctx:
-            a = model.get_deterministic_action(lo.to(torch.bfloat16) if autocast else lo.float()).view(n_envs, 2)
+            if mask_illegal:
+                a = model.get_deterministic_action(lo.to(torch.bfloat16) if autocast else lo.float(),
+                                                   legal=mappo.canonicalize_legal(legal[:, 1::2], False).reshape(-1)).view(n_envs, 2)
+            else:
+                a = model.get_deterministic_action(lo.to(torch.bfloat16) if autocast else lo.float()).view(n_envs, 2)
         acts = torch.empty((n_envs, 4), dtype=torch.int8, device=dev)
         acts[:, 0], acts[:, 2] = opp[0], opp[1]
         acts[:, [1, 3]] = a.to(torch.int8)
         obs, rew, done, info = env.step(acts)
+        legal = info["legal_actions"]
         ret += torch.where(alive, rew[:, 1] + rew[:, 1], torch.zeros_like(ret))     # sum over both learners' rewards (:328)
         d = done.to(torch.bool) & alive
         final = torch.where(d, info["score"], final)

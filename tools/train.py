@@ -47,6 +47,8 @@ def parser():
     ap.add_argument("--seed", type=int, default=0)
     ap.add_argument("--unpaired", action="store_true", help="the reference's independent shuffle of agent samples (critic runs per sample)")
     ap.add_argument("--curriculum-scale", type=float, default=1.0, help="compress the curriculum's phase thresholds (updates 200 / 800)")
+    ap.add_argument("--mask-illegal", action="store_true", help="sample, train and evaluate over the legal actions only (the env's legal-action masks; "
+                                                                "off by default: the reference samples from all five logits)")
     ap.add_argument("--graph", action="store_true", help="replay the optimizer step from a hipGraph (launch-bound minibatches, e.g. 512)")
     return ap
 
@@ -88,7 +90,7 @@ def main():
     tr = trainer.VecMAPPOTrainer(layout, args.envs, horizon=args.horizon, minibatch=args.minibatch, epochs=args.epochs, redraw_layouts=args.redraw,
                                  obs_dtype=args.obs, device=f"cuda:{local}", seed=args.seed, rank=rank, world_size=world,
                                  total_updates=args.total_updates, opponent=args.opponent, algorithm=args.algorithm, use_graph=args.graph, paired_minibatches=not args.unpaired, curriculum_scale=args.curriculum_scale,
-                                 hard_bots=tuple(args.hard_bots.split(",")))
+                                 hard_bots=tuple(args.hard_bots.split(",")), mask_illegal=args.mask_illegal)
     for u in range(args.updates):
         torch.cuda.synchronize(); t0 = time.perf_counter()
         st = tr.train_update()
@@ -102,8 +104,8 @@ def main():
                                   clip_frac=f("clip_frac"), grad_norm=f("grad_norm"), steps=st["optimizer_steps"]))
             if args.eval_every and u and u % args.eval_every == 0:
                 emit(dict(update=u, algorithm=args.algorithm,
-                          eval_vs_baseline=trainer.evaluate_vectorized(tr.model, eval_layout, 1024, "baseline", device=f"cuda:{local}"),
-                          eval_vs_random=trainer.evaluate_vectorized(tr.model, eval_layout, 1024, "random", device=f"cuda:{local}")))
+                          eval_vs_baseline=trainer.evaluate_vectorized(tr.model, eval_layout, 1024, "baseline", device=f"cuda:{local}", mask_illegal=args.mask_illegal),
+                          eval_vs_random=trainer.evaluate_vectorized(tr.model, eval_layout, 1024, "random", device=f"cuda:{local}", mask_illegal=args.mask_illegal)))
     if rank == 0 and args.save:
         tr.save_ema(args.save)
     if world > 1:
