@@ -202,6 +202,15 @@ int pmx_observe(pmx_env *env, void *obs_dev, uint8_t *legal_dev, void *stream);
  * after pmx_reset / pmx_set_state (all agents see the current state). */
 int pmx_emit_team_obs(pmx_env *env, int team_red, void *team_obs_dev, void *merged_dev, void *stream);
 
+/* pmx_emit_team_obs with the learners' colour chosen PER ENV, for a rollout whose envs play different pairings at once (the
+ * reference draws one opponent and one side per rollout of its single env, pacman_mappo_resnet.py:396-438; the frames are
+ * those of :215-229 and :267-274).  team_red_dev [n_envs] uint8, non-zero = this env's learners are red.  Rows are written for
+ * the envs first .. first + count - 1 only, output row j for env first + j: team_obs_dev [count][2][8][H][W], merged_dev
+ * [count][8][H][W] or NULL.  Row e - first is byte for byte row e of pmx_emit_team_obs(env, team_red_dev[e] != 0, ...).
+ * count == 0 launches nothing; PMX_ERR_INVALID for a range outside the handle's envs. */
+int pmx_emit_team_obs_mixed(pmx_env *env, const uint8_t *team_red_dev, int32_t first, int32_t count, void *team_obs_dev,
+                            void *merged_dev, void *stream);
+
 /* The layout each env is currently on (host output [n_envs]; all zeros for a single-layout handle).  Synchronises the stream. */
 int pmx_get_layout_index(pmx_env *env, int32_t *index_out, void *stream);
 
@@ -220,8 +229,8 @@ int pmx_maze_distances_layout(pmx_env *env, int32_t layout, int8_t *cells_dev, u
 /* Measurement hooks (no reference counterpart): between begin and end, every tick attaches a start and a stop HIP event
  * to its rule-kernel and to its expansion-kernel dispatch on the caller's stream (hipExtLaunchKernelGGL); end
  * synchronises them and returns the summed kernel durations (milliseconds) and launch counts.  bench.py's roofline
- * figures come from here.  A pmx_emit_team_obs launch is recorded with the expansion launches (a training loop calls it in
- * place of the four-agent expansion).
+ * figures come from here.  A pmx_emit_team_obs or pmx_emit_team_obs_mixed launch is recorded with the expansion launches (a
+ * training loop calls it in place of the four-agent expansion).
  * While a profile is open pmx_step runs the FULL expansion: outside one it stores the wall plane (plane 0, a per-layout
  * constant) from extra blocks of the rule launch and starts the expansion kernel behind it (float32 planes up to 900 MB, no
  * redraw_layouts).  The expansion duration reported here, which bench.py divides all plane bytes by, is therefore that of the

@@ -103,6 +103,10 @@ struct PmxEmitParams {
     void *merged;                // [N][8][H][W] or NULL
     int32_t N, red;              // red: agents (0, 2), x-flipped with planes 2<->3 and 6<->7 swapped; else agents (1, 3) as they are
     int32_t lay_H, lay_W;
+    // pmx_emit_team_obs_mixed only (pmx_emit_team_kernel<DT, true>; zero and unread otherwise): the colour per env in place of
+    // `red`, and the env range of the launch -- team_obs / merged then hold `count` rows, row j for env first + j
+    const uint8_t *team_red;     // [N], non-zero = red
+    int32_t first, count;
 };
 
 // Host-side launch tuning, changed through pmx_set_tuning: -1 = the built-in choice.

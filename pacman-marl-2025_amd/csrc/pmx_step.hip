@@ -1555,7 +1555,10 @@ __device__ __forceinline__ uint32_t flip_row(uint32_t v, int W, bool flip) { ret
 // filled six to 60 %, and the set-up (snapshot loads, stream assembly, the block's look-up table) is paid once per env
 // instead of once per slot: 28.3 -> 14.5 us at 16 384 smallCapture envs, 12.3 -> 10.0 / 20.3 -> 17.0 us on the 20 x 20 boards
 // (4 096 / 8 192 envs).  U = store instructions per group of look-ups (1: 16.0 us, 2: 14.5, 4: 14.4, 5: 15.0 on smallCapture).
-template <int DT>
+// MIXED (pmx_emit_team_obs_mixed): the colour is the ENV's (p.team_red[env], read once per wave, so first / second / flip stay
+// wave-uniform) and the launch covers the envs p.first .. p.first + p.count - 1, output row j = env p.first + j.  The uniform
+// instantiation reads none of the three fields and is the kernel it was before they existed.
+template <int DT, bool MIXED>
 __global__ __launch_bounds__(PMX_BLOCK) void pmx_emit_team_kernel(PmxEmitParams p)
 {
     constexpr int VEC = ObsVec<DT>::VEC;
@@ -1580,17 +1583,20 @@ __global__ __launch_bounds__(PMX_BLOCK) void pmx_emit_team_kernel(PmxEmitParams 
     const int half = lane >> 5, hl = lane & 31;
     const int W = p.lay_W, H = p.lay_H, HW = H * W;
     long blk = (long)blockIdx.x;
-    if ((p.N & 127) == 0) {                                   // the 16 envs of one 64-byte line of snapshot words: one XCD
-        const long r = blk & 31;
+    if (((MIXED ? p.count : p.N) & 127) == 0) {               // the 16 envs of one 64-byte line of snapshot words: one XCD
+        const long r = blk & 31;                              // (a permutation of the launched blocks: whole groups of 32 only)
         blk = (blk & ~31L) + (r & 7) * 4 + (r >> 3);
     }
-    const long env = blk * 4 + wave;
-    if (env >= p.N) return;
-    const bool flip = p.red != 0;
-    const int first = p.red ? 0 : 1, second = first + 2;
+    const long row = blk * 4 + wave;                          // output row; the env itself unless MIXED
+    if (row >= (MIXED ? p.count : p.N)) return;
+    const long env = MIXED ? row + p.first : row;
+    const int red_v = MIXED ? __builtin_amdgcn_readfirstlane((int)p.team_red[env]) : p.red;
+    const bool flip = red_v != 0;
+    const int first = red_v ? 0 : 1, second = first + 2;
     const int agent = half ? second : first;
     const size_t N = (size_t)p.N;
-    const uint32_t *S = (half ? p.snap[second] : p.snap[first]) + env;
+    const uint32_t *S = (MIXED ? (half ? (flip ? p.snap[2] : p.snap[3]) : (flip ? p.snap[0] : p.snap[1]))
+                               : (half ? p.snap[second] : p.snap[first])) + env;
     uint32_t *T = tab[wave][half];
     const PmxLayoutDev *L = p.lay + (p.layout_idx ? p.layout_idx[env] : 0);
 
@@ -1646,8 +1652,8 @@ __global__ __launch_bounds__(PMX_BLOCK) void pmx_emit_team_kernel(PmxEmitParams 
 
     const int n_vec = 8 * HW / VEC;
     const int total = (p.merged ? 3 : 2) * n_vec;
-    uint4 *out_team = reinterpret_cast<uint4 *>(p.team_obs) + (size_t)env * 2 * n_vec;            // slots 0, 1 are contiguous
-    uint4 *out_merged = reinterpret_cast<uint4 *>(p.merged) + (size_t)env * n_vec - 2 * n_vec;   // indexed by kk >= 2 n_vec
+    uint4 *out_team = reinterpret_cast<uint4 *>(p.team_obs) + (size_t)row * 2 * n_vec;            // slots 0, 1 are contiguous
+    uint4 *out_merged = reinterpret_cast<uint4 *>(p.merged) + (size_t)row * n_vec - 2 * n_vec;   // indexed by kk >= 2 n_vec
     const uint32_t *T0 = tab[wave][0], *T1 = tab[wave][1];
     for (int base = 0; base < total; base += 64 * U) {
         uint32_t bits[U], e0s[U];
@@ -1698,15 +1704,27 @@ __global__ __launch_bounds__(PMX_BLOCK) void pmx_emit_team_kernel(PmxEmitParams 
 extern "C" hipError_t pmx_launch_emit_team(const PmxEmitParams *p, int dtype, hipStream_t st, hipEvent_t ev0, hipEvent_t ev1)
 {
     const unsigned blocks = (unsigned)(((long)p->N + 3) / 4);    // one wave per env
-#define PMX_EMIT(DT)                                                                                                          \
+#define PMX_EMIT(DT, MIXED)                                                                                                   \
     do {                                                                                                                      \
-        if (ev0) hipExtLaunchKernelGGL(pmx_emit_team_kernel<DT>, dim3(blocks), dim3(PMX_BLOCK), 0, st, ev0, ev1, 0, *p);       \
-        else hipLaunchKernelGGL(pmx_emit_team_kernel<DT>, dim3(blocks), dim3(PMX_BLOCK), 0, st, *p);                           \
+        if (ev0) hipExtLaunchKernelGGL((pmx_emit_team_kernel<DT, MIXED>), dim3(blocks), dim3(PMX_BLOCK), 0, st, ev0, ev1, 0, *p); \
+        else hipLaunchKernelGGL((pmx_emit_team_kernel<DT, MIXED>), dim3(blocks), dim3(PMX_BLOCK), 0, st, *p);                  \
     } while (0)
     switch (dtype) {
-    case 0: PMX_EMIT(0); break;
-    case 1: PMX_EMIT(1); break;
-    default: PMX_EMIT(2); break;
+    case 0: PMX_EMIT(0, false); break;
+    case 1: PMX_EMIT(1, false); break;
+    default: PMX_EMIT(2, false); break;
+    }
+    return hipGetLastError();
+}
+
+// pmx_emit_team_obs_mixed: p->team_red, p->first and p->count set, one wave per env of the range (p->count > 0)
+extern "C" hipError_t pmx_launch_emit_team_mixed(const PmxEmitParams *p, int dtype, hipStream_t st, hipEvent_t ev0, hipEvent_t ev1)
+{
+    const unsigned blocks = (unsigned)(((long)p->count + 3) / 4);
+    switch (dtype) {
+    case 0: PMX_EMIT(0, true); break;
+    case 1: PMX_EMIT(1, true); break;
+    default: PMX_EMIT(2, true); break;
     }
 #undef PMX_EMIT
     return hipGetLastError();

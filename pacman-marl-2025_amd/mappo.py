@@ -348,7 +348,44 @@ class MAPPOAgent(nn.Module):
 _RED_ACTION_MAP = (0, 3, 2, 1, 4)   # East <-> West for a red learner (pacman_mappo_resnet.py:232-238)
 
 
+def _per_env(red, like):
+    """A per-env colour vector [N] (bool / uint8) as a bool tensor that broadcasts over the leading dimension of `like`."""
+    return red.to(torch.bool).view((-1,) + (1,) * (like.dim() - 1))
+
+
+def canonicalize_action_per_env(action, red):
+    """canonicalize_action with the colour chosen per env: action [N, ...], red [N] bool / uint8; East and West swap only in
+    the rows where red is set.  (The map is its own inverse, so this also takes canonical actions back to the env's frame.)"""
+    return torch.where(_per_env(red, action) & ((action == 1) | (action == 3)), 4 - action, action)
+
+
+def canonicalize_legal_per_env(bits, red):
+    """canonicalize_legal with the colour chosen per env: bits [N, ...] env mask bits, red [N]; int32 words."""
+    w = bits.to(torch.int32) & 0x1F
+    return torch.where(_per_env(red, w), (w & 0x15) | ((w & 2) << 2) | ((w & 8) >> 2), w)
+
+
+def _team_column_index(red, opponents):
+    # the [N, 4] agent axis seen as [N, 2, 2]: agent = 2k + c with c = 0 red, c = 1 blue
+    c = red.to(torch.bool) if opponents else ~red.to(torch.bool)
+    return c.to(torch.int64).view(-1, 1, 1).expand(-1, 2, 1)
+
+
+def team_columns(x, red, opponents=False):
+    """The learners' two columns of x [N, 4] per env -- agents (0, 2) where red [N] is set, (1, 3) elsewhere -- as [N, 2];
+    opponents=True: the other team's."""
+    return x.reshape(-1, 2, 2).gather(2, _team_column_index(red, opponents)).squeeze(2)
+
+
+def set_team_columns(x, red, values, opponents=False):
+    """The inverse of team_columns: writes values [N, 2] into the learners' (opponents') two columns of x [N, 4], in place."""
+    x.view(-1, 2, 2).scatter_(2, _team_column_index(red, opponents), values.to(x.dtype).unsqueeze(2))
+    return x
+
+
 def canonicalize_action(action, is_red_agent):
+    if isinstance(is_red_agent, torch.Tensor):                # a colour per env
+        return canonicalize_action_per_env(action, is_red_agent)
     if not is_red_agent:
         return action
     if isinstance(action, torch.Tensor):
@@ -364,6 +401,8 @@ _RED_LEGAL_TENSORS = {}
 def canonicalize_legal(bits, is_red_agent):
     """Env mask bits (PmxVecEnv.legal: bit a = action a legal, in the env's frame) as the int32 words the policy reads, in the
     learner's canonical frame: for a red learner East and West swap, as in canonicalize_action."""
+    if isinstance(is_red_agent, torch.Tensor):                # a colour per env
+        return canonicalize_legal_per_env(bits, is_red_agent)
     if isinstance(bits, torch.Tensor):
         w = bits.to(torch.int32) & 0x1F
         if not is_red_agent:

@@ -12,6 +12,7 @@ heuristic teams of the reference's curriculum are wall-clock-bounded searches an
 """
 import copy
 from collections import deque
+from fractions import Fraction
 
 import numpy as np
 import torch
@@ -41,6 +42,38 @@ def shaping_from_agent_words(prev, cur):
 BOT_TEAMS = {"baseline": (_lib.ACTION_BASELINE_OFFENSE, _lib.ACTION_BASELINE_DEFENSE),      # createTeam: first index offensive,
              "approxq": (_lib.ACTION_APPROXQ_OFFENSE, _lib.ACTION_APPROXQ_DEFENSE)}         # second defensive
 _OBS_CODES = {torch.float32: _lib.OBS_F32, torch.bfloat16: _lib.OBS_BF16, torch.uint8: _lib.OBS_U8}
+
+
+def mix_plan(update_idx, curriculum_scale, n_envs, hard_bots, opponent_mode):
+    """The opponents of ONE rollout spread over its envs (mix_opponents): [(mode, red, first, count), ...], contiguous env ranges
+    from 0 in the order self, pool, each team of hard_bots, random.  The shares are the probabilities _pick_opponent draws
+    with -- all random up to update 200 * scale; 5/6 hard teams (split evenly) and 1/6 random up to 800 * scale; then 0.40 self,
+    0.20 pool and 0.40 x (5/6 hard, 1/6 random) -- or the single mode of a fixed opponent_mode.  Counts are rounded by largest
+    remainder (ties to the earlier group) and sum to n_envs; empty groups are left out.  Bot and random groups play the learner
+    blue, as the reference does; self and pool groups are split into a red first half (count // 2) and a blue rest, where the
+    reference flips a coin.  A pure host function of its arguments: no draw, so every rank computes the same plan."""
+    hard = [(b, Fraction(5, 6) / len(hard_bots)) for b in hard_bots] + [("random", Fraction(1, 6))]
+    if opponent_mode != "curriculum":
+        shares = [(opponent_mode, Fraction(1))]
+    elif update_idx <= 200 * curriculum_scale:
+        shares = [("random", Fraction(1))]
+    elif update_idx <= 800 * curriculum_scale:
+        shares = hard
+    else:
+        shares = [("self", Fraction(2, 5)), ("pool", Fraction(1, 5))] + [(m, Fraction(2, 5) * f) for m, f in hard]
+    exact = [f * n_envs for _, f in shares]
+    counts = [int(x) for x in exact]                            # floor (the shares are not negative)
+    by_remainder = sorted(range(len(shares)), key=lambda i: (-(exact[i] - counts[i]), i))
+    for i in by_remainder[:n_envs - sum(counts)]:
+        counts[i] += 1
+    plan, first = [], 0
+    for (mode, _), c in zip(shares, counts):
+        parts = [(True, c // 2), (False, c - c // 2)] if mode in ("self", "pool") else [(False, c)]
+        for red, k in parts:
+            if k:
+                plan.append((mode, red, first, k))
+                first += k
+    return plan
 
 
 def _plane_kernel_ok(*ts):
@@ -78,7 +111,8 @@ class VecMAPPOTrainer:
     def __init__(self, layout, n_envs, horizon=32, minibatch=512, epochs=UPDATE_EPOCHS, obs_dtype=None,
                  device="cuda:0", seed=0, rank=0, world_size=1, process_group=None, total_updates=2000, length=300,
                  use_autocast=True, opponent="random", use_graph=False, algorithm="mappo", paired_minibatches=True, curriculum_scale=1.0,
-                 env=None, redraw_layouts=False, force_collectives=False, hard_bots=("baseline",), mask_illegal=False):
+                 env=None, redraw_layouts=False, force_collectives=False, hard_bots=("baseline",), mask_illegal=False,
+                 mix_opponents=False):
         self.device = torch.device(device)
         self.rank, self.world_size = rank, world_size
         # hard_bots: the in-kernel teams the curriculum draws its "hard" opponent from (the reference's hard teams are
@@ -155,6 +189,10 @@ class VecMAPPOTrainer:
             self.legal_buf = torch.zeros((T, N, 2), dtype=torch.int32, device=dev)
             self.sample_seed = (seed + 0x9E3779B9 * rank) & 0xFFFFFFFF         # the trainer's seed; other ranks draw other streams
             self.sample_counter = 0
+        # mix_opponents: every rollout realises the opponent mixture ACROSS its envs (mix_plan: contiguous groups of envs per
+        # opponent, both colours where the reference flips a coin) instead of drawing one opponent and one colour for all of
+        # them; the observations come from pmx_emit_team_obs_mixed.  Off: one pairing per rollout, the reference's scheme
+        self.mix_opponents = bool(mix_opponents)
         starts = self.env.layout.starts.astype(np.int64)
         self.start_words = torch.tensor([int(starts[i, 0]) | (int(starts[i, 1]) << 8) for i in range(4)],
                                         dtype=torch.int32, device=dev)
@@ -242,6 +280,8 @@ class VecMAPPOTrainer:
         observations into obs_buf[t] and the merged critic input into merged_buf[t] (pmx_emit_team_obs -- no select / flip /
         copy / merge passes over the planes, and the four-agent observation tensor of pmx_step is not produced at all), the
         policy samples both learners' actions and one value, the env steps with the actions taken from a persistent tensor."""
+        if self.mix_opponents:
+            return self._rollout_mixed()
         env, N, T = self.env, self.N, self.T
         mode, red = self._pick_opponent()
         self._freeze_tower_packs(True)
@@ -308,6 +348,96 @@ class VecMAPPOTrainer:
                 self.last_value = self.model.value(self._net_in(self._boot_obs.view((-1,) + self.obs_shape))).float().view(N, 2)
         self._freeze_tower_packs(False)
         self.stats.update(opponent=mode, play_as_red=red, rollout_reward=ep_ret, episodes=n_done, wins=n_win)
+
+    def _rollout_mixed(self):
+        """rollout() with the pairing chosen per env (mix_opponents): the plan's groups play side by side in one rollout.  The
+        learners' colour is a [N] tensor, so the frame helpers take their per-env forms and the reward, shaping and win test
+        pick their columns by it; a stored sample is canonical and does not know its env's colour, so the buffers, the GAE and
+        update() are those of the default path.  Network opponents (self: the current model, pool: ONE snapshot per rollout)
+        fill the first envs and get their observations from a second emission over that range with the colours inverted."""
+        env, N, T = self.env, self.N, self.T
+        plan = mix_plan(self.update_idx, self.curriculum_scale, N, self.hard_bots, self.opponent_mode)
+        n_self = sum(c for m, _, _, c in plan if m == "self")
+        n_pool = sum(c for m, _, _, c in plan if m == "pool")
+        n_net = n_self + n_pool                                    # self then pool: envs [0, n_self) and [n_self, n_net)
+        if n_pool:                                                 # the rollout's only draw, the same on every rank
+            self.opponent_model.load_state_dict(self.opponent_pool[self.np_rng.randint(len(self.opponent_pool))])
+        self._freeze_tower_packs(True)
+        dev = self.device
+        if self._acts is None:
+            dt = self.obs_buf.dtype
+            self._acts = torch.empty((N, 4), dtype=torch.int8, device=dev)
+            self._opp_obs = torch.empty((N, 2) + self.obs_shape, dtype=dt, device=dev)
+            self._boot_obs = torch.empty((N, 2) + self.obs_shape, dtype=dt, device=dev)
+            self._boot_merged = torch.empty((N,) + self.obs_shape, dtype=dt, device=dev)
+        red_host = np.zeros(N, np.uint8)
+        acts_host = np.full((N, 4), _lib.ACTION_RANDOM_LEGAL, np.int8)
+        for mode, red, first, count in plan:
+            red_host[first:first + count] = red
+            if mode in BOT_TEAMS:                                  # (bot groups are blue: the bots play agents 0 and 2)
+                acts_host[first:first + count, 1 if red else 0], acts_host[first:first + count, 3 if red else 2] = BOT_TEAMS[mode]
+        red_u8 = torch.from_numpy(red_host).to(dev)
+        inv_u8 = 1 - red_u8
+        red_b = red_u8.to(torch.bool)
+        acts = self._acts
+        acts.copy_(torch.from_numpy(acts_host))
+        self.mix_groups, self.team_red = plan, red_u8
+        opp_obs = self._opp_obs[:n_net]
+        ep_ret = torch.zeros((), dtype=torch.float64, device=dev)
+        done_env = torch.zeros(N, dtype=torch.int64, device=dev)
+        win_env = torch.zeros(N, dtype=torch.int64, device=dev)
+        mappo_alg = self.algorithm == "mappo"
+        masks = self.mask_illegal
+        lg = None
+        for t in range(T):
+            env.emit_team_obs_mixed(red_u8, self.obs_buf[t], self.merged_buf[t] if mappo_alg else None)
+            if masks:
+                self.legal_buf[t].copy_(mappo.canonicalize_legal(mappo.team_columns(env.legal, red_u8), red_u8))
+                lg = self.legal_buf[t]
+            if mappo_alg:
+                a, lp, v = self._forward_policy(self.model, self.obs_buf[t], self.merged_buf[t], True, lg)
+                self.val_buf[t].copy_(v[:, None].expand(N, 2))
+            else:
+                a, lp, v = self._forward_policy(self.model, self.obs_buf[t], self.obs_buf[t].view((-1,) + self.obs_shape), True, lg)
+                self.val_buf[t].copy_(v.view(N, 2))
+            self.act_buf[t].copy_(a)
+            self.logp_buf[t].copy_(lp)
+            mappo.set_team_columns(acts, red_u8, mappo.canonicalize_action(a, red_u8))
+            if n_net:
+                env.emit_team_obs_mixed(inv_u8, opp_obs, None, 0, n_net)     # the opponent is red where the learner is blue
+                olg = mappo.canonicalize_legal(mappo.team_columns(env.legal, red_u8, opponents=True), inv_u8) if masks else None
+                for model, lo, hi in ((self.model, 0, n_self), (self.opponent_model, n_self, n_net)):
+                    if hi > lo:
+                        oa, _, _ = self._forward_policy(model, opp_obs[lo:hi], None, False, olg[lo:hi] if masks else None)
+                        mappo.set_team_columns(acts[lo:hi], red_u8[lo:hi], mappo.canonicalize_action(oa, inv_u8[lo:hi]), opponents=True)
+            _, rew, done, info = env.step(acts, want_obs=False)
+            cur_agent = info["agent"]
+            shp = shaping_from_agent_words(mappo.team_columns(self.prev_agent, red_u8), mappo.team_columns(cur_agent, red_u8))   # [N,2] f64
+            own = torch.where(red_b, rew[:, 0], rew[:, 1])
+            team_reward = own + own                                  # sum over the two learners' (identical) rewards
+            self.rew_buf[t].copy_((team_reward[:, None] + mappo.SHAPING_SCALE * shp).to(torch.float32))
+            d = done.to(torch.bool)
+            self.done_buf[t].copy_(done.to(torch.float32)[:, None].expand(N, 2))
+            self.prev_agent = torch.where(d[:, None], self.start_words[None].expand(N, 4), cur_agent)
+            ep_ret += team_reward.sum()
+            done_env += d
+            sc = info["score"]
+            win_env += d & torch.where(red_b, sc > 0, sc < 0)
+        # bootstrap value of the state after the last tick (:541-546)
+        env.emit_team_obs_mixed(red_u8, self._boot_obs, self._boot_merged if mappo_alg else None)
+        ctx = torch.autocast(device_type=self.device.type, dtype=self.autocast_dtype) if self.autocast_dtype else _NullCtx()
+        with torch.no_grad(), ctx:
+            if mappo_alg:
+                self.last_value = self.model.value(self._net_in(self._boot_merged)).float()[:, None].expand(N, 2).contiguous()
+            else:
+                self.last_value = self.model.value(self._net_in(self._boot_obs.view((-1,) + self.obs_shape))).float().view(N, 2)
+        self._freeze_tower_packs(False)
+        by_mode = {}
+        for mode, _, first, count in plan:
+            e, w = by_mode.get(mode, (0, 0))
+            by_mode[mode] = (e + done_env[first:first + count].sum(), w + win_env[first:first + count].sum())
+        self.stats.update(opponent="mixed", play_as_red=None, rollout_reward=ep_ret, episodes=done_env.sum(), wins=win_env.sum(),
+                          episodes_by_mode={m: e for m, (e, _) in by_mode.items()}, wins_by_mode={m: w for m, (_, w) in by_mode.items()})
 
     def compute_gae(self):
         T, n = self.T, self.N * 2
@@ -402,6 +532,8 @@ class VecMAPPOTrainer:
         # (the mask flag and the sampler's counter are written only when the flag is on: a file of the default path is the one
         # earlier versions wrote)
         extra = {"mask_illegal": 1, "sample_counter": int(self.sample_counter)} if self.mask_illegal else {}
+        if self.mix_opponents:                                           # (likewise written only when on)
+            extra["mix_opponents"] = 1
         torch.save({**extra, "data": self.learner.bucket.data, "ema": self.learner.ema, "exp_avg": self.learner.exp_avg,
                     "exp_avg_sq": self.learner.exp_avg_sq, "step": int(self.learner.step_count), "update": int(self.update_idx),
                     "total_updates": int(self.total_updates), "pool": list(self.opponent_pool), "gen": self.gen.get_state(),
@@ -418,6 +550,9 @@ class VecMAPPOTrainer:
         if bool(ck.get("mask_illegal", 0)) != self.mask_illegal:          # (no key: written with the flag off)
             raise ValueError(f"checkpoint was written with mask_illegal={bool(ck.get('mask_illegal', 0))}, this trainer has "
                              f"mask_illegal={self.mask_illegal}: a policy trained under masks is sampled under masks")
+        if bool(ck.get("mix_opponents", 0)) != self.mix_opponents:        # (no key: written with the flag off)
+            raise ValueError(f"checkpoint was written with mix_opponents={bool(ck.get('mix_opponents', 0))}, this trainer has "
+                             f"mix_opponents={self.mix_opponents}: the opponent draws of the two schemes do not continue one another")
         if int(ck["total_updates"]) != int(self.total_updates):
             raise ValueError(f"checkpoint was written for a schedule of {ck['total_updates']} updates, this trainer has {self.total_updates}")
         self.learner.restore(ck)                                         # (weights, Adam moments, EMA and step count: the same keys)
@@ -464,11 +599,17 @@ def evaluate_vs_bots(model, num_episodes=20, layout_file="bloxCapture", teams=("
 
 @torch.no_grad()
 def evaluate_vectorized(model, layout="bloxCapture", n_envs=1024, opponent="baseline", length=300, device="cuda:0", seed=0,
-                        autocast=True, mask_illegal=False):
+                        autocast=True, mask_illegal=False, side="blue"):
     """evaluate_vs_bots (pacman_mappo_resnet.py:293-337) for n_envs episodes at once: the learner plays blue with argmax
     actions against the in-kernel randomTeam / baselineTeam / approxQTeam (opponent "random" / "baseline" / "approxq"), one episode per env (an env stops counting at its first done).
     Returns (mean episode return of the learner team as the reference sums it, std, win rate = share with final score < 0).
-    mask_illegal: the argmax runs over the legal actions only (a policy trained with the trainer's mask_illegal)."""
+    mask_illegal: the argmax runs over the legal actions only (a policy trained with the trainer's mask_illegal).
+    side: "blue" as above; "red": the learner plays red and the bots blue; "both": red in the first half of the envs, blue in
+    the rest (a policy trained with mix_opponents plays both colours).  A red learner's win is a final score > 0."""
+    if side not in ("blue", "red", "both"):
+        raise ValueError(f"side must be blue, red or both, got {side!r}")
+    if side != "blue":
+        return _evaluate_sides(model, layout, n_envs, opponent, length, device, seed, autocast, mask_illegal, side)
     dev = torch.device(device)
     env = PmxVecEnv(layout, n_envs, length=length, auto_reset=True, obs_dtype="bfloat16" if autocast else "float32", device=dev,
                     seed=seed, bots=opponent in BOT_TEAMS)
@@ -503,6 +644,50 @@ def evaluate_vectorized(model, layout="bloxCapture", n_envs=1024, opponent="base
     if was_training:
         model.train()
     return float(ret.mean()), float(ret.std()), float((final < 0).double().mean())
+
+
+def _evaluate_sides(model, layout, n_envs, opponent, length, device, seed, autocast, mask_illegal, side):
+    """evaluate_vectorized with the learner's colour chosen per env: observations from pmx_emit_team_obs_mixed (canonical, so the
+    policy sees a red game as it was trained to), actions and masks through the per-env frame helpers."""
+    dev = torch.device(device)
+    env = PmxVecEnv(layout, n_envs, length=length, auto_reset=True, obs_dtype="bfloat16" if autocast else "float32", device=dev,
+                    seed=seed, bots=opponent in BOT_TEAMS)
+    env.reset(want_obs=False)
+    was_training = model.training
+    model.eval()
+    red = torch.zeros(n_envs, dtype=torch.uint8, device=dev)
+    red[:n_envs if side == "red" else n_envs // 2] = 1
+    red_b = red.to(torch.bool)
+    alive = torch.ones(n_envs, dtype=torch.bool, device=dev)
+    ret = torch.zeros(n_envs, dtype=torch.float64, device=dev)
+    final = torch.zeros(n_envs, dtype=torch.int32, device=dev)
+    opp = BOT_TEAMS.get(opponent, (_lib.ACTION_RANDOM_LEGAL,) * 2)
+    acts = torch.empty((n_envs, 4), dtype=torch.int8, device=dev)
+    mappo.set_team_columns(acts, red, torch.tensor(opp, dtype=torch.int8, device=dev)[None].expand(n_envs, 2), opponents=True)
+    team_obs = torch.empty((n_envs, 2) + env.obs_shape, dtype=env.obs_torch_dtype, device=dev)
+    ctx = torch.autocast(device_type=dev.type, dtype=torch.bfloat16) if autocast else _NullCtx()
+    for _ in range(length + 1):
+        env.emit_team_obs_mixed(red, team_obs)
+        lo = team_obs.view((-1,) + env.obs_shape)
+        with ctx:
+            if mask_illegal:
+                lg = mappo.canonicalize_legal(mappo.team_columns(env.legal, red), red).reshape(-1)
+                a = model.get_deterministic_action(lo, legal=lg).view(n_envs, 2)
+            else:
+                a = model.get_deterministic_action(lo).view(n_envs, 2)
+        mappo.set_team_columns(acts, red, mappo.canonicalize_action(a, red))
+        _, rew, done, info = env.step(acts, want_obs=False)
+        own = torch.where(red_b, rew[:, 0], rew[:, 1])
+        ret += torch.where(alive, own + own, torch.zeros_like(ret))                 # sum over both learners' rewards (:328)
+        d = done.to(torch.bool) & alive
+        final = torch.where(d, info["score"], final)
+        alive &= ~d
+        if not bool(alive.any()):
+            break
+    env.close()
+    if was_training:
+        model.train()
+    return float(ret.mean()), float(ret.std()), float(torch.where(red_b, final > 0, final < 0).double().mean())
 
 
 class _NullCtx:

@@ -200,6 +200,24 @@ class PmxVecEnv:
                       merged.data_ptr() if merged is not None else None, _lib.stream(self.device))
         return team_obs, merged
 
+    def emit_team_obs_mixed(self, team_red, team_obs, merged=None, first=0, count=None):
+        """emit_team_obs with the learners' colour chosen per env (pmx_emit_team_obs_mixed): team_red uint8 [N], non-zero = that
+        env's learners are red.  Writes rows for the envs first .. first + count - 1 (count None: up to the last env), row j for
+        env first + j, into team_obs [count,2,8,H,W] and, if given, merged [count,8,H,W]."""
+        N = self.n_envs
+        first = int(first)
+        count = N - first if count is None else int(count)
+        assert team_red.shape == (N,) and team_red.dtype == torch.uint8 and team_red.is_contiguous() and team_red.device == team_obs.device
+        assert team_obs.shape == (count, 2) + self.obs_shape and team_obs.dtype == self.obs_torch_dtype and team_obs.is_contiguous()
+        if merged is not None:
+            assert merged.shape == (count,) + self.obs_shape and merged.dtype == self.obs_torch_dtype and merged.is_contiguous()
+        if count == 0:                                   # (an empty tensor has no address to pass)
+            return team_obs, merged
+        with torch.cuda.device(self.device):
+            _lib.call("pmx_emit_team_obs_mixed", self.handle, team_red.data_ptr(), first, count, team_obs.data_ptr(),
+                      merged.data_ptr() if merged is not None else None, _lib.stream(self.device))
+        return team_obs, merged
+
     # -- measurement ---------------------------------------------------------------------------------------------
     def profile_begin(self, max_launches):
         _lib.call("pmx_profile_begin", self.handle, int(max_launches))

@@ -49,6 +49,10 @@ def parser():
     ap.add_argument("--curriculum-scale", type=float, default=1.0, help="compress the curriculum's phase thresholds (updates 200 / 800)")
     ap.add_argument("--mask-illegal", action="store_true", help="sample, train and evaluate over the legal actions only (the env's legal-action masks; "
                                                                 "off by default: the reference samples from all five logits)")
+    ap.add_argument("--mix-opponents", action="store_true", help="spread the opponent mixture over the envs of every rollout (self / pool / bots side by side, "
+                                                                 "both colours) instead of one opponent and one colour per rollout")
+    ap.add_argument("--eval-side", default="blue", choices=["blue", "red", "both"], help="the colour the evaluated policy plays (both: red in the first half of "
+                                                                                         "the envs); a policy trained with --mix-opponents plays both")
     ap.add_argument("--graph", action="store_true", help="replay the optimizer step from a hipGraph (launch-bound minibatches, e.g. 512)")
     return ap
 
@@ -90,22 +94,24 @@ def main():
     tr = trainer.VecMAPPOTrainer(layout, args.envs, horizon=args.horizon, minibatch=args.minibatch, epochs=args.epochs, redraw_layouts=args.redraw,
                                  obs_dtype=args.obs, device=f"cuda:{local}", seed=args.seed, rank=rank, world_size=world,
                                  total_updates=args.total_updates, opponent=args.opponent, algorithm=args.algorithm, use_graph=args.graph, paired_minibatches=not args.unpaired, curriculum_scale=args.curriculum_scale,
-                                 hard_bots=tuple(args.hard_bots.split(",")), mask_illegal=args.mask_illegal)
+                                 hard_bots=tuple(args.hard_bots.split(",")), mask_illegal=args.mask_illegal,
+                                 **({"mix_opponents": True} if args.mix_opponents else {}))
     for u in range(args.updates):
         torch.cuda.synchronize(); t0 = time.perf_counter()
         st = tr.train_update()
         torch.cuda.synchronize(); dt = time.perf_counter() - t0
         if rank == 0:
             f = lambda k: float(st[k]) if k in st else None
+            by_mode = {"by_mode": {m: [int(st["episodes_by_mode"][m]), int(st["wins_by_mode"][m])] for m in st["episodes_by_mode"]}} if args.mix_opponents else {}
             emit(dict(update=u, algorithm=args.algorithm, opponent=st["opponent"], red=st["play_as_red"], sec=round(dt, 3),
                                   env_steps_per_s=round(world * tr.N * tr.T / dt), episodes=int(st["episodes"]),
                                   win_rate=(float(st["wins"]) / max(int(st["episodes"]), 1)),
                                   reward=float(st["rollout_reward"]) / max(tr.N, 1), pg=f("pg"), vl=f("vl"), entropy=f("entropy"),
-                                  clip_frac=f("clip_frac"), grad_norm=f("grad_norm"), steps=st["optimizer_steps"]))
+                                  clip_frac=f("clip_frac"), grad_norm=f("grad_norm"), steps=st["optimizer_steps"], **by_mode))
             if args.eval_every and u and u % args.eval_every == 0:
                 emit(dict(update=u, algorithm=args.algorithm,
-                          eval_vs_baseline=trainer.evaluate_vectorized(tr.model, eval_layout, 1024, "baseline", device=f"cuda:{local}", mask_illegal=args.mask_illegal),
-                          eval_vs_random=trainer.evaluate_vectorized(tr.model, eval_layout, 1024, "random", device=f"cuda:{local}", mask_illegal=args.mask_illegal)))
+                          eval_vs_baseline=trainer.evaluate_vectorized(tr.model, eval_layout, 1024, "baseline", device=f"cuda:{local}", mask_illegal=args.mask_illegal, side=args.eval_side),
+                          eval_vs_random=trainer.evaluate_vectorized(tr.model, eval_layout, 1024, "random", device=f"cuda:{local}", mask_illegal=args.mask_illegal, side=args.eval_side)))
     if rank == 0 and args.save:
         tr.save_ema(args.save)
     if world > 1:
