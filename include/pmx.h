@@ -211,6 +211,19 @@ int pmx_emit_team_obs(pmx_env *env, int team_red, void *team_obs_dev, void *merg
 int pmx_emit_team_obs_mixed(pmx_env *env, const uint8_t *team_red_dev, int32_t first, int32_t count, void *team_obs_dev,
                             void *merged_dev, void *stream);
 
+/* The contest's sight rule on the learners' planes (GameState.makeObservation, capture.py:268-292, which gymPacMan's
+ * get_Observation never applies).  The two calls above with one difference: in a learner's plane 5 the cell of enemy e is 0
+ * unless min over the two team agents m of |x_e - x_m| + |y_e - y_m| <= sight_range, all positions taken from the snapshot
+ * that learner's planes are encoded from.  The rule is the team's (an enemy next to either learner shows in both), and the two
+ * learners read different snapshots, so one enemy can show in one slot and not in the other.  The merged slot is the
+ * full-information critic input: byte for byte that of the call without fog.  sight_range 0 .. PMX_SIGHT_RANGE_MAX, anything
+ * else is PMX_ERR_INVALID and launches nothing; from 62 on (the longest distance on a 32 x 32 board) nothing is hidden. */
+#define PMX_SIGHT_RANGE 5       /* capture.py:69 */
+#define PMX_SIGHT_RANGE_MAX 64
+int pmx_emit_team_obs_fog(pmx_env *env, int team_red, int32_t sight_range, void *team_obs_dev, void *merged_dev, void *stream);
+int pmx_emit_team_obs_mixed_fog(pmx_env *env, const uint8_t *team_red_dev, int32_t first, int32_t count, int32_t sight_range,
+                                void *team_obs_dev, void *merged_dev, void *stream);
+
 /* The layout each env is currently on (host output [n_envs]; all zeros for a single-layout handle).  Synchronises the stream. */
 int pmx_get_layout_index(pmx_env *env, int32_t *index_out, void *stream);
 
@@ -229,7 +242,7 @@ int pmx_maze_distances_layout(pmx_env *env, int32_t layout, int8_t *cells_dev, u
 /* Measurement hooks (no reference counterpart): between begin and end, every tick attaches a start and a stop HIP event
  * to its rule-kernel and to its expansion-kernel dispatch on the caller's stream (hipExtLaunchKernelGGL); end
  * synchronises them and returns the summed kernel durations (milliseconds) and launch counts.  bench.py's roofline
- * figures come from here.  A pmx_emit_team_obs or pmx_emit_team_obs_mixed launch is recorded with the expansion launches (a
+ * figures come from here.  A pmx_emit_team_obs or pmx_emit_team_obs_mixed launch (or its _fog form) is recorded with the expansion launches (a
  * training loop calls it in place of the four-agent expansion).
  * While a profile is open pmx_step runs the FULL expansion: outside one it stores the wall plane (plane 0, a per-layout
  * constant) from extra blocks of the rule launch and starts the expansion kernel behind it (float32 planes up to 900 MB, no

@@ -79,6 +79,8 @@ PROTOTYPES = [
     ("pmx_observe", C.c_int, [_VP, _VP, _VP, _VP]),
     ("pmx_emit_team_obs", C.c_int, [_VP, C.c_int, _VP, _VP, _VP]),
     ("pmx_emit_team_obs_mixed", C.c_int, [_VP, _VP, _I32, _I32, _VP, _VP, _VP]),
+    ("pmx_emit_team_obs_fog", C.c_int, [_VP, C.c_int, _I32, _VP, _VP, _VP]),
+    ("pmx_emit_team_obs_mixed_fog", C.c_int, [_VP, _VP, _I32, _I32, _I32, _VP, _VP, _VP]),
     ("pmx_get_layout_index", C.c_int, [_VP, C.POINTER(_I32), _VP]),
     ("pmx_get_state", C.c_int, [_VP, _I32, _I32, C.POINTER(State), _VP]),
     ("pmx_set_state", C.c_int, [_VP, _I32, _I32, C.POINTER(State), _VP]),

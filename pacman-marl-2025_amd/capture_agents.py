@@ -71,6 +71,9 @@ class CaptureAgent:
     def registerTeam(self, agentsOnTeam):
         self.agentsOnTeam = agentsOnTeam
 
+    def observationFunction(self, gameState):                       # captureAgents.py:121-123: what a contest game hands the agent
+        return gameState.makeObservation(self.index)
+
     def getAction(self, gameState):
         self.observationHistory.append(gameState)
         myPos = gameState.getAgentState(self.index).getPosition()

@@ -18,6 +18,7 @@ extern "C" hipError_t pmx_launch_bot_query(const PmxTickParams *p, int H, int ag
                                            uint8_t *flags, hipStream_t st);
 extern "C" hipError_t pmx_launch_emit_team(const PmxEmitParams *p, int dtype, hipStream_t st, hipEvent_t ev0, hipEvent_t ev1);
 extern "C" hipError_t pmx_launch_emit_team_mixed(const PmxEmitParams *p, int dtype, hipStream_t st, hipEvent_t ev0, hipEvent_t ev1);
+extern "C" hipError_t pmx_launch_emit_team_fog(const PmxEmitParams *p, int mixed, int dtype, hipStream_t st, hipEvent_t ev0, hipEvent_t ev1);
 extern "C" hipError_t pmx_launch_expand(const PmxExpandParams *p, int dtype, hipStream_t st, hipEvent_t ev0, hipEvent_t ev1);
 extern "C" hipError_t pmx_launch_maze(const PmxLayoutDev *lay_dev, const int16_t *cell_index_dev, int n_cells,
                                       const int8_t *cells_dev, uint8_t *dist_dev, hipStream_t st);
@@ -472,6 +473,58 @@ int pmx_emit_team_obs_mixed(pmx_env *env, const uint8_t *team_red_dev, int32_t f
     x.first = first, x.count = count;
     hipEvent_t *ev = prof_pair(env, true);           // recorded with the expansion launches, as pmx_emit_team_obs is
     HIP_TRY(pmx_launch_emit_team_mixed(&x, env->cfg.obs_dtype, as_stream(stream), ev ? ev[0] : nullptr, ev ? ev[1] : nullptr));
+    return PMX_OK;
+}
+
+// The fog pair: the same parameter block as the pair above plus the sight range, checked before anything is launched.
+int pmx_emit_team_obs_fog(pmx_env *env, int team_red, int32_t sight_range, void *team_obs_dev, void *merged_dev, void *stream)
+{
+    if (!env || !team_obs_dev) return fail(PMX_ERR_INVALID, "pmx_emit_team_obs_fog: null argument");
+    if (sight_range < 0 || sight_range > PMX_SIGHT_RANGE_MAX)
+        return fail(PMX_ERR_INVALID, "pmx_emit_team_obs_fog: sight_range %d outside 0 .. %d", sight_range, PMX_SIGHT_RANGE_MAX);
+    if (env->open_agent != 0) return fail(PMX_ERR_INVALID, "pmx_emit_team_obs_fog: a tick opened with pmx_step_agent is unfinished");
+    PmxEmitParams x;
+    std::memset(&x, 0, sizeof(x));
+    const size_t snap_sz = (size_t)PMX_SNAP_WORDS(env->lay.H) * env->cfg.n_envs;
+    for (int a = 0; a < 4; ++a) x.snap[a] = (env->snaps_valid && a < 3) ? env->snap_dev + a * snap_sz : env->state_dev;
+    x.lay = env->lay_dev;
+    x.layout_idx = env->layout_idx_dev;
+    x.team_obs = team_obs_dev;
+    x.merged = merged_dev;
+    x.N = env->cfg.n_envs;
+    x.red = team_red ? 1 : 0;
+    x.lay_H = env->lay.H, x.lay_W = env->lay.W;
+    x.sight = sight_range;
+    hipEvent_t *ev = prof_pair(env, true);           // recorded with the expansion launches, as pmx_emit_team_obs is
+    HIP_TRY(pmx_launch_emit_team_fog(&x, 0, env->cfg.obs_dtype, as_stream(stream), ev ? ev[0] : nullptr, ev ? ev[1] : nullptr));
+    return PMX_OK;
+}
+
+int pmx_emit_team_obs_mixed_fog(pmx_env *env, const uint8_t *team_red_dev, int32_t first, int32_t count, int32_t sight_range,
+                                void *team_obs_dev, void *merged_dev, void *stream)
+{
+    if (!env || !team_red_dev || !team_obs_dev) return fail(PMX_ERR_INVALID, "pmx_emit_team_obs_mixed_fog: null argument");
+    if (first < 0 || count < 0 || (int64_t)first + count > env->cfg.n_envs)
+        return fail(PMX_ERR_INVALID, "pmx_emit_team_obs_mixed_fog: envs %d .. %lld of %d", first, (long long)first + count - 1, env->cfg.n_envs);
+    if (sight_range < 0 || sight_range > PMX_SIGHT_RANGE_MAX)
+        return fail(PMX_ERR_INVALID, "pmx_emit_team_obs_mixed_fog: sight_range %d outside 0 .. %d", sight_range, PMX_SIGHT_RANGE_MAX);
+    if (env->open_agent != 0) return fail(PMX_ERR_INVALID, "pmx_emit_team_obs_mixed_fog: a tick opened with pmx_step_agent is unfinished");
+    if (count == 0) return PMX_OK;
+    PmxEmitParams x;
+    std::memset(&x, 0, sizeof(x));
+    const size_t snap_sz = (size_t)PMX_SNAP_WORDS(env->lay.H) * env->cfg.n_envs;
+    for (int a = 0; a < 4; ++a) x.snap[a] = (env->snaps_valid && a < 3) ? env->snap_dev + a * snap_sz : env->state_dev;
+    x.lay = env->lay_dev;
+    x.layout_idx = env->layout_idx_dev;
+    x.team_obs = team_obs_dev;
+    x.merged = merged_dev;
+    x.N = env->cfg.n_envs;
+    x.lay_H = env->lay.H, x.lay_W = env->lay.W;
+    x.team_red = team_red_dev;
+    x.first = first, x.count = count;
+    x.sight = sight_range;
+    hipEvent_t *ev = prof_pair(env, true);
+    HIP_TRY(pmx_launch_emit_team_fog(&x, 1, env->cfg.obs_dtype, as_stream(stream), ev ? ev[0] : nullptr, ev ? ev[1] : nullptr));
     return PMX_OK;
 }
 

@@ -107,6 +107,9 @@ struct PmxEmitParams {
     // `red`, and the env range of the launch -- team_obs / merged then hold `count` rows, row j for env first + j
     const uint8_t *team_red;     // [N], non-zero = red
     int32_t first, count;
+    // pmx_emit_team_obs_fog / _mixed_fog only (pmx_emit_team_kernel<DT, MIXED, true>; zero and unread otherwise): an enemy shows
+    // in a learner's plane 5 only within this Manhattan distance of one of the two team agents (capture.py:285-291)
+    int32_t sight;
 };
 
 // Host-side launch tuning, changed through pmx_set_tuning: -1 = the built-in choice.

@@ -1558,7 +1558,12 @@ __device__ __forceinline__ uint32_t flip_row(uint32_t v, int W, bool flip) { ret
 // MIXED (pmx_emit_team_obs_mixed): the colour is the ENV's (p.team_red[env], read once per wave, so first / second / flip stay
 // wave-uniform) and the launch covers the envs p.first .. p.first + p.count - 1, output row j = env p.first + j.  The uniform
 // instantiation reads none of the three fields and is the kernel it was before they existed.
-template <int DT, bool MIXED>
+// FOG (pmx_emit_team_obs_fog / _mixed_fog): the contest's sight rule (capture.py:285-291) on the learners' slots.  An enemy whose
+// Manhattan distance to BOTH team agents, in the snapshot of the half that encodes it, exceeds p.sight is left out of that half's
+// stream; the merged slot stays full-information, so the first half's hidden enemies (at most two bit offsets, wave-uniform) are
+// put back in registers while slot 2 is expanded, as the mate's bit is.  Everything is under `if constexpr (FOG)`: the six
+// instantiations without it read no new field and are the code they were.
+template <int DT, bool MIXED, bool FOG>
 __global__ __launch_bounds__(PMX_BLOCK) void pmx_emit_team_kernel(PmxEmitParams p)
 {
     constexpr int VEC = ObsVec<DT>::VEC;
@@ -1618,11 +1623,27 @@ __global__ __launch_bounds__(PMX_BLOCK) void pmx_emit_team_kernel(PmxEmitParams 
         stream_or_row(T, (uint32_t)(((flip ? 6 : 7) * H + hl) * W), red, W);
     }
     uint32_t pt_off = 0;                                      // lanes 0-3 of each half: that agent's bit offset in the stream
+    [[maybe_unused]] int hid_v = -1;                          // FOG, lanes 0-3 of each half: pt_off of an enemy this half does not see
+    [[maybe_unused]] uint32_t team_a = 0, team_b = 0;         // FOG: word A of the two team agents in this half's snapshot
+    if constexpr (FOG) {
+        const int a0 = first ? __builtin_amdgcn_readlane((int)pt, 1) : __builtin_amdgcn_readlane((int)pt, 0);
+        const int b0 = first ? __builtin_amdgcn_readlane((int)pt, 3) : __builtin_amdgcn_readlane((int)pt, 2);
+        const int a1 = first ? __builtin_amdgcn_readlane((int)pt, 33) : __builtin_amdgcn_readlane((int)pt, 32);
+        const int b1 = first ? __builtin_amdgcn_readlane((int)pt, 35) : __builtin_amdgcn_readlane((int)pt, 34);
+        team_a = (uint32_t)(half ? a1 : a0), team_b = (uint32_t)(half ? b1 : b0);
+    }
     if (hl < 4) {
         const int x0 = pt & 0xFF, y = (pt >> 8) & 0xFF, x = flip ? W - 1 - x0 : x0;
         const int plane = hl == agent ? 1 : (((hl ^ agent) == 2) ? 4 : 5);
         pt_off = (uint32_t)((plane * H + y) * W + x);
-        atomicOr(&T[pt_off >> 5], 1u << (pt_off & 31));
+        bool shown = true;
+        if constexpr (FOG) {                                  // the x-flip keeps |dx|, so the snapshot's own coordinates serve
+            const int da = abs(x0 - (int)(team_a & 0xFF)) + abs(y - (int)((team_a >> 8) & 0xFF));
+            const int db = abs(x0 - (int)(team_b & 0xFF)) + abs(y - (int)((team_b >> 8) & 0xFF));
+            shown = plane != 5 || (da < db ? da : db) <= p.sight;
+            if (!shown) hid_v = (int)pt_off;
+        }
+        if (shown) atomicOr(&T[pt_off >> 5], 1u << (pt_off & 31));
     } else if (hl < 8) {
         const uint32_t cxy = (pt >> (16 * ((hl - 4) & 1))) & 0xFFFFu;
         if (cxy != 0xFFFFu) {
@@ -1646,6 +1667,12 @@ __global__ __launch_bounds__(PMX_BLOCK) void pmx_emit_team_kernel(PmxEmitParams 
     if (fmate == fself0) {
         carry_m = carry0 > carry1 ? carry0 : carry1;
         fmate = -1;
+    }
+    // FOG: the first half's hidden enemies (its lanes 1 - first and 3 - first), -1 = seen; two on one cell share their distances
+    [[maybe_unused]] int hid_a = -1, hid_b = -1;
+    if constexpr (FOG) {
+        hid_a = first ? __builtin_amdgcn_readlane(hid_v, 0) : __builtin_amdgcn_readlane(hid_v, 1);
+        hid_b = first ? __builtin_amdgcn_readlane(hid_v, 2) : __builtin_amdgcn_readlane(hid_v, 3);
     }
     __builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "wavefront");
     __builtin_amdgcn_wave_barrier();
@@ -1671,6 +1698,11 @@ __global__ __launch_bounds__(PMX_BLOCK) void pmx_emit_team_kernel(PmxEmitParams 
                 if (d4 < (uint32_t)VEC) bits[u] &= ~(1u << d4);
                 const uint32_t d2 = (uint32_t)(fmate - (int)e0s[u]);
                 if (fmate >= 0 && d2 < (uint32_t)VEC) bits[u] |= 1u << d2;
+                if constexpr (FOG) {                          // nothing is hidden from the critic (-1 - e0 is no offset below VEC)
+                    const uint32_t ha = (uint32_t)(hid_a - (int)e0s[u]), hb = (uint32_t)(hid_b - (int)e0s[u]);
+                    if (ha < (uint32_t)VEC) bits[u] |= 1u << ha;
+                    if (hb < (uint32_t)VEC) bits[u] |= 1u << hb;
+                }
             }
         }
         uint4 v[U];
@@ -1704,15 +1736,30 @@ __global__ __launch_bounds__(PMX_BLOCK) void pmx_emit_team_kernel(PmxEmitParams 
 extern "C" hipError_t pmx_launch_emit_team(const PmxEmitParams *p, int dtype, hipStream_t st, hipEvent_t ev0, hipEvent_t ev1)
 {
     const unsigned blocks = (unsigned)(((long)p->N + 3) / 4);    // one wave per env
-#define PMX_EMIT(DT, MIXED)                                                                                                   \
-    do {                                                                                                                      \
-        if (ev0) hipExtLaunchKernelGGL((pmx_emit_team_kernel<DT, MIXED>), dim3(blocks), dim3(PMX_BLOCK), 0, st, ev0, ev1, 0, *p); \
-        else hipLaunchKernelGGL((pmx_emit_team_kernel<DT, MIXED>), dim3(blocks), dim3(PMX_BLOCK), 0, st, *p);                  \
+#define PMX_EMIT(DT, MIXED, FOG)                                                                                                   \
+    do {                                                                                                                           \
+        if (ev0) hipExtLaunchKernelGGL((pmx_emit_team_kernel<DT, MIXED, FOG>), dim3(blocks), dim3(PMX_BLOCK), 0, st, ev0, ev1, 0, *p); \
+        else hipLaunchKernelGGL((pmx_emit_team_kernel<DT, MIXED, FOG>), dim3(blocks), dim3(PMX_BLOCK), 0, st, *p);                  \
     } while (0)
     switch (dtype) {
-    case 0: PMX_EMIT(0, false); break;
-    case 1: PMX_EMIT(1, false); break;
-    default: PMX_EMIT(2, false); break;
+    case 0: PMX_EMIT(0, false, false); break;
+    case 1: PMX_EMIT(1, false, false); break;
+    default: PMX_EMIT(2, false, false); break;
+    }
+    return hipGetLastError();
+}
+
+// pmx_emit_team_obs_fog / pmx_emit_team_obs_mixed_fog: p->sight set; mixed != 0: the fields of pmx_launch_emit_team_mixed too
+extern "C" hipError_t pmx_launch_emit_team_fog(const PmxEmitParams *p, int mixed, int dtype, hipStream_t st, hipEvent_t ev0, hipEvent_t ev1)
+{
+    const unsigned blocks = (unsigned)(((long)(mixed ? p->count : p->N) + 3) / 4);
+    switch (dtype + (mixed ? 3 : 0)) {
+    case 0: PMX_EMIT(0, false, true); break;
+    case 1: PMX_EMIT(1, false, true); break;
+    case 2: PMX_EMIT(2, false, true); break;
+    case 3: PMX_EMIT(0, true, true); break;
+    case 4: PMX_EMIT(1, true, true); break;
+    default: PMX_EMIT(2, true, true); break;
     }
     return hipGetLastError();
 }
@@ -1722,9 +1769,9 @@ extern "C" hipError_t pmx_launch_emit_team_mixed(const PmxEmitParams *p, int dty
 {
     const unsigned blocks = (unsigned)(((long)p->count + 3) / 4);
     switch (dtype) {
-    case 0: PMX_EMIT(0, true); break;
-    case 1: PMX_EMIT(1, true); break;
-    default: PMX_EMIT(2, true); break;
+    case 0: PMX_EMIT(0, true, false); break;
+    case 1: PMX_EMIT(1, true, false); break;
+    default: PMX_EMIT(2, true, false); break;
     }
 #undef PMX_EMIT
     return hipGetLastError();

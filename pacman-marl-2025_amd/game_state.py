@@ -7,6 +7,7 @@ for every legal action's successor: agents/baselineTeam.py:65-104).  What runs o
 unpacking bit rows into Grid-like objects, splitting them at the half line (capture.py:332-350).
 """
 import ctypes as C
+import random
 
 import torch
 
@@ -15,6 +16,19 @@ from .vec_env import LEGAL_LIST_ORDER, PmxVecEnv
 
 DIR_NAMES = ("North", "East", "South", "West", "Stop")            # action / direction codes 0..4
 DIR_CODE = {n: i for i, n in enumerate(DIR_NAMES)}
+
+# what an agent is allowed to know about the others (capture.py:67-69)
+SONAR_NOISE_RANGE = 13                                             # odd: the readings are the true distance -6 .. +6
+SONAR_NOISE_VALUES = [i - (SONAR_NOISE_RANGE - 1) / 2 for i in range(SONAR_NOISE_RANGE)]
+SIGHT_RANGE = 5                                                    # Manhattan cells
+
+
+def _manhattan(a, b):
+    return abs(a[0] - b[0]) + abs(a[1] - b[1])
+
+
+def noisyDistance(pos1, pos2):                                     # capture.py:77-78: one random.choice per reading
+    return int(_manhattan(pos1, pos2) + random.choice(SONAR_NOISE_VALUES))
 
 
 class Directions:                                                  # game.py:49-68
@@ -76,11 +90,11 @@ class AgentState:                                                  # game.py:120
         self.isPacman, self.scaredTimer = is_pacman, scared
         self.numCarrying, self.numReturned = carrying, returned
 
-    def getPosition(self):
-        return self.configuration.getPosition()
+    def getPosition(self):                                         # None: an enemy out of sight in an observation
+        return None if self.configuration is None else self.configuration.getPosition()
 
     def getDirection(self):
-        return self.configuration.getDirection()
+        return None if self.configuration is None else self.configuration.getDirection()
 
 
 class _LayoutView:
@@ -146,6 +160,7 @@ class GameState:
         self.redTeam, self.blueTeam = [0, 2], [1, 3]                # capture.py:316-319 (validated by pmx_create)
         self.teams = [True, False, True, False]
         self.agentDistances = []
+        self._observation = False                                   # True on what makeObservation returns
 
     # -- accessors ------------------------------------------------------------------------------------------------
     def getLegalActions(self, agentIndex=0):                        # capture.py:101-105, list order N,S,E,W,Stop
@@ -214,8 +229,31 @@ class GameState:
     def isOnRedTeam(self, agentIndex):
         return self.teams[agentIndex]
 
-    def getAgentDistances(self):
-        return None
+    def getAgentDistances(self):                                    # the sonar of an observation; a plain state has none
+        return self.agentDistances if self._observation else None
+
+    def getDistanceProb(self, trueDistance, noisyDistance):         # capture.py:219-224
+        return 1.0 / SONAR_NOISE_RANGE if noisyDistance - trueDistance in SONAR_NOISE_VALUES else 0
+
+    def makeObservation(self, index):
+        """What agent `index` is allowed to see (capture.py:268-292): a copy of this state with the four sonar readings --
+        noisyDistance from the observer to every agent, drawn in agent order -- in agentDistances, and with the configuration of
+        every enemy that is farther than SIGHT_RANGE (Manhattan) from BOTH agents of the observer's team removed, so that
+        getAgentPosition returns None for it.  The draws are random.choice calls on the module-level generator, as the
+        reference's are: the same seed gives the same readings and leaves the stream at the same place."""
+        obs = GameState(self._layout, self.data.layout, self._state, self._legal, self._engine, self.data.timeleft, self.data.scoreChange)
+        for mine, theirs in zip(obs.data.agentStates, self.data.agentStates):
+            if theirs.configuration is None:                        # (an observation of an observation keeps what was hidden)
+                mine.configuration = None
+        pos = obs.getAgentPosition(index)
+        obs.agentDistances = [noisyDistance(pos, obs.getAgentPosition(i)) for i in range(obs.getNumAgents())]
+        obs._observation = True
+        team, others = (self.blueTeam, self.redTeam) if index in self.blueTeam else (self.redTeam, self.blueTeam)
+        for enemy in others:
+            where = obs.getAgentPosition(enemy)
+            if not any(_manhattan(where, obs.getAgentPosition(mate)) <= SIGHT_RANGE for mate in team):
+                obs.data.agentStates[enemy].configuration = None
+        return obs
 
     def getInitialAgentPosition(self, agentIndex):
         return self._layout.agent_positions[agentIndex]

@@ -107,13 +107,43 @@ def canonicalize_obs(o):
     return torch.flip(o, dims=[-1])[..., [0, 1, 3, 2, 4, 5, 7, 6], :, :]
 
 
+SIGHT_RANGE = 5                   # capture.py:69
+
+
+def fog_obs(obs, sight_range=SIGHT_RANGE):
+    """The contest's sight rule (GameState.makeObservation, capture.py:268-292) stated on observation planes [..., 8, H, W] of any
+    element type, raw or canonical (planes 1, 4 and 5 keep their index under canonicalize_obs and the x-flip keeps Manhattan
+    distances): the team's cells are the non-zero cells of planes 1 (self) and 4 (ally); an enemy cell of plane 5 is kept iff its
+    Manhattan distance to one of them is <= sight_range.  Returns a new tensor; every other plane is unchanged.  The rollout
+    gets the same planes from pmx_emit_team_obs_fog without a pass of its own; this is the path where no emission kernel runs
+    (evaluate_vs_bots) and the statement that kernel is tested against."""
+    H, W = obs.shape[-2], obs.shape[-1]
+    ys = torch.arange(H, device=obs.device).repeat_interleave(W)
+    xs = torch.arange(W, device=obs.device).repeat(H)
+    within = ((ys[:, None] - ys[None, :]).abs() + (xs[:, None] - xs[None, :]).abs() <= int(sight_range)).to(torch.float32)   # [HW, HW]
+    team = ((obs[..., 1, :, :] != 0) | (obs[..., 4, :, :] != 0)).reshape(obs.shape[:-3] + (H * W,)).to(torch.float32)
+    seen = (team @ within > 0).reshape(obs.shape[:-3] + (H, W))      # cells within sight of a team cell (a count of at most H * W: exact)
+    out = obs.clone()
+    out[..., 5, :, :] = torch.where(seen, obs[..., 5, :, :], torch.zeros_like(obs[..., 5, :, :]))
+    return out
+
+
 class VecMAPPOTrainer:
     def __init__(self, layout, n_envs, horizon=32, minibatch=512, epochs=UPDATE_EPOCHS, obs_dtype=None,
                  device="cuda:0", seed=0, rank=0, world_size=1, process_group=None, total_updates=2000, length=300,
                  use_autocast=True, opponent="random", use_graph=False, algorithm="mappo", paired_minibatches=True, curriculum_scale=1.0,
                  env=None, redraw_layouts=False, force_collectives=False, hard_bots=("baseline",), mask_illegal=False,
-                 mix_opponents=False):
+                 mix_opponents=False, fog_of_war=False, sight_range=SIGHT_RANGE):
         self.device = torch.device(device)
+        # fog_of_war: every policy input of the rollout (the learners', the self / pool opponent networks', the bootstrap
+        # observation) comes from the fog entry points -- an enemy shows only within sight_range of one of the team's agents, the
+        # contest's rule (capture.py:268-292) -- while merged_buf, the centralised critic's input, stays full-information.  Off: no
+        # keyword is passed and the calls are the ones made before the flag existed
+        self.fog_of_war = bool(fog_of_war)
+        self.sight_range = int(sight_range)
+        if self.fog_of_war and not 0 <= self.sight_range <= 64:
+            raise ValueError(f"sight_range must be 0 .. 64, got {sight_range!r}")
+        self._fog = {"sight_range": self.sight_range} if self.fog_of_war else {}
         self.rank, self.world_size = rank, world_size
         # hard_bots: the in-kernel teams the curriculum draws its "hard" opponent from (the reference's hard teams are
         # baselineTeam, AstarTeam and approxQTeam, pacman_mappo_resnet.py:40-47); the default keeps the draws of earlier versions
@@ -306,7 +336,7 @@ class VecMAPPOTrainer:
         own, other = (slice(0, 4, 2), slice(1, 4, 2)) if red else (slice(1, 4, 2), slice(0, 4, 2))   # learner_ids / opp_ids of env.legal
         lg = None
         for t in range(T):
-            env.emit_team_obs(red, self.obs_buf[t], self.merged_buf[t] if mappo_alg else None)
+            env.emit_team_obs(red, self.obs_buf[t], self.merged_buf[t] if mappo_alg else None, **self._fog)
             if masks:
                 # env.legal: the masks of the state this tick acts on (written by the reset, the last step or its auto-reset)
                 self.legal_buf[t].copy_(mappo.canonicalize_legal(env.legal[:, own], red))
@@ -321,7 +351,7 @@ class VecMAPPOTrainer:
             self.logp_buf[t].copy_(lp)
             acts[:, learner_ids] = mappo.canonicalize_action(a, red).to(torch.int8)
             if mode in ("self", "pool"):
-                env.emit_team_obs(not red, self._opp_obs, None)      # the opponent is red when the learner is blue
+                env.emit_team_obs(not red, self._opp_obs, None, **self._fog)      # the opponent is red when the learner is blue
                 # (under masks the opponent, a copy of a policy trained under masks, samples the same way under its own ids' masks)
                 oa, _, _ = self._forward_policy(self.opponent_model, self._opp_obs, None, False,
                                                 mappo.canonicalize_legal(env.legal[:, other], not red) if masks else None)
@@ -339,7 +369,7 @@ class VecMAPPOTrainer:
             sc = info["score"]
             n_win += (d & ((sc > 0) if red else (sc < 0))).sum()
         # bootstrap value of the state after the last tick (:541-546)
-        env.emit_team_obs(red, self._boot_obs, self._boot_merged if mappo_alg else None)
+        env.emit_team_obs(red, self._boot_obs, self._boot_merged if mappo_alg else None, **self._fog)
         ctx = torch.autocast(device_type=self.device.type, dtype=self.autocast_dtype) if self.autocast_dtype else _NullCtx()
         with torch.no_grad(), ctx:
             if mappo_alg:
@@ -390,7 +420,7 @@ class VecMAPPOTrainer:
         masks = self.mask_illegal
         lg = None
         for t in range(T):
-            env.emit_team_obs_mixed(red_u8, self.obs_buf[t], self.merged_buf[t] if mappo_alg else None)
+            env.emit_team_obs_mixed(red_u8, self.obs_buf[t], self.merged_buf[t] if mappo_alg else None, **self._fog)
             if masks:
                 self.legal_buf[t].copy_(mappo.canonicalize_legal(mappo.team_columns(env.legal, red_u8), red_u8))
                 lg = self.legal_buf[t]
@@ -404,7 +434,7 @@ class VecMAPPOTrainer:
             self.logp_buf[t].copy_(lp)
             mappo.set_team_columns(acts, red_u8, mappo.canonicalize_action(a, red_u8))
             if n_net:
-                env.emit_team_obs_mixed(inv_u8, opp_obs, None, 0, n_net)     # the opponent is red where the learner is blue
+                env.emit_team_obs_mixed(inv_u8, opp_obs, None, 0, n_net, **self._fog)     # the opponent is red where the learner is blue
                 olg = mappo.canonicalize_legal(mappo.team_columns(env.legal, red_u8, opponents=True), inv_u8) if masks else None
                 for model, lo, hi in ((self.model, 0, n_self), (self.opponent_model, n_self, n_net)):
                     if hi > lo:
@@ -424,7 +454,7 @@ class VecMAPPOTrainer:
             sc = info["score"]
             win_env += d & torch.where(red_b, sc > 0, sc < 0)
         # bootstrap value of the state after the last tick (:541-546)
-        env.emit_team_obs_mixed(red_u8, self._boot_obs, self._boot_merged if mappo_alg else None)
+        env.emit_team_obs_mixed(red_u8, self._boot_obs, self._boot_merged if mappo_alg else None, **self._fog)
         ctx = torch.autocast(device_type=self.device.type, dtype=self.autocast_dtype) if self.autocast_dtype else _NullCtx()
         with torch.no_grad(), ctx:
             if mappo_alg:
@@ -534,6 +564,8 @@ class VecMAPPOTrainer:
         extra = {"mask_illegal": 1, "sample_counter": int(self.sample_counter)} if self.mask_illegal else {}
         if self.mix_opponents:                                           # (likewise written only when on)
             extra["mix_opponents"] = 1
+        if self.fog_of_war:                                              # (likewise)
+            extra["fog_of_war"], extra["sight_range"] = 1, int(self.sight_range)
         torch.save({**extra, "data": self.learner.bucket.data, "ema": self.learner.ema, "exp_avg": self.learner.exp_avg,
                     "exp_avg_sq": self.learner.exp_avg_sq, "step": int(self.learner.step_count), "update": int(self.update_idx),
                     "total_updates": int(self.total_updates), "pool": list(self.opponent_pool), "gen": self.gen.get_state(),
@@ -553,6 +585,11 @@ class VecMAPPOTrainer:
         if bool(ck.get("mix_opponents", 0)) != self.mix_opponents:        # (no key: written with the flag off)
             raise ValueError(f"checkpoint was written with mix_opponents={bool(ck.get('mix_opponents', 0))}, this trainer has "
                              f"mix_opponents={self.mix_opponents}: the opponent draws of the two schemes do not continue one another")
+        ck_fog = (bool(ck.get("fog_of_war", 0)), int(ck.get("sight_range", self.sight_range)))      # (no key: written with the flag off)
+        if ck_fog[0] != self.fog_of_war or (self.fog_of_war and ck_fog[1] != self.sight_range):
+            raise ValueError(f"checkpoint was written with fog_of_war={ck_fog[0]}" + (f", sight_range={ck_fog[1]}" if ck_fog[0] else "") +
+                             f", this trainer has fog_of_war={self.fog_of_war}" + (f", sight_range={self.sight_range}" if self.fog_of_war else "") +
+                             ": a policy trained on fogged planes is fed fogged planes")
         if int(ck["total_updates"]) != int(self.total_updates):
             raise ValueError(f"checkpoint was written for a schedule of {ck['total_updates']} updates, this trainer has {self.total_updates}")
         self.learner.restore(ck)                                         # (weights, Adam moments, EMA and step count: the same keys)
@@ -568,10 +605,11 @@ class VecMAPPOTrainer:
 
 
 def evaluate_vs_bots(model, num_episodes=20, layout_file="bloxCapture", teams=("baselineTeam", "randomTeam"), length=300,
-                     device="cuda:0"):
+                     device="cuda:0", fog_of_war=False, sight_range=SIGHT_RANGE):
     """evaluate_vs_bots (pacman_mappo_resnet.py:293-337): a fresh env per episode against host CaptureAgent bots (red),
     the learner plays blue with argmax actions; returns (mean return, std, win rate), a win being final score < 0.
-    The reference cycles through its A*/approx-Q/baseline/MCTS teams; here through the team files this build ships."""
+    The reference cycles through its A*/approx-Q/baseline/MCTS teams; here through the team files this build ships.
+    fog_of_war: the learner's planes go through fog_obs (the host bots keep the full state the env gives them)."""
     from .gym_env import gymPacMan_parallel_env
     was_training = model.training
     model.eval()
@@ -584,6 +622,8 @@ def evaluate_vs_bots(model, num_episodes=20, layout_file="bloxCapture", teams=("
         ep_ret, done = 0.0, False
         while not done:
             lo = torch.stack([obs_dict[env.agents[i]].float() for i in learner_ids])
+            if fog_of_war:
+                lo = fog_obs(lo, sight_range)
             with torch.no_grad():
                 acts = model.get_deterministic_action(lo.to(next(model.parameters()).device)).cpu()
             obs_dict, rewards, dones, _ = env.step({env.agents[a]: int(acts[k]) for k, a in enumerate(learner_ids)})
@@ -599,17 +639,20 @@ def evaluate_vs_bots(model, num_episodes=20, layout_file="bloxCapture", teams=("
 
 @torch.no_grad()
 def evaluate_vectorized(model, layout="bloxCapture", n_envs=1024, opponent="baseline", length=300, device="cuda:0", seed=0,
-                        autocast=True, mask_illegal=False, side="blue"):
+                        autocast=True, mask_illegal=False, side="blue", fog_of_war=False, sight_range=SIGHT_RANGE):
     """evaluate_vs_bots (pacman_mappo_resnet.py:293-337) for n_envs episodes at once: the learner plays blue with argmax
     actions against the in-kernel randomTeam / baselineTeam / approxQTeam (opponent "random" / "baseline" / "approxq"), one episode per env (an env stops counting at its first done).
     Returns (mean episode return of the learner team as the reference sums it, std, win rate = share with final score < 0).
     mask_illegal: the argmax runs over the legal actions only (a policy trained with the trainer's mask_illegal).
     side: "blue" as above; "red": the learner plays red and the bots blue; "both": red in the first half of the envs, blue in
-    the rest (a policy trained with mix_opponents plays both colours).  A red learner's win is a final score > 0."""
+    the rest (a policy trained with mix_opponents plays both colours).  A red learner's win is a final score > 0.
+    fog_of_war: the policy sees an enemy only within sight_range of one of its two agents (pmx_emit_team_obs_mixed_fog); every
+    side, blue included, then runs the emission-based loop.  The in-kernel bots keep the full state."""
     if side not in ("blue", "red", "both"):
         raise ValueError(f"side must be blue, red or both, got {side!r}")
-    if side != "blue":
-        return _evaluate_sides(model, layout, n_envs, opponent, length, device, seed, autocast, mask_illegal, side)
+    if side != "blue" or fog_of_war:
+        return _evaluate_sides(model, layout, n_envs, opponent, length, device, seed, autocast, mask_illegal, side,
+                               int(sight_range) if fog_of_war else None)
     dev = torch.device(device)
     env = PmxVecEnv(layout, n_envs, length=length, auto_reset=True, obs_dtype="bfloat16" if autocast else "float32", device=dev,
                     seed=seed, bots=opponent in BOT_TEAMS)
@@ -646,9 +689,10 @@ def evaluate_vectorized(model, layout="bloxCapture", n_envs=1024, opponent="base
     return float(ret.mean()), float(ret.std()), float((final < 0).double().mean())
 
 
-def _evaluate_sides(model, layout, n_envs, opponent, length, device, seed, autocast, mask_illegal, side):
+def _evaluate_sides(model, layout, n_envs, opponent, length, device, seed, autocast, mask_illegal, side, sight_range=None):
     """evaluate_vectorized with the learner's colour chosen per env: observations from pmx_emit_team_obs_mixed (canonical, so the
-    policy sees a red game as it was trained to), actions and masks through the per-env frame helpers."""
+    policy sees a red game as it was trained to), actions and masks through the per-env frame helpers.  sight_range (an int): the
+    fog form of the emission."""
     dev = torch.device(device)
     env = PmxVecEnv(layout, n_envs, length=length, auto_reset=True, obs_dtype="bfloat16" if autocast else "float32", device=dev,
                     seed=seed, bots=opponent in BOT_TEAMS)
@@ -656,7 +700,7 @@ def _evaluate_sides(model, layout, n_envs, opponent, length, device, seed, autoc
     was_training = model.training
     model.eval()
     red = torch.zeros(n_envs, dtype=torch.uint8, device=dev)
-    red[:n_envs if side == "red" else n_envs // 2] = 1
+    red[:{"red": n_envs, "both": n_envs // 2, "blue": 0}[side]] = 1
     red_b = red.to(torch.bool)
     alive = torch.ones(n_envs, dtype=torch.bool, device=dev)
     ret = torch.zeros(n_envs, dtype=torch.float64, device=dev)
@@ -667,7 +711,7 @@ def _evaluate_sides(model, layout, n_envs, opponent, length, device, seed, autoc
     team_obs = torch.empty((n_envs, 2) + env.obs_shape, dtype=env.obs_torch_dtype, device=dev)
     ctx = torch.autocast(device_type=dev.type, dtype=torch.bfloat16) if autocast else _NullCtx()
     for _ in range(length + 1):
-        env.emit_team_obs_mixed(red, team_obs)
+        env.emit_team_obs_mixed(red, team_obs, **({} if sight_range is None else {"sight_range": sight_range}))
         lo = team_obs.view((-1,) + env.obs_shape)
         with ctx:
             if mask_illegal:

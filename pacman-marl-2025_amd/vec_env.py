@@ -188,22 +188,29 @@ class PmxVecEnv:
                       _lib.stream(self.device))
         return self.obs, self.legal
 
-    def emit_team_obs(self, team_red, team_obs, merged=None):
+    def emit_team_obs(self, team_red, team_obs, merged=None, sight_range=None):
         """The two observations of one team for the CURRENT tick (canonicalised for red) into team_obs [N,2,8,H,W] and, if
-        given, the merged critic input into merged [N,8,H,W] (pmx_emit_team_obs; pacman_mappo_resnet.py:215-229, :267-274)."""
+        given, the merged critic input into merged [N,8,H,W] (pmx_emit_team_obs; pacman_mappo_resnet.py:215-229, :267-274).
+        sight_range (an int): the contest's fog of war on the two learners' planes (pmx_emit_team_obs_fog; capture.py:268-292),
+        an enemy shows only within that Manhattan distance of one of the team's agents; merged stays full-information."""
         N = self.n_envs
         assert team_obs.shape == (N, 2) + self.obs_shape and team_obs.dtype == self.obs_torch_dtype and team_obs.is_contiguous()
         if merged is not None:
             assert merged.shape == (N,) + self.obs_shape and merged.dtype == self.obs_torch_dtype and merged.is_contiguous()
         with torch.cuda.device(self.device):
+            if sight_range is not None:
+                _lib.call("pmx_emit_team_obs_fog", self.handle, int(bool(team_red)), int(sight_range), team_obs.data_ptr(),
+                          merged.data_ptr() if merged is not None else None, _lib.stream(self.device))
+                return team_obs, merged
             _lib.call("pmx_emit_team_obs", self.handle, int(bool(team_red)), team_obs.data_ptr(),
                       merged.data_ptr() if merged is not None else None, _lib.stream(self.device))
         return team_obs, merged
 
-    def emit_team_obs_mixed(self, team_red, team_obs, merged=None, first=0, count=None):
+    def emit_team_obs_mixed(self, team_red, team_obs, merged=None, first=0, count=None, sight_range=None):
         """emit_team_obs with the learners' colour chosen per env (pmx_emit_team_obs_mixed): team_red uint8 [N], non-zero = that
         env's learners are red.  Writes rows for the envs first .. first + count - 1 (count None: up to the last env), row j for
-        env first + j, into team_obs [count,2,8,H,W] and, if given, merged [count,8,H,W]."""
+        env first + j, into team_obs [count,2,8,H,W] and, if given, merged [count,8,H,W].  sight_range as in emit_team_obs
+        (pmx_emit_team_obs_mixed_fog)."""
         N = self.n_envs
         first = int(first)
         count = N - first if count is None else int(count)
@@ -214,6 +221,10 @@ class PmxVecEnv:
         if count == 0:                                   # (an empty tensor has no address to pass)
             return team_obs, merged
         with torch.cuda.device(self.device):
+            if sight_range is not None:
+                _lib.call("pmx_emit_team_obs_mixed_fog", self.handle, team_red.data_ptr(), first, count, int(sight_range),
+                          team_obs.data_ptr(), merged.data_ptr() if merged is not None else None, _lib.stream(self.device))
+                return team_obs, merged
             _lib.call("pmx_emit_team_obs_mixed", self.handle, team_red.data_ptr(), first, count, team_obs.data_ptr(),
                       merged.data_ptr() if merged is not None else None, _lib.stream(self.device))
         return team_obs, merged

@@ -53,6 +53,9 @@ def parser():
                                                                  "both colours) instead of one opponent and one colour per rollout")
     ap.add_argument("--eval-side", default="blue", choices=["blue", "red", "both"], help="the colour the evaluated policy plays (both: red in the first half of "
                                                                                          "the envs); a policy trained with --mix-opponents plays both")
+    ap.add_argument("--fog-of-war", action="store_true", help="the contest's sight rule on every policy input: an enemy shows only within --sight-range of one of the "
+                                                              "team's two agents (the critic's merged input stays full); the evaluation runs under the same rule")
+    ap.add_argument("--sight-range", type=int, default=5, help="with --fog-of-war: Manhattan cells (the contest's SIGHT_RANGE is 5)")
     ap.add_argument("--graph", action="store_true", help="replay the optimizer step from a hipGraph (launch-bound minibatches, e.g. 512)")
     return ap
 
@@ -91,11 +94,12 @@ def main():
             with open(args.log, "a") as fh:
                 fh.write(line + "\n")
 
+    fog = {"fog_of_war": True, "sight_range": args.sight_range} if args.fog_of_war else {}
     tr = trainer.VecMAPPOTrainer(layout, args.envs, horizon=args.horizon, minibatch=args.minibatch, epochs=args.epochs, redraw_layouts=args.redraw,
                                  obs_dtype=args.obs, device=f"cuda:{local}", seed=args.seed, rank=rank, world_size=world,
                                  total_updates=args.total_updates, opponent=args.opponent, algorithm=args.algorithm, use_graph=args.graph, paired_minibatches=not args.unpaired, curriculum_scale=args.curriculum_scale,
                                  hard_bots=tuple(args.hard_bots.split(",")), mask_illegal=args.mask_illegal,
-                                 **({"mix_opponents": True} if args.mix_opponents else {}))
+                                 **({"mix_opponents": True} if args.mix_opponents else {}), **fog)
     for u in range(args.updates):
         torch.cuda.synchronize(); t0 = time.perf_counter()
         st = tr.train_update()
@@ -110,8 +114,8 @@ def main():
                                   clip_frac=f("clip_frac"), grad_norm=f("grad_norm"), steps=st["optimizer_steps"], **by_mode))
             if args.eval_every and u and u % args.eval_every == 0:
                 emit(dict(update=u, algorithm=args.algorithm,
-                          eval_vs_baseline=trainer.evaluate_vectorized(tr.model, eval_layout, 1024, "baseline", device=f"cuda:{local}", mask_illegal=args.mask_illegal, side=args.eval_side),
-                          eval_vs_random=trainer.evaluate_vectorized(tr.model, eval_layout, 1024, "random", device=f"cuda:{local}", mask_illegal=args.mask_illegal, side=args.eval_side)))
+                          eval_vs_baseline=trainer.evaluate_vectorized(tr.model, eval_layout, 1024, "baseline", device=f"cuda:{local}", mask_illegal=args.mask_illegal, side=args.eval_side, **fog),
+                          eval_vs_random=trainer.evaluate_vectorized(tr.model, eval_layout, 1024, "random", device=f"cuda:{local}", mask_illegal=args.mask_illegal, side=args.eval_side, **fog)))
     if rank == 0 and args.save:
         tr.save_ema(args.save)
     if world > 1:
