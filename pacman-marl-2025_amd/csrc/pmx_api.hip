@@ -147,7 +147,7 @@ hipEvent_t *prof_pair(pmx_env *env, bool expand)
     return p;
 }
 
-// walls_done: the rule launch of this pmx_step stored the vectors wholly inside plane 0 (split_walls)
+// walls_done: the rule launch of this pmx_step stored every block's wall vectors up to its wall_split_vec (split_walls)
 int launch_expand(pmx_env *env, void *obs, bool from_snapshots, int single_agent, hipStream_t st, bool walls_done = false)
 {
     PmxExpandParams x;

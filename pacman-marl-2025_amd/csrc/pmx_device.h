@@ -90,9 +90,22 @@ struct PmxExpandParams {
     int32_t single_agent;        // >= 0: obs is [N][8][H][W] for that agent only (pmx_step_agent)
     int32_t lay_H, lay_W;        // host-side copies of the common layout dimensions (launch sizing)
     int32_t reverse;             // 1: walk the blocks from the highest address down (alternate ticks, see pmx_launch_expand)
-    int32_t first_vec;           // pmx_expand_kernel<0, false, true>: first 16-byte vector of a block it stores.  0: the whole block; H*W*4/16:
-                                 // the vectors wholly inside plane 0 were stored by the rule launch (PmxTickParams::obs)
+    int32_t first_vec;           // pmx_expand_kernel<0, false, true>: number of 16-byte vectors wholly inside plane 0, H*W*4/16.  0: the
+                                 // kernel stores the whole block; otherwise the rule launch (PmxTickParams::obs) stored the block's
+                                 // first wall_split_vec(block, first_vec) vectors and the kernel starts behind them
 };
+
+// Where a float32 (env, agent) block is split between the wall writer (streaming stores) and the expansion (ordinary stores):
+// the largest s <= first_vec for which block + 16 s is a multiple of 128, or 0 if there is none.  first_vec = H*W*4/16 is the
+// number of vectors wholly inside plane 0; the vectors s .. first_vec - 1 hold walls only and the expansion stores them from its
+// stream table.  With the split on a 128-byte line of the ADDRESS every 1 KiB store instruction behind it covers 8 whole lines,
+// and no 64-byte granule is written half by a streaming and half by an ordinary store.  The writer and the reader of a block
+// both call this with the block's own address, so a buffer of any (16-byte) alignment is split consistently.
+__host__ __device__ inline int wall_split_vec(const void *block, int first_vec)
+{
+    const int s = first_vec - (int)(((uintptr_t)block / 16 + (uintptr_t)first_vec) & 7);
+    return s > 0 ? s : 0;
+}
 
 // pmx_emit_team_obs: the two observations of one team, canonicalised for a red team, + the merged critic input
 struct PmxEmitParams {

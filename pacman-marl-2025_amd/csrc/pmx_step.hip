@@ -968,9 +968,10 @@ __device__ __forceinline__ uint4 pack_obs(uint32_t bits)
 // ---------------------------------------------------------------------------------------------------------------
 // Wall writer of the rule launch (pmx_rule_kernel, blocks behind the rule blocks).  Plane 0 of every (env, emitted agent)
 // block is the layout's wall_stream expanded to float32 (the split is used for float32 planes only, see pmx_step).  One wave
-// per block walks the (env, agent) blocks grid-stride and stores the 16-byte vectors that lie WHOLLY inside plane 0:
-// first_vec = H*W*4 / 16, rounded down.  The
-// vector that plane 0 shares with plane 1, and everything behind it, belongs to pmx_expand_kernel (PmxExpandParams::first_vec).
+// per block walks the (env, agent) blocks grid-stride and stores the block's first wall_split_vec(block, first_vec) vectors
+// (pmx_device.h): of the first_vec = H*W*4 / 16 vectors that lie WHOLLY inside plane 0, those in front of the last 128-byte
+// line boundary of the block's address.  The wall-only vectors behind that boundary, the
+// vector that plane 0 shares with plane 1, and everything behind it, belong to pmx_expand_kernel (PmxExpandParams::first_vec).
 // With one layout the vectors are computed once per wave and only stored again; with per-env layouts they are recomputed
 // from the env's layout record.  A lane holds vector lane + 64 j; the largest board (32 x 32) needs j < 4.
 // ---------------------------------------------------------------------------------------------------------------
@@ -996,9 +997,10 @@ __device__ __forceinline__ void write_walls(const PmxTickParams &p)
     for (long q = (long)blockIdx.x - p.rule_blocks; q < total; q += stride) {
         if (p.layout_idx) pack(p.lay + p.layout_idx[q / p.n_emit]);
         uint4 *out = reinterpret_cast<uint4 *>(p.obs) + (size_t)q * n_vec;
+        const int split = wall_split_vec(out, first_vec);
 #pragma unroll
         for (int j = 0; j < MAXJ; ++j)
-            if (lane + 64 * j < first_vec) {   // streaming stores (one dwordx4 nt): see the measurements at pmx_launch_rule
+            if (lane + 64 * j < split) {   // streaming stores (one dwordx4 nt): see the measurements at pmx_launch_rule
                 uint4 *o = &out[lane + 64 * j];
                 __builtin_nontemporal_store(v[j].x, &o->x); __builtin_nontemporal_store(v[j].y, &o->y);
                 __builtin_nontemporal_store(v[j].z, &o->z); __builtin_nontemporal_store(v[j].w, &o->w);
@@ -1058,7 +1060,9 @@ __device__ __forceinline__ void stream_or_row(uint32_t *T, uint32_t off, uint32_
 // 8-bit look-ups of 8 bytes) instead of being computed: with the observation buffer partly resident in the Infinity Cache the
 // float32 kernel had become instruction bound (~1.8 T elements/s whatever the footprint), and the expansion arithmetic was most
 // of its ~35 instructions per 16 bytes.
-// BEHIND (float32, ordinary stores): the store loop starts at p.first_vec, behind the wall vectors the rule launch stored.  A
+// BEHIND (float32, ordinary stores): the store loop starts at wall_split_vec(block, H*W*4/16), behind the wall vectors the rule
+// launch stored, i.e. on a 128-byte line of the block's address; the wall-only vectors from there to the end of plane 0 come
+// out of the stream table like every other vector.  (PmxExpandParams::first_vec > 0 only selects this instantiation.)  A
 // template flag and not a test of first_vec, so that the full-plane instantiations are the code they were without the split.
 template <int DT, bool NT, bool BEHIND = false>
 __global__ __launch_bounds__(PMX_BLOCK) void pmx_expand_kernel(PmxExpandParams p)
@@ -1139,7 +1143,7 @@ __global__ __launch_bounds__(PMX_BLOCK) void pmx_expand_kernel(PmxExpandParams p
 
     const int n_vec = 8 * HW / VEC;
     uint4 *out = reinterpret_cast<uint4 *>(p.obs) + (size_t)q * n_vec;
-    for (int k = (BEHIND ? p.first_vec : 0) + lane; k < n_vec; k += 64) {
+    for (int k = (BEHIND ? wall_split_vec(out, HW * (int)sizeof(float) / 16) : 0) + lane; k < n_vec; k += 64) {
         const uint32_t e0 = (uint32_t)k * VEC;
         const uint32_t bits = T[e0 >> 5] >> (e0 & 31);
         uint4 v;
@@ -1168,7 +1172,8 @@ __global__ __launch_bounds__(PMX_BLOCK) void pmx_expand_kernel(PmxExpandParams p
 //   phase A0 wave 0 loads the state of its 64 envs and runs sub-step 0 with pmx_rule_kernel's device functions and lane mapping;
 //            where that kernel stores a snapshot to global memory, this one copies the H + 10 words into the LDS area
 //            snap[4][..][64].  Waves 1-15 store the wall vectors of the workgroup's 256 (env, agent) blocks with streaming
-//            stores, as write_walls does.  Barrier.
+//            stores, as write_walls does: those in front of the block's wall_split_vec, a 128-byte line of its address, so
+//            that every store instruction of the expansion behind it covers 8 whole lines.  Barrier.
 //   phase A1 wave 0 runs sub-steps 1-3 and tick_finish (slots 1, 2 and, with the H + 13 words of the final state, 3); waves 1-15
 //            expand the 64 agent-0 blocks from slot 0, which is complete: HBM has plane bytes to store while the rule wave runs.
 //            An env that finishes shows the fresh game to all four agents, so its agent-0 block is stale: wave 0 writes the fresh
@@ -1216,7 +1221,7 @@ __device__ __forceinline__ void snapshot_to_lds(const Env &e, const Ctx &c, uint
 }
 
 // One wave expands the planes behind the wall vectors of one (env, agent) block: S = the env's column of the snapshot slot,
-// T = the wave's stream table, out = the block.  Ordinary stores from first_vec on.
+// T = the wave's stream table, out = the block.  Ordinary stores from wall_split_vec(out, first_vec) on: whole 128-byte lines.
 __device__ __forceinline__ void fused_expand_block(const PmxTickParams &p, const uint32_t *S, int agent, uint32_t *T, const uint32_t *lut,
                                                    uint32_t wallw, uint4 *out, int lane)
 {
@@ -1255,7 +1260,7 @@ __device__ __forceinline__ void fused_expand_block(const PmxTickParams &p, const
     __builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "wavefront");
     __builtin_amdgcn_wave_barrier();
 
-    for (int k = first_vec + lane; k < n_vec; k += 64) {
+    for (int k = wall_split_vec(out, first_vec) + lane; k < n_vec; k += 64) {
         const uint32_t e0 = (uint32_t)k * VEC;
         const uint32_t bits = T[e0 >> 5] >> (e0 & 31);
         uint4 v = *reinterpret_cast<const uint4 *>(&lut[(bits & 15u) * 4]);
@@ -1319,9 +1324,10 @@ __global__ __launch_bounds__(PMX_FUSED_WAVES * 64) void pmx_tick_fused_kernel(Pm
         }
         for (int b = wave - 1; b < NB; b += PMX_FUSED_WAVES - 1) {
             uint4 *out = obs + (size_t)(reverse ? NB - 1 - b : b) * n_vec;
+            const int split = wall_split_vec(out, first_vec);
 #pragma unroll
             for (int j = 0; j < MAXJ; ++j)
-                if (lane + 64 * j < first_vec) {   // streaming stores, as in write_walls
+                if (lane + 64 * j < split) {   // streaming stores, as in write_walls
                     uint4 *o = &out[lane + 64 * j];
                     __builtin_nontemporal_store(v[j].x, &o->x); __builtin_nontemporal_store(v[j].y, &o->y);
                     __builtin_nontemporal_store(v[j].z, &o->z); __builtin_nontemporal_store(v[j].w, &o->w);
