@@ -224,6 +224,57 @@ int pmx_emit_team_obs_fog(pmx_env *env, int team_red, int32_t sight_range, void 
 int pmx_emit_team_obs_mixed_fog(pmx_env *env, const uint8_t *team_red_dev, int32_t first, int32_t count, int32_t sight_range,
                                 void *team_obs_dev, void *merged_dev, void *stream);
 
+/* ---- Belief sets: what a team can know about the enemies the sight rule hides ------------------------------------------------
+ * Besides the sight rule the contest gives a team a noisy distance to every agent at every turn (capture.py:67-78 SONAR_NOISE_RANGE
+ * = 13, :210-224 noisyDistance, :268-275 makeObservation).  The tracker below turns those readings, the sight rule and the rules
+ * of motion into, per learner slot and hidden enemy, the SET of cells the enemy can be on -- possibilistic, not weighted: a cell is
+ * in or out -- and the belief emission writes the sets into plane 5, the plane that holds the enemies, with values 0 or 1.  All of
+ * it is integer and exact.
+ *
+ * Team and enemies.  For a team of colour `red`: first = red ? 0 : 1, second = first + 2.  Enemy k (0 or 1) is agent
+ * e_k = (1 - first) + 2 k.  Slot j (0 or 1) belongs to learner a_j = first + 2 j and is read from the snapshot that learner's
+ * planes are encoded from, the snapshots pmx_emit_team_obs reads; P[i] is agent i's cell in it.
+ *
+ * Belief buffer (caller-owned): uint32_t belief[rows][2 slots][2 enemies][32].  Bit x of word y = the enemy can be on cell (x, y),
+ * raw coordinates (not flipped); words y >= H are 0.  512 contiguous bytes per env.
+ *
+ * Sonar reading of learner a_j for enemy e_k: r = manhattan(P[a_j], P[e_k]) + n, n = (int)(((uint64_t)h * 13) >> 32) - 6 in
+ * -6 .. 6, h = h(PMX_SALT_SONAR) the counter-based generator documented at PMX_ACTION_APPROXQ_OFFENSE with `agent` =
+ * 4 a_j + e_k and `ticks` = the env's ticks word at the time of the call (the value pmx_get_state returns).  Distribution-
+ * equivalent to noisyDistance; r may be negative, as in the reference.
+ *
+ * pmx_belief_update, once after each pmx_step, for the envs first .. first + count - 1 (belief / sonar row env - first; colour
+ * team_red_dev[env] != 0, or the uniform team_red when team_red_dev is NULL).  For slot j = 0, then j = 1, and both enemies k:
+ *   1. starting set  S = the previous call's slot-1 set when j == 0, the slot-0 set just computed when j == 1;
+ *   2. motion        if e_k == (a_j + 3) % 4 -- the enemy whose sub-step lies between the two snapshots --
+ *                    S = (S | S << 1 | S >> 1 | row above | row below) & open cells  (Stop is a move; an extra dilation is never unsound);
+ *   3. respawn       S |= bit(start cell of e_k): every death returns an agent to its start, whoever's move caused it, so the
+ *                    rule is sound for every sight_range;
+ *   4. sight         seen = min over m in {first, second} of manhattan(P[e_k], P[m]) <= sight_range (the fog kernels' rule).
+ *                    Seen: S = bit(P[e_k]).  Otherwise every cell within sight_range of P[first] or P[second] leaves S, and so
+ *                    does every cell c with |manhattan(P[a_j], c) - r| > 6;
+ *   5. store         belief[row][j][k] = S; sonar_dev[row][j][k] = r (int8 [count][2][2], may be NULL).
+ * reset_dev (uint8 [n_envs], may be NULL; pass `done` of the last step under auto_reset): where reset_dev[env] != 0 the steps are
+ * skipped, both slots of both enemies become the enemy's start cell in the env's CURRENT layout (redraw_layouts) and the four
+ * readings are 0.  PMX_ERR_INVALID for a range outside the handle's envs or a sight_range outside 0 .. PMX_SIGHT_RANGE_MAX;
+ * count == 0 launches nothing.  An open profile (pmx_profile_begin) records the launch with the rule launches.
+ *
+ * pmx_belief_init takes no colour, so a buffer can be set up before the learners' colour is drawn.  kind 0 (valid after pmx_reset):
+ * the sets of enemy k, in both slots, hold the start cells of agents 2 k and 2 k + 1 -- enemy k of a blue and of a red team -- which
+ * is sound for either colour; the updates' sight and sonar rules narrow it.  kind 1 (valid after pmx_set_state, or
+ * when the learners' colour changes): every set holds every open cell.  Any other kind is PMX_ERR_INVALID. */
+#define PMX_SALT_SONAR 0x534F4E41u
+int pmx_belief_update(pmx_env *env, int team_red, const uint8_t *team_red_dev, int32_t first, int32_t count, int32_t sight_range,
+                      const uint8_t *reset_dev, uint32_t *belief_dev, int8_t *sonar_dev, void *stream);
+int pmx_belief_init(pmx_env *env, int32_t first, int32_t count, int32_t kind, uint32_t *belief_dev, void *stream);
+/* pmx_emit_team_obs / pmx_emit_team_obs_mixed with one difference: learner slot j's plane 5 is belief[row][j][0] | belief[row][j][1]
+ * (row = the output row), x-flipped for red like every other plane, in place of the enemies' own bits.  A seen enemy is a one-cell
+ * set, so no sight test runs here.  Every other plane and the whole merged slot -- the full-information critic input -- are byte
+ * for byte those of the plain call.  The buffer is read, never written. */
+int pmx_emit_team_obs_belief(pmx_env *env, int team_red, const uint32_t *belief_dev, void *team_obs_dev, void *merged_dev, void *stream);
+int pmx_emit_team_obs_mixed_belief(pmx_env *env, const uint8_t *team_red_dev, int32_t first, int32_t count, const uint32_t *belief_dev,
+                                   void *team_obs_dev, void *merged_dev, void *stream);
+
 /* The layout each env is currently on (host output [n_envs]; all zeros for a single-layout handle).  Synchronises the stream. */
 int pmx_get_layout_index(pmx_env *env, int32_t *index_out, void *stream);
 

@@ -14,6 +14,9 @@ ACTION_RANDOM_LEGAL = -2
 ACTION_BASELINE_OFFENSE, ACTION_BASELINE_DEFENSE = -3, -4
 ACTION_APPROXQ_OFFENSE, ACTION_APPROXQ_DEFENSE = -5, -6
 BOT_FLAG_HOME, BOT_FLAG_EXPLORED = 1, 2          # pmx_bot_query flags
+SIGHT_RANGE_MAX = 64                             # PMX_SIGHT_RANGE_MAX
+SALT_SONAR = 0x534F4E41                          # PMX_SALT_SONAR: the sonar's noise draw (pmx_belief_update)
+BELIEF_START_CELLS, BELIEF_OPEN_CELLS = 0, 1     # pmx_belief_init kinds
 COLSUM_BLOCKS = 512
 LN32_PARTIAL_ROWS = 2048
 ACTOR_PACK_BYTES = 297984
@@ -81,6 +84,10 @@ PROTOTYPES = [
     ("pmx_emit_team_obs_mixed", C.c_int, [_VP, _VP, _I32, _I32, _VP, _VP, _VP]),
     ("pmx_emit_team_obs_fog", C.c_int, [_VP, C.c_int, _I32, _VP, _VP, _VP]),
     ("pmx_emit_team_obs_mixed_fog", C.c_int, [_VP, _VP, _I32, _I32, _I32, _VP, _VP, _VP]),
+    ("pmx_belief_update", C.c_int, [_VP, C.c_int, _VP, _I32, _I32, _I32, _VP, _VP, _VP, _VP]),
+    ("pmx_belief_init", C.c_int, [_VP, _I32, _I32, _I32, _VP, _VP]),
+    ("pmx_emit_team_obs_belief", C.c_int, [_VP, C.c_int, _VP, _VP, _VP, _VP]),
+    ("pmx_emit_team_obs_mixed_belief", C.c_int, [_VP, _VP, _I32, _I32, _VP, _VP, _VP, _VP]),
     ("pmx_get_layout_index", C.c_int, [_VP, C.POINTER(_I32), _VP]),
     ("pmx_get_state", C.c_int, [_VP, _I32, _I32, C.POINTER(State), _VP]),
     ("pmx_set_state", C.c_int, [_VP, _I32, _I32, C.POINTER(State), _VP]),

@@ -19,6 +19,8 @@ extern "C" hipError_t pmx_launch_bot_query(const PmxTickParams *p, int H, int ag
 extern "C" hipError_t pmx_launch_emit_team(const PmxEmitParams *p, int dtype, hipStream_t st, hipEvent_t ev0, hipEvent_t ev1);
 extern "C" hipError_t pmx_launch_emit_team_mixed(const PmxEmitParams *p, int dtype, hipStream_t st, hipEvent_t ev0, hipEvent_t ev1);
 extern "C" hipError_t pmx_launch_emit_team_fog(const PmxEmitParams *p, int mixed, int dtype, hipStream_t st, hipEvent_t ev0, hipEvent_t ev1);
+extern "C" hipError_t pmx_launch_emit_team_belief(const PmxEmitParams *p, int mixed, int dtype, hipStream_t st, hipEvent_t ev0, hipEvent_t ev1);
+extern "C" hipError_t pmx_launch_belief(const PmxBeliefParams *p, int init, hipStream_t st, hipEvent_t ev0, hipEvent_t ev1);
 extern "C" hipError_t pmx_launch_expand(const PmxExpandParams *p, int dtype, hipStream_t st, hipEvent_t ev0, hipEvent_t ev1);
 extern "C" hipError_t pmx_launch_maze(const PmxLayoutDev *lay_dev, const int16_t *cell_index_dev, int n_cells,
                                       const int8_t *cells_dev, uint8_t *dist_dev, hipStream_t st);
@@ -525,6 +527,108 @@ int pmx_emit_team_obs_mixed_fog(pmx_env *env, const uint8_t *team_red_dev, int32
     x.sight = sight_range;
     hipEvent_t *ev = prof_pair(env, true);
     HIP_TRY(pmx_launch_emit_team_fog(&x, 1, env->cfg.obs_dtype, as_stream(stream), ev ? ev[0] : nullptr, ev ? ev[1] : nullptr));
+    return PMX_OK;
+}
+
+// The belief pair: the plain pair's parameter block plus the tracker's buffer, which the kernel only reads.
+int pmx_emit_team_obs_belief(pmx_env *env, int team_red, const uint32_t *belief_dev, void *team_obs_dev, void *merged_dev, void *stream)
+{
+    if (!env || !team_obs_dev || !belief_dev) return fail(PMX_ERR_INVALID, "pmx_emit_team_obs_belief: null argument");
+    if (env->open_agent != 0) return fail(PMX_ERR_INVALID, "pmx_emit_team_obs_belief: a tick opened with pmx_step_agent is unfinished");
+    PmxEmitParams x;
+    std::memset(&x, 0, sizeof(x));
+    const size_t snap_sz = (size_t)PMX_SNAP_WORDS(env->lay.H) * env->cfg.n_envs;
+    for (int a = 0; a < 4; ++a) x.snap[a] = (env->snaps_valid && a < 3) ? env->snap_dev + a * snap_sz : env->state_dev;
+    x.lay = env->lay_dev;
+    x.layout_idx = env->layout_idx_dev;
+    x.team_obs = team_obs_dev;
+    x.merged = merged_dev;
+    x.N = env->cfg.n_envs;
+    x.red = team_red ? 1 : 0;
+    x.lay_H = env->lay.H, x.lay_W = env->lay.W;
+    x.belief = belief_dev;
+    hipEvent_t *ev = prof_pair(env, true);           // recorded with the expansion launches, as pmx_emit_team_obs is
+    HIP_TRY(pmx_launch_emit_team_belief(&x, 0, env->cfg.obs_dtype, as_stream(stream), ev ? ev[0] : nullptr, ev ? ev[1] : nullptr));
+    return PMX_OK;
+}
+
+int pmx_emit_team_obs_mixed_belief(pmx_env *env, const uint8_t *team_red_dev, int32_t first, int32_t count, const uint32_t *belief_dev,
+                                   void *team_obs_dev, void *merged_dev, void *stream)
+{
+    if (!env || !team_red_dev || !team_obs_dev || !belief_dev) return fail(PMX_ERR_INVALID, "pmx_emit_team_obs_mixed_belief: null argument");
+    if (first < 0 || count < 0 || (int64_t)first + count > env->cfg.n_envs)
+        return fail(PMX_ERR_INVALID, "pmx_emit_team_obs_mixed_belief: envs %d .. %lld of %d", first, (long long)first + count - 1, env->cfg.n_envs);
+    if (env->open_agent != 0) return fail(PMX_ERR_INVALID, "pmx_emit_team_obs_mixed_belief: a tick opened with pmx_step_agent is unfinished");
+    if (count == 0) return PMX_OK;
+    PmxEmitParams x;
+    std::memset(&x, 0, sizeof(x));
+    const size_t snap_sz = (size_t)PMX_SNAP_WORDS(env->lay.H) * env->cfg.n_envs;
+    for (int a = 0; a < 4; ++a) x.snap[a] = (env->snaps_valid && a < 3) ? env->snap_dev + a * snap_sz : env->state_dev;
+    x.lay = env->lay_dev;
+    x.layout_idx = env->layout_idx_dev;
+    x.team_obs = team_obs_dev;
+    x.merged = merged_dev;
+    x.N = env->cfg.n_envs;
+    x.lay_H = env->lay.H, x.lay_W = env->lay.W;
+    x.team_red = team_red_dev;
+    x.first = first, x.count = count;
+    x.belief = belief_dev;
+    hipEvent_t *ev = prof_pair(env, true);
+    HIP_TRY(pmx_launch_emit_team_belief(&x, 1, env->cfg.obs_dtype, as_stream(stream), ev ? ev[0] : nullptr, ev ? ev[1] : nullptr));
+    return PMX_OK;
+}
+
+namespace {
+// what pmx_belief_update and pmx_belief_init share: the range check and the parameter block
+int fill_belief_params(pmx_env *env, const char *who, int32_t first, int32_t count, uint32_t *belief_dev, PmxBeliefParams &b)
+{
+    if (!env || !belief_dev) return fail(PMX_ERR_INVALID, "%s: null argument", who);
+    if (first < 0 || count < 0 || (int64_t)first + count > env->cfg.n_envs)
+        return fail(PMX_ERR_INVALID, "%s: envs %d .. %lld of %d", who, first, (long long)first + count - 1, env->cfg.n_envs);
+    if (env->open_agent != 0) return fail(PMX_ERR_INVALID, "%s: a tick opened with pmx_step_agent is unfinished", who);
+    std::memset(&b, 0, sizeof(b));
+    const size_t snap_sz = (size_t)PMX_SNAP_WORDS(env->lay.H) * env->cfg.n_envs;
+    for (int a = 0; a < 4; ++a) b.snap[a] = (env->snaps_valid && a < 3) ? env->snap_dev + a * snap_sz : env->state_dev;
+    b.state = env->state_dev;
+    b.lay = env->lay_dev;
+    b.layout_idx = env->layout_idx_dev;
+    b.belief = belief_dev;
+    b.N = env->cfg.n_envs;
+    b.first = first, b.count = count;
+    b.lay_H = env->lay.H, b.lay_W = env->lay.W;
+    b.seed = env->cfg.seed;
+    return PMX_OK;
+}
+}  // namespace
+
+int pmx_belief_update(pmx_env *env, int team_red, const uint8_t *team_red_dev, int32_t first, int32_t count, int32_t sight_range,
+                      const uint8_t *reset_dev, uint32_t *belief_dev, int8_t *sonar_dev, void *stream)
+{
+    PmxBeliefParams b;
+    const int rc = fill_belief_params(env, "pmx_belief_update", first, count, belief_dev, b);
+    if (rc != PMX_OK) return rc;
+    if (sight_range < 0 || sight_range > PMX_SIGHT_RANGE_MAX)
+        return fail(PMX_ERR_INVALID, "pmx_belief_update: sight_range %d outside 0 .. %d", sight_range, PMX_SIGHT_RANGE_MAX);
+    if (count == 0) return PMX_OK;
+    b.red = team_red ? 1 : 0;
+    b.team_red = team_red_dev;
+    b.sight = sight_range;
+    b.reset = reset_dev;
+    b.sonar = sonar_dev;
+    hipEvent_t *ev = prof_pair(env, false);          // an open profile records the tracker with the rule launches
+    HIP_TRY(pmx_launch_belief(&b, 0, as_stream(stream), ev ? ev[0] : nullptr, ev ? ev[1] : nullptr));
+    return PMX_OK;
+}
+
+int pmx_belief_init(pmx_env *env, int32_t first, int32_t count, int32_t kind, uint32_t *belief_dev, void *stream)
+{
+    PmxBeliefParams b;
+    const int rc = fill_belief_params(env, "pmx_belief_init", first, count, belief_dev, b);
+    if (rc != PMX_OK) return rc;
+    if (kind != 0 && kind != 1) return fail(PMX_ERR_INVALID, "pmx_belief_init: kind %d is neither 0 (start cells) nor 1 (open cells)", kind);
+    if (count == 0) return PMX_OK;
+    b.kind = kind;
+    HIP_TRY(pmx_launch_belief(&b, 1, as_stream(stream), nullptr, nullptr));
     return PMX_OK;
 }
 

@@ -123,6 +123,25 @@ struct PmxEmitParams {
     // pmx_emit_team_obs_fog / _mixed_fog only (pmx_emit_team_kernel<DT, MIXED, true>; zero and unread otherwise): an enemy shows
     // in a learner's plane 5 only within this Manhattan distance of one of the two team agents (capture.py:285-291)
     int32_t sight;
+    // pmx_emit_team_obs_belief / _mixed_belief only (pmx_emit_team_kernel<DT, MIXED, false, true>; NULL and unread otherwise): the
+    // tracker's sets, [rows][2 slots][2 enemies][32] row words; learner slot j's plane 5 is the OR of its two sets
+    const uint32_t *belief;
+};
+
+// pmx_belief_update / pmx_belief_init: the possibilistic tracker of the hidden enemies (include/pmx.h, "Belief sets")
+struct PmxBeliefParams {
+    const uint32_t *snap[4];     // per agent: the snapshot its planes are encoded from (as in PmxEmitParams)
+    const uint32_t *state;       // the env's state words: the tick counter keys the sonar draw
+    const PmxLayoutDev *lay;
+    const int32_t *layout_idx;
+    const uint8_t *team_red;     // [N] colour per env, or NULL: `red` for all
+    const uint8_t *reset;        // [N] non-zero = back to the start cells, or NULL
+    uint32_t *belief;            // [count][2][2][32]
+    int8_t *sonar;               // [count][2][2] or NULL
+    int32_t N, red, first, count, sight;
+    int32_t lay_H, lay_W;
+    uint32_t seed;
+    int32_t kind;                // pmx_belief_init only: 0 = start cells, 1 = every open cell
 };
 
 // Host-side launch tuning, changed through pmx_set_tuning: -1 = the built-in choice.

@@ -133,7 +133,7 @@ class VecMAPPOTrainer:
                  device="cuda:0", seed=0, rank=0, world_size=1, process_group=None, total_updates=2000, length=300,
                  use_autocast=True, opponent="random", use_graph=False, algorithm="mappo", paired_minibatches=True, curriculum_scale=1.0,
                  env=None, redraw_layouts=False, force_collectives=False, hard_bots=("baseline",), mask_illegal=False,
-                 mix_opponents=False, fog_of_war=False, sight_range=SIGHT_RANGE):
+                 mix_opponents=False, fog_of_war=False, sight_range=SIGHT_RANGE, belief=False):
         self.device = torch.device(device)
         # fog_of_war: every policy input of the rollout (the learners', the self / pool opponent networks', the bootstrap
         # observation) comes from the fog entry points -- an enemy shows only within sight_range of one of the team's agents, the
@@ -144,6 +144,15 @@ class VecMAPPOTrainer:
         if self.fog_of_war and not 0 <= self.sight_range <= 64:
             raise ValueError(f"sight_range must be 0 .. 64, got {sight_range!r}")
         self._fog = {"sight_range": self.sight_range} if self.fog_of_war else {}
+        # belief (needs fog_of_war): the env tracks, per learner slot and hidden enemy, the set of cells the enemy can be on
+        # (pmx_belief_update: motion, respawn, the sight rule and the noisy sonar distances of the contest, capture.py:210-224) and
+        # every policy input shows the sets in plane 5 (pmx_emit_team_obs_belief; a seen enemy is a one-cell set, so the sight
+        # rule needs no pass of its own there).  One buffer for the learners; a second one, updated with the colours inverted,
+        # when the opponent can be a network, which then sees what a learner of its colour sees.  The buffers are not part of
+        # a checkpoint.  Off: no keyword is passed and no tracker call is made
+        self.belief = bool(belief)
+        if self.belief and not self.fog_of_war:
+            raise ValueError("belief=True needs fog_of_war=True: without the sight rule no enemy is hidden and there is nothing to track")
         self.rank, self.world_size = rank, world_size
         # hard_bots: the in-kernel teams the curriculum draws its "hard" opponent from (the reference's hard teams are
         # baselineTeam, AstarTeam and approxQTeam, pacman_mappo_resnet.py:40-47); the default keeps the draws of earlier versions
@@ -227,6 +236,9 @@ class VecMAPPOTrainer:
         self.start_words = torch.tensor([int(starts[i, 0]) | (int(starts[i, 1]) << 8) for i in range(4)],
                                         dtype=torch.int32, device=dev)
         self.env.reset()
+        if self.belief:
+            self._belief = self._new_belief()
+            self._belief_opp = self._new_belief() if opponent in ("self", "pool", "curriculum") else None
         self._acts = None                                          # persistent per-rollout tensors, allocated on first use
         self.prev_agent = self.start_words[None].expand(N, 4).clone()
         self.update_idx = 0
@@ -275,6 +287,29 @@ class VecMAPPOTrainer:
                 self.sample_counter += 1
             v = model.value(self._net_in(merged)).float() if want_value else None
         return a.view(-1, 2), lp.view(-1, 2), v
+
+    # ---- belief buffers: [tensor, colour] with colour a host array [N]: 0 / 1 = the row tracks the enemies of a blue / red team,
+    # -1 = start cells of the reset the constructor made, -2 = every open cell (both sound for either colour), 2 = the row missed
+    # the last rollout's updates and is re-initialised before it is used again
+    def _new_belief(self):
+        b = self.env.new_belief()
+        self.env.belief_init(b, 0)
+        return [b, np.full(self.N, -1, np.int8)]
+
+    def _belief_for(self, buf, want, n=None):
+        """The buffer's tensor for a rollout whose rows 0 .. n - 1 (None: all) track the enemies of a team of colour want[row]:
+        rows that tracked the other colour (or none, last rollout) are re-initialised to every open cell, run by run."""
+        n = self.N if n is None else n
+        t, colour = buf
+        want = np.broadcast_to(np.asarray(want, np.int8), (self.N,))[:n]
+        bad = np.nonzero((colour[:n] >= 0) & (colour[:n] != want))[0]
+        if len(bad):
+            cuts = np.nonzero(np.diff(bad) != 1)[0] + 1
+            for run in np.split(bad, cuts):
+                self.env.belief_init(t[int(run[0]):int(run[-1]) + 1], 1, first=int(run[0]), count=len(run))
+        colour[:n] = want
+        colour[n:] = np.where(colour[n:] == -2, -2, 2)
+        return t[:n]
 
     def _hard_bot(self):
         """The hard in-kernel team of this rollout: one extra draw, made only when there is a choice."""
@@ -335,8 +370,16 @@ class VecMAPPOTrainer:
         masks = self.mask_illegal
         own, other = (slice(0, 4, 2), slice(1, 4, 2)) if red else (slice(1, 4, 2), slice(0, 4, 2))   # learner_ids / opp_ids of env.legal
         lg = None
+        kw = okw = self._fog                                         # keywords of the learners' / the opponent network's emissions
+        if self.belief:
+            net = mode in ("self", "pool")
+            bel = self._belief_for(self._belief, int(red))
+            kw = {"belief": bel}
+            if self._belief_opp is not None:
+                obel = self._belief_for(self._belief_opp, int(not red), None if net else 0)
+                okw = {"belief": obel}
         for t in range(T):
-            env.emit_team_obs(red, self.obs_buf[t], self.merged_buf[t] if mappo_alg else None, **self._fog)
+            env.emit_team_obs(red, self.obs_buf[t], self.merged_buf[t] if mappo_alg else None, **kw)
             if masks:
                 # env.legal: the masks of the state this tick acts on (written by the reset, the last step or its auto-reset)
                 self.legal_buf[t].copy_(mappo.canonicalize_legal(env.legal[:, own], red))
@@ -351,12 +394,16 @@ class VecMAPPOTrainer:
             self.logp_buf[t].copy_(lp)
             acts[:, learner_ids] = mappo.canonicalize_action(a, red).to(torch.int8)
             if mode in ("self", "pool"):
-                env.emit_team_obs(not red, self._opp_obs, None, **self._fog)      # the opponent is red when the learner is blue
+                env.emit_team_obs(not red, self._opp_obs, None, **okw)            # the opponent is red when the learner is blue
                 # (under masks the opponent, a copy of a policy trained under masks, samples the same way under its own ids' masks)
                 oa, _, _ = self._forward_policy(self.opponent_model, self._opp_obs, None, False,
                                                 mappo.canonicalize_legal(env.legal[:, other], not red) if masks else None)
                 acts[:, opp_ids] = mappo.canonicalize_action(oa, not red).to(torch.int8)
             _, rew, done, info = env.step(acts, want_obs=False)
+            if self.belief:
+                env.belief_update(red, bel, self.sight_range, reset=done)
+                if net:
+                    env.belief_update(not red, obel, self.sight_range, reset=done)
             cur_agent = info["agent"]
             shp = shaping_from_agent_words(self.prev_agent[:, learner_ids], cur_agent[:, learner_ids])   # [N,2] f64
             team_reward = rew[:, team] + rew[:, team]                # sum over the two learners' (identical) rewards
@@ -369,7 +416,7 @@ class VecMAPPOTrainer:
             sc = info["score"]
             n_win += (d & ((sc > 0) if red else (sc < 0))).sum()
         # bootstrap value of the state after the last tick (:541-546)
-        env.emit_team_obs(red, self._boot_obs, self._boot_merged if mappo_alg else None, **self._fog)
+        env.emit_team_obs(red, self._boot_obs, self._boot_merged if mappo_alg else None, **kw)
         ctx = torch.autocast(device_type=self.device.type, dtype=self.autocast_dtype) if self.autocast_dtype else _NullCtx()
         with torch.no_grad(), ctx:
             if mappo_alg:
@@ -419,8 +466,15 @@ class VecMAPPOTrainer:
         mappo_alg = self.algorithm == "mappo"
         masks = self.mask_illegal
         lg = None
+        kw = okw = self._fog                                         # keywords of the learners' / the opponent networks' emissions
+        if self.belief:
+            bel = self._belief_for(self._belief, red_host)
+            kw = {"belief": bel}
+            if self._belief_opp is not None:
+                obel = self._belief_for(self._belief_opp, 1 - red_host, n_net)
+                okw = {"belief": obel}
         for t in range(T):
-            env.emit_team_obs_mixed(red_u8, self.obs_buf[t], self.merged_buf[t] if mappo_alg else None, **self._fog)
+            env.emit_team_obs_mixed(red_u8, self.obs_buf[t], self.merged_buf[t] if mappo_alg else None, **kw)
             if masks:
                 self.legal_buf[t].copy_(mappo.canonicalize_legal(mappo.team_columns(env.legal, red_u8), red_u8))
                 lg = self.legal_buf[t]
@@ -434,13 +488,17 @@ class VecMAPPOTrainer:
             self.logp_buf[t].copy_(lp)
             mappo.set_team_columns(acts, red_u8, mappo.canonicalize_action(a, red_u8))
             if n_net:
-                env.emit_team_obs_mixed(inv_u8, opp_obs, None, 0, n_net, **self._fog)     # the opponent is red where the learner is blue
+                env.emit_team_obs_mixed(inv_u8, opp_obs, None, 0, n_net, **okw)           # the opponent is red where the learner is blue
                 olg = mappo.canonicalize_legal(mappo.team_columns(env.legal, red_u8, opponents=True), inv_u8) if masks else None
                 for model, lo, hi in ((self.model, 0, n_self), (self.opponent_model, n_self, n_net)):
                     if hi > lo:
                         oa, _, _ = self._forward_policy(model, opp_obs[lo:hi], None, False, olg[lo:hi] if masks else None)
                         mappo.set_team_columns(acts[lo:hi], red_u8[lo:hi], mappo.canonicalize_action(oa, inv_u8[lo:hi]), opponents=True)
             _, rew, done, info = env.step(acts, want_obs=False)
+            if self.belief:
+                env.belief_update(red_u8, bel, self.sight_range, reset=done)
+                if n_net:
+                    env.belief_update(inv_u8, obel, self.sight_range, reset=done, first=0, count=n_net)
             cur_agent = info["agent"]
             shp = shaping_from_agent_words(mappo.team_columns(self.prev_agent, red_u8), mappo.team_columns(cur_agent, red_u8))   # [N,2] f64
             own = torch.where(red_b, rew[:, 0], rew[:, 1])
@@ -454,7 +512,7 @@ class VecMAPPOTrainer:
             sc = info["score"]
             win_env += d & torch.where(red_b, sc > 0, sc < 0)
         # bootstrap value of the state after the last tick (:541-546)
-        env.emit_team_obs_mixed(red_u8, self._boot_obs, self._boot_merged if mappo_alg else None, **self._fog)
+        env.emit_team_obs_mixed(red_u8, self._boot_obs, self._boot_merged if mappo_alg else None, **kw)
         ctx = torch.autocast(device_type=self.device.type, dtype=self.autocast_dtype) if self.autocast_dtype else _NullCtx()
         with torch.no_grad(), ctx:
             if mappo_alg:
@@ -602,14 +660,22 @@ class VecMAPPOTrainer:
         r = ck["np_rng"]
         self.np_rng.set_state((r["kind"], r["keys"].cpu().numpy().astype(np.uint32), int(r["pos"]), int(r["has_gauss"]),
                                float(r["cached_gaussian"])))
+        if self.belief:                                                  # the sets are not saved: a resumed run knows the board only
+            for buf in (self._belief, self._belief_opp):
+                if buf is not None:
+                    self.env.belief_init(buf[0], 1)
+                    buf[1][:] = -2
 
 
 def evaluate_vs_bots(model, num_episodes=20, layout_file="bloxCapture", teams=("baselineTeam", "randomTeam"), length=300,
-                     device="cuda:0", fog_of_war=False, sight_range=SIGHT_RANGE):
+                     device="cuda:0", fog_of_war=False, sight_range=SIGHT_RANGE, belief=False):
     """evaluate_vs_bots (pacman_mappo_resnet.py:293-337): a fresh env per episode against host CaptureAgent bots (red),
     the learner plays blue with argmax actions; returns (mean return, std, win rate), a win being final score < 0.
     The reference cycles through its A*/approx-Q/baseline/MCTS teams; here through the team files this build ships.
     fog_of_war: the learner's planes go through fog_obs (the host bots keep the full state the env gives them)."""
+    if belief:
+        raise ValueError("evaluate_vs_bots has no belief tracker (no emission kernel runs on the host-bot path): evaluate a policy "
+                         "trained with belief=True with evaluate_vectorized(belief=True)")
     from .gym_env import gymPacMan_parallel_env
     was_training = model.training
     model.eval()
@@ -639,7 +705,7 @@ def evaluate_vs_bots(model, num_episodes=20, layout_file="bloxCapture", teams=("
 
 @torch.no_grad()
 def evaluate_vectorized(model, layout="bloxCapture", n_envs=1024, opponent="baseline", length=300, device="cuda:0", seed=0,
-                        autocast=True, mask_illegal=False, side="blue", fog_of_war=False, sight_range=SIGHT_RANGE):
+                        autocast=True, mask_illegal=False, side="blue", fog_of_war=False, sight_range=SIGHT_RANGE, belief=False):
     """evaluate_vs_bots (pacman_mappo_resnet.py:293-337) for n_envs episodes at once: the learner plays blue with argmax
     actions against the in-kernel randomTeam / baselineTeam / approxQTeam (opponent "random" / "baseline" / "approxq"), one episode per env (an env stops counting at its first done).
     Returns (mean episode return of the learner team as the reference sums it, std, win rate = share with final score < 0).
@@ -647,12 +713,16 @@ def evaluate_vectorized(model, layout="bloxCapture", n_envs=1024, opponent="base
     side: "blue" as above; "red": the learner plays red and the bots blue; "both": red in the first half of the envs, blue in
     the rest (a policy trained with mix_opponents plays both colours).  A red learner's win is a final score > 0.
     fog_of_war: the policy sees an enemy only within sight_range of one of its two agents (pmx_emit_team_obs_mixed_fog); every
-    side, blue included, then runs the emission-based loop.  The in-kernel bots keep the full state."""
+    side, blue included, then runs the emission-based loop.  The in-kernel bots keep the full state.
+    belief (needs fog_of_war): plane 5 shows the tracker's sets (pmx_belief_update after every step, pmx_emit_team_obs_mixed_belief),
+    the inputs of a policy trained with the trainer's belief=True."""
     if side not in ("blue", "red", "both"):
         raise ValueError(f"side must be blue, red or both, got {side!r}")
+    if belief and not fog_of_war:
+        raise ValueError("belief=True needs fog_of_war=True")
     if side != "blue" or fog_of_war:
         return _evaluate_sides(model, layout, n_envs, opponent, length, device, seed, autocast, mask_illegal, side,
-                               int(sight_range) if fog_of_war else None)
+                               int(sight_range) if fog_of_war else None, **({"belief": True} if belief else {}))
     dev = torch.device(device)
     env = PmxVecEnv(layout, n_envs, length=length, auto_reset=True, obs_dtype="bfloat16" if autocast else "float32", device=dev,
                     seed=seed, bots=opponent in BOT_TEAMS)
@@ -689,10 +759,10 @@ def evaluate_vectorized(model, layout="bloxCapture", n_envs=1024, opponent="base
     return float(ret.mean()), float(ret.std()), float((final < 0).double().mean())
 
 
-def _evaluate_sides(model, layout, n_envs, opponent, length, device, seed, autocast, mask_illegal, side, sight_range=None):
+def _evaluate_sides(model, layout, n_envs, opponent, length, device, seed, autocast, mask_illegal, side, sight_range=None, belief=False):
     """evaluate_vectorized with the learner's colour chosen per env: observations from pmx_emit_team_obs_mixed (canonical, so the
     policy sees a red game as it was trained to), actions and masks through the per-env frame helpers.  sight_range (an int): the
-    fog form of the emission."""
+    fog form of the emission; with belief the belief form, the sets advanced after every step."""
     dev = torch.device(device)
     env = PmxVecEnv(layout, n_envs, length=length, auto_reset=True, obs_dtype="bfloat16" if autocast else "float32", device=dev,
                     seed=seed, bots=opponent in BOT_TEAMS)
@@ -710,8 +780,12 @@ def _evaluate_sides(model, layout, n_envs, opponent, length, device, seed, autoc
     mappo.set_team_columns(acts, red, torch.tensor(opp, dtype=torch.int8, device=dev)[None].expand(n_envs, 2), opponents=True)
     team_obs = torch.empty((n_envs, 2) + env.obs_shape, dtype=env.obs_torch_dtype, device=dev)
     ctx = torch.autocast(device_type=dev.type, dtype=torch.bfloat16) if autocast else _NullCtx()
+    kw = {} if sight_range is None else {"sight_range": sight_range}
+    if belief:
+        bel = env.belief_init(env.new_belief(), 0)
+        kw = {"belief": bel}
     for _ in range(length + 1):
-        env.emit_team_obs_mixed(red, team_obs, **({} if sight_range is None else {"sight_range": sight_range}))
+        env.emit_team_obs_mixed(red, team_obs, **kw)
         lo = team_obs.view((-1,) + env.obs_shape)
         with ctx:
             if mask_illegal:
@@ -721,6 +795,8 @@ def _evaluate_sides(model, layout, n_envs, opponent, length, device, seed, autoc
                 a = model.get_deterministic_action(lo).view(n_envs, 2)
         mappo.set_team_columns(acts, red, mappo.canonicalize_action(a, red))
         _, rew, done, info = env.step(acts, want_obs=False)
+        if belief:
+            env.belief_update(red, bel, sight_range, reset=done)
         own = torch.where(red_b, rew[:, 0], rew[:, 1])
         ret += torch.where(alive, own + own, torch.zeros_like(ret))                 # sum over both learners' rewards (:328)
         d = done.to(torch.bool) & alive

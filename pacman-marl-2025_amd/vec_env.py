@@ -188,16 +188,24 @@ class PmxVecEnv:
                       _lib.stream(self.device))
         return self.obs, self.legal
 
-    def emit_team_obs(self, team_red, team_obs, merged=None, sight_range=None):
+    def emit_team_obs(self, team_red, team_obs, merged=None, sight_range=None, belief=None):
         """The two observations of one team for the CURRENT tick (canonicalised for red) into team_obs [N,2,8,H,W] and, if
         given, the merged critic input into merged [N,8,H,W] (pmx_emit_team_obs; pacman_mappo_resnet.py:215-229, :267-274).
         sight_range (an int): the contest's fog of war on the two learners' planes (pmx_emit_team_obs_fog; capture.py:268-292),
-        an enemy shows only within that Manhattan distance of one of the team's agents; merged stays full-information."""
+        an enemy shows only within that Manhattan distance of one of the team's agents; merged stays full-information.
+        belief (a new_belief() tensor, in place of sight_range): plane 5 of slot j is the OR of the tracker's two sets of that
+        slot (pmx_emit_team_obs_belief); the tensor is only read."""
         N = self.n_envs
         assert team_obs.shape == (N, 2) + self.obs_shape and team_obs.dtype == self.obs_torch_dtype and team_obs.is_contiguous()
         if merged is not None:
             assert merged.shape == (N,) + self.obs_shape and merged.dtype == self.obs_torch_dtype and merged.is_contiguous()
         with torch.cuda.device(self.device):
+            if belief is not None:
+                assert sight_range is None, "the belief emission applies no sight rule of its own: pass one of the two"
+                self._check_belief(belief, N)
+                _lib.call("pmx_emit_team_obs_belief", self.handle, int(bool(team_red)), belief.data_ptr(), team_obs.data_ptr(),
+                          merged.data_ptr() if merged is not None else None, _lib.stream(self.device))
+                return team_obs, merged
             if sight_range is not None:
                 _lib.call("pmx_emit_team_obs_fog", self.handle, int(bool(team_red)), int(sight_range), team_obs.data_ptr(),
                           merged.data_ptr() if merged is not None else None, _lib.stream(self.device))
@@ -206,11 +214,12 @@ class PmxVecEnv:
                       merged.data_ptr() if merged is not None else None, _lib.stream(self.device))
         return team_obs, merged
 
-    def emit_team_obs_mixed(self, team_red, team_obs, merged=None, first=0, count=None, sight_range=None):
+    def emit_team_obs_mixed(self, team_red, team_obs, merged=None, first=0, count=None, sight_range=None, belief=None):
         """emit_team_obs with the learners' colour chosen per env (pmx_emit_team_obs_mixed): team_red uint8 [N], non-zero = that
         env's learners are red.  Writes rows for the envs first .. first + count - 1 (count None: up to the last env), row j for
         env first + j, into team_obs [count,2,8,H,W] and, if given, merged [count,8,H,W].  sight_range as in emit_team_obs
-        (pmx_emit_team_obs_mixed_fog)."""
+        (pmx_emit_team_obs_mixed_fog); belief as there too, a [count,2,2,32] tensor whose row j belongs to env first + j
+        (pmx_emit_team_obs_mixed_belief)."""
         N = self.n_envs
         first = int(first)
         count = N - first if count is None else int(count)
@@ -221,6 +230,12 @@ class PmxVecEnv:
         if count == 0:                                   # (an empty tensor has no address to pass)
             return team_obs, merged
         with torch.cuda.device(self.device):
+            if belief is not None:
+                assert sight_range is None, "the belief emission applies no sight rule of its own: pass one of the two"
+                self._check_belief(belief, count)
+                _lib.call("pmx_emit_team_obs_mixed_belief", self.handle, team_red.data_ptr(), first, count, belief.data_ptr(),
+                          team_obs.data_ptr(), merged.data_ptr() if merged is not None else None, _lib.stream(self.device))
+                return team_obs, merged
             if sight_range is not None:
                 _lib.call("pmx_emit_team_obs_mixed_fog", self.handle, team_red.data_ptr(), first, count, int(sight_range),
                           team_obs.data_ptr(), merged.data_ptr() if merged is not None else None, _lib.stream(self.device))
@@ -228,6 +243,51 @@ class PmxVecEnv:
             _lib.call("pmx_emit_team_obs_mixed", self.handle, team_red.data_ptr(), first, count, team_obs.data_ptr(),
                       merged.data_ptr() if merged is not None else None, _lib.stream(self.device))
         return team_obs, merged
+
+    # -- belief sets of the hidden enemies (include/pmx.h, "Belief sets") -------------------------------------------
+    def new_belief(self, count=None):
+        """A belief buffer for `count` envs (None: all): int32 [count, 2 slots, 2 enemies, 32 row words], zeroed; bit x of word y
+        = the enemy can be on cell (x, y).  Call belief_init before the first use."""
+        return torch.zeros((self.n_envs if count is None else int(count), 2, 2, 32), dtype=torch.int32, device=self.device)
+
+    def _check_belief(self, belief, count):
+        assert belief.shape == (count, 2, 2, 32) and belief.dtype == torch.int32 and belief.is_contiguous() and belief.device == self.device
+
+    def belief_init(self, belief, kind=0, first=0, count=None):
+        """pmx_belief_init on rows 0 .. count - 1 of `belief` for the envs first .. first + count - 1: kind 0 = the start cells
+        (after reset()), kind 1 = every open cell (after set_state(), or when the learners' colour changes)."""
+        first = int(first)
+        count = self.n_envs - first if count is None else int(count)
+        if count == 0:
+            return belief
+        self._check_belief(belief, count)
+        with torch.cuda.device(self.device):
+            _lib.call("pmx_belief_init", self.handle, first, count, int(kind), belief.data_ptr(), _lib.stream(self.device))
+        return belief
+
+    def belief_update(self, team_red, belief, sight_range, reset=None, first=0, count=None, sonar=None):
+        """pmx_belief_update, once after each step(): advances the sets of the envs first .. first + count - 1 (row j of `belief`
+        for env first + j) by the enemy's motion, the respawn rule, the sight rule and this tick's sonar readings.  team_red: a
+        bool, or a uint8 [N] tensor (per env).  reset: uint8 [N], non-zero = that env was reset (pass step()'s done under
+        auto_reset): its sets go back to the start cells.  sonar: optional int8 [count, 2, 2] output of the readings."""
+        first = int(first)
+        count = self.n_envs - first if count is None else int(count)
+        if count == 0:
+            return belief
+        self._check_belief(belief, count)
+        red_dev = None
+        if isinstance(team_red, torch.Tensor):
+            assert team_red.shape == (self.n_envs,) and team_red.dtype == torch.uint8 and team_red.is_contiguous() and team_red.device == self.device
+            red_dev, team_red = team_red.data_ptr(), 0
+        if reset is not None:
+            assert reset.shape == (self.n_envs,) and reset.dtype == torch.uint8 and reset.is_contiguous() and reset.device == self.device
+        if sonar is not None:
+            assert sonar.shape == (count, 2, 2) and sonar.dtype == torch.int8 and sonar.is_contiguous() and sonar.device == self.device
+        with torch.cuda.device(self.device):
+            _lib.call("pmx_belief_update", self.handle, int(bool(team_red)), red_dev, first, count, int(sight_range),
+                      reset.data_ptr() if reset is not None else None, belief.data_ptr(), sonar.data_ptr() if sonar is not None else None,
+                      _lib.stream(self.device))
+        return belief
 
     # -- measurement ---------------------------------------------------------------------------------------------
     def profile_begin(self, max_launches):

@@ -1,0 +1,125 @@
+"""Measurements of the belief sets (profiles/belief/README.md).
+
+  times      the kernels' own durations (the start / stop events pmx_profile_begin attaches to each dispatch) of pmx_belief_update,
+             pmx_emit_team_obs_belief and pmx_emit_team_obs_fog on byte planes, interleaved launch by launch in one process after a
+             warm-up, and the budget a reviewer would hold the belief emission to: the fog emission's time plus the time of 512
+             more bytes per env at the fog emission's own bandwidth
+  tightness  over a game of in-kernel baselineTeam bots on both sides: the mean size of a hidden enemy's set and the share of
+             hidden cases whose set still holds the enemy's start cell while the enemy is more than 6 cells from it (the price of
+             the respawn rule), for blue learners' second slot, whose snapshot is the end-of-tick state pmx_get_state returns
+  eval       greedy win rate of an EMA checkpoint (tools/train.py --save) against the in-kernel baselineTeam under fog, with or
+             without the belief sets (--belief)
+"""
+import argparse
+import json
+import os
+import sys
+
+sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
+import numpy as np
+import torch
+
+import pmx
+from pmx import mappo, trainer
+
+
+def times(args):
+    N, s = args.envs, args.sight_range
+    env = pmx.PmxVecEnv(args.layout, N, obs_dtype="uint8", seed=1)
+    env.reset(want_obs=False)
+    g = torch.Generator(device="cuda").manual_seed(2)
+    n_slots = 4                                                 # rotate the outputs and the buffers
+    bel = [env.belief_init(env.new_belief(), 0) for _ in range(n_slots)]
+    for _ in range(8):                                          # a few ticks: valid snapshots, agents off their starts, sets of many cells
+        env.step(torch.randint(0, 5, (N, 4), generator=g, device="cuda", dtype=torch.int8), want_obs=False)
+        for b in bel:
+            env.belief_update(False, b, s, reset=env.done)
+    team = [torch.empty((N, 2) + env.obs_shape, dtype=torch.uint8, device="cuda") for _ in range(n_slots)]
+    merged = [torch.empty((N,) + env.obs_shape, dtype=torch.uint8, device="cuda") for _ in range(n_slots)]
+    t = {"update": [], "emit_belief": [], "emit_fog": []}
+    for k in range(args.warmup + args.launches):
+        i = k % n_slots
+        env.profile_begin(4)
+        env.belief_update(False, bel[i], s)
+        env.emit_team_obs(False, team[i], merged[i], belief=bel[i])
+        a = env.profile_end()
+        env.profile_begin(4)
+        env.emit_team_obs(False, team[i], merged[i], sight_range=s)
+        b = env.profile_end()
+        if k >= args.warmup:
+            t["update"].append(a["rule_ms"] * 1e3)
+            t["emit_belief"].append(a["expand_ms"] * 1e3)
+            t["emit_fog"].append(b["expand_ms"] * 1e3)
+    H, W = env.layout.height, env.layout.width
+    out = {"envs": N, "layout": args.layout, "launches": args.launches, "warmup": args.warmup, "sight_range": s,
+           "mean_set_cells": round(float(sum(bin(int(w) & 0xFFFFFFFF).count("1") for w in bel[0][:256].cpu().numpy().ravel())) / (256 * 4), 2)}
+    for name, v in t.items():
+        v = np.array(v)
+        out[name + "_us"] = {"mean": round(float(v.mean()), 3), "median": round(float(np.median(v)), 3), "min": round(float(v.min()), 3),
+                             "max": round(float(v.max()), 3), "std": round(float(v.std()), 3)}
+    fog, belief, upd = (out[k + "_us"]["mean"] for k in ("emit_fog", "emit_belief", "update"))
+    stored = 3 * 8 * H * W                                      # bytes an emission stores per env (three slots of byte planes)
+    out["update_share_of_fog_emission"] = round(upd / fog, 4)
+    out["fog_emission_GBps"] = round(N * stored / (fog * 1e-6) / 1e9, 1)
+    out["belief_emission_budget_us"] = round(fog * (1 + 512 / stored), 3)
+    out["belief_emission_excess_us"] = round(belief - out["belief_emission_budget_us"], 3)
+    print(json.dumps(out))
+
+
+def tightness(args):
+    N, T, s = args.envs, args.ticks, args.sight_range
+    env = pmx.PmxVecEnv(args.layout, N, length=T, obs_dtype="uint8", seed=args.seed, bots=True)
+    env.reset(want_obs=False)
+    lay = env.layout
+    starts = lay.starts.astype(np.int64)
+    codes = torch.tensor([-3, -3, -4, -4], dtype=torch.int8, device="cuda")[None].expand(N, 4).contiguous()
+    bel = env.belief_init(env.new_belief(), 0)
+    hidden = cells = with_start = 0
+    for _ in range(T):
+        env.step(codes, want_obs=False)
+        env.belief_update(False, bel, s, reset=env.done)
+        st = env.get_state()
+        pos = np.array([[[p.pos[i][0], p.pos[i][1]] for i in range(4)] for p in st], np.int64)
+        live = ~env.done.cpu().numpy().astype(bool)
+        words = bel[:, 1].cpu().numpy().view(np.uint32)         # blue learners' second slot: the end-of-tick state
+        for k, e in enumerate((0, 2)):
+            d = np.minimum(np.abs(pos[:, e] - pos[:, 1]).sum(1), np.abs(pos[:, e] - pos[:, 3]).sum(1))
+            h = live & (d > s)
+            size = np.array([sum(bin(int(w)).count("1") for w in words[n, k]) for n in np.nonzero(h)[0]])
+            hidden += int(h.sum())
+            cells += int(size.sum())
+            sx, sy = int(starts[e, 0]), int(starts[e, 1])
+            has = ((words[:, k, sy] >> np.uint32(sx)) & 1).astype(bool)
+            away = np.abs(pos[:, e] - starts[e]).sum(1) > 6
+            with_start += int((h & has & away).sum())
+    print(json.dumps({"layout": args.layout, "envs": N, "ticks": T, "sight_range": s, "hidden_cases": hidden,
+                      "mean_set_cells": round(cells / max(hidden, 1), 2),
+                      "start_cell_kept_while_far_share": round(with_start / max(hidden, 1), 4)}))
+
+
+def evaluate(args):
+    lay = pmx.get_layout(args.layout)
+    model = mappo.MAPPOAgent((8, lay.height, lay.width), 5, 2).cuda()
+    model.load_state_dict(torch.load(args.checkpoint, map_location="cuda", weights_only=True))
+    kw = dict(fog_of_war=True, sight_range=args.sight_range, **({"belief": True} if args.belief else {}))
+    mean, std, rate = trainer.evaluate_vectorized(model, args.layout, args.episodes, "baseline", seed=args.seed, **kw)
+    print(json.dumps({"checkpoint": os.path.basename(args.checkpoint), "layout": args.layout, "episodes": args.episodes, "opponent": "baseline",
+                      "sight_range": args.sight_range, "belief": bool(args.belief), "win_rate": rate, "return_mean": round(mean, 3),
+                      "return_std": round(std, 3)}))
+
+
+if __name__ == "__main__":
+    ap = argparse.ArgumentParser()
+    ap.add_argument("what", choices=["times", "tightness", "eval"])
+    ap.add_argument("--layout", default="smallCapture")
+    ap.add_argument("--envs", type=int, default=16384)
+    ap.add_argument("--launches", type=int, default=520)
+    ap.add_argument("--warmup", type=int, default=40)
+    ap.add_argument("--ticks", type=int, default=300)
+    ap.add_argument("--sight-range", type=int, default=5)
+    ap.add_argument("--checkpoint", default="")
+    ap.add_argument("--belief", action="store_true")
+    ap.add_argument("--episodes", type=int, default=1024)
+    ap.add_argument("--seed", type=int, default=0)
+    a = ap.parse_args()
+    {"times": times, "tightness": tightness, "eval": evaluate}[a.what](a)

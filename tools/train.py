@@ -55,6 +55,8 @@ def parser():
                                                                                          "the envs); a policy trained with --mix-opponents plays both")
     ap.add_argument("--fog-of-war", action="store_true", help="the contest's sight rule on every policy input: an enemy shows only within --sight-range of one of the "
                                                               "team's two agents (the critic's merged input stays full); the evaluation runs under the same rule")
+    ap.add_argument("--belief", action="store_true", help="with --fog-of-war: track, per hidden enemy, the set of cells it can be on (sight rule, noisy sonar "
+                    "distances, motion) on the device and show the sets in plane 5 of every policy input, in training and in the evaluations")
     ap.add_argument("--sight-range", type=int, default=5, help="with --fog-of-war: Manhattan cells (the contest's SIGHT_RANGE is 5)")
     ap.add_argument("--graph", action="store_true", help="replay the optimizer step from a hipGraph (launch-bound minibatches, e.g. 512)")
     return ap
@@ -95,6 +97,8 @@ def main():
                 fh.write(line + "\n")
 
     fog = {"fog_of_war": True, "sight_range": args.sight_range} if args.fog_of_war else {}
+    if args.belief:
+        fog["belief"] = True                                    # (without --fog-of-war the trainer rejects it)
     tr = trainer.VecMAPPOTrainer(layout, args.envs, horizon=args.horizon, minibatch=args.minibatch, epochs=args.epochs, redraw_layouts=args.redraw,
                                  obs_dtype=args.obs, device=f"cuda:{local}", seed=args.seed, rank=rank, world_size=world,
                                  total_updates=args.total_updates, opponent=args.opponent, algorithm=args.algorithm, use_graph=args.graph, paired_minibatches=not args.unpaired, curriculum_scale=args.curriculum_scale,
