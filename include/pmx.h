@@ -275,6 +275,59 @@ int pmx_emit_team_obs_belief(pmx_env *env, int team_red, const uint32_t *belief_
 int pmx_emit_team_obs_mixed_belief(pmx_env *env, const uint8_t *team_red_dev, int32_t first, int32_t count, const uint32_t *belief_dev,
                                    void *team_obs_dev, void *merged_dev, void *stream);
 
+/* ---- Belief weights: an exact Bayes filter that refines the sets ----------------------------------------------------------------
+ * A set cannot say that one cell is a hundred times less likely than another.  The weighted tracker keeps, beside every set, an
+ * integer weight per cell: the contest's standard exact inference with a uniform random walk over the legal moves (Stop included)
+ * as the motion model, a small respawn prior on the start cell, the sight rule, and the sonar, whose likelihood is flat over its 13
+ * values and so only cuts the annulus the set rule already cuts.  All integer and exact; the support of the weights IS the set.
+ *
+ * Buffers (caller-owned), HW = H * W of the handle, cell c = y * W + x in raw (not flipped) coordinates:
+ *   belief   uint32_t [rows][2][2][32]          the sets, advanced by the table of "Belief sets" unchanged
+ *   weights  uint16_t [rows][2 slots][2 enemies][HW]
+ *   levels   uint8_t  [rows][2 slots][HW]       what the weighted emission shows, 0 .. PMX_BELIEF_LEVELS
+ * R[d] = floor(65536 / d): 65536, 32768, 21845, 16384, 13107 for d = 1 .. 5.  deg(n) = 1 + the number of open 4-neighbours of cell
+ * n, the count of legal actions there, Stop included.
+ *
+ * pmx_belief_weights_update REPLACES pmx_belief_update (same arguments plus the two buffers; it is not run in addition): it draws
+ * the same readings with the same key, salt and tick word and applies the same five steps to the sets, so belief and sonar_dev come
+ * out bit for bit as pmx_belief_update leaves them.  Beside them, for slot j = 0, then j = 1, and both enemies k:
+ *   1. start      q = the previous call's slot-1 weights when j == 0, the slot-0 weights just computed when j == 1;
+ *   2. motion     for the enemy that moved (the set rule's condition, e_k == (a_j + 3) % 4):
+ *                 t[c] = sum over n in {c} + N4(c), n open, of (q[n] * R[deg(n)]) >> 16 for open c, 0 on walls, in uint32;
+ *                 for the other enemy t = q;
+ *   3. respawn    t[start cell of e_k] += 1 + (T >> PMX_BELIEF_RESPAWN_SHIFT), T = sum of t: about 1/64 of the mass per tick over
+ *                 the two slots.  A modelling constant, not a measured one;
+ *   4. sight and sonar   S' = the set this step produces (step 4 of the set table).  Enemy seen: q' = 65535 on its cell, 0
+ *                 elsewhere, and step 5 is skipped.  Hidden: u[c] = max(t[c], 1) for c in S', 0 elsewhere; the floor of 1 makes
+ *                 support(q') == S' hold exactly whatever the rounding did;
+ *   5. normalise  by a shift, no division: m = max u, b = 32 - clz(m).  b > 16: q'[c] = max(u[c] >> (b - 16), 1) on S';
+ *                 otherwise q'[c] = u[c] << (16 - b); S' empty: q' = 0.  Hence 32768 <= max q' <= 65535 for a hidden enemy;
+ *   6. store      weights[row][j][k] = q';  levels[row][j][c] = max over k of (q'_k[c] == 0 ? 0 : 1 + (q'_k[c] >> 12)), 0 .. 16:
+ *                 a seen enemy's cell is 16, a hidden enemy's mode cell 9 .. 16.
+ * Bounds: q <= 65535 and R <= 65536, so a product is below 2^32; t[c] <= 5 * 65535; T <= 1024 * 5 * 65535 < 2^32;
+ * u <= 5 * 65535 + 1 + (T >> 7) < 2^22.
+ * reset_dev[env] != 0: as for the sets -- both slots of both enemies become 65535 on the enemy's start cell in the env's current
+ * layout, the levels 16 there, the readings 0.  Errors as pmx_belief_update, and PMX_ERR_INVALID for a NULL weights_dev or
+ * levels_dev; count == 0 launches nothing.
+ *
+ * pmx_belief_weights_init: belief as pmx_belief_init writes it; weights 65535 on the cells of each set (kind 0: the start cells,
+ * kind 1: every open cell) in both slots, 0 elsewhere; levels 16 on the union of the two enemies' sets, so an emission straight
+ * after it is valid. */
+#define PMX_BELIEF_RESPAWN_SHIFT 7
+#define PMX_BELIEF_LEVELS 16
+int pmx_belief_weights_update(pmx_env *env, int team_red, const uint8_t *team_red_dev, int32_t first, int32_t count, int32_t sight_range,
+                              const uint8_t *reset_dev, uint32_t *belief_dev, int8_t *sonar_dev, uint16_t *weights_dev, uint8_t *levels_dev,
+                              void *stream);
+int pmx_belief_weights_init(pmx_env *env, int32_t first, int32_t count, int32_t kind, uint32_t *belief_dev, uint16_t *weights_dev,
+                            uint8_t *levels_dev, void *stream);
+/* pmx_emit_team_obs_belief / _mixed_belief with levels_dev in place of belief_dev and one difference: learner slot j's plane 5 is
+ * levels[row][j] (x-flipped for red like every other plane) as a NUMBER in the output's element type -- the byte itself in uint8
+ * planes, the exactly converted integer in bfloat16 and float32.  Every other plane and the whole merged slot are byte for byte
+ * the plain call's.  The buffer is read, never written. */
+int pmx_emit_team_obs_weighted(pmx_env *env, int team_red, const uint8_t *levels_dev, void *team_obs_dev, void *merged_dev, void *stream);
+int pmx_emit_team_obs_mixed_weighted(pmx_env *env, const uint8_t *team_red_dev, int32_t first, int32_t count, const uint8_t *levels_dev,
+                                     void *team_obs_dev, void *merged_dev, void *stream);
+
 /* The layout each env is currently on (host output [n_envs]; all zeros for a single-layout handle).  Synchronises the stream. */
 int pmx_get_layout_index(pmx_env *env, int32_t *index_out, void *stream);
 

@@ -21,6 +21,8 @@ extern "C" hipError_t pmx_launch_emit_team_mixed(const PmxEmitParams *p, int dty
 extern "C" hipError_t pmx_launch_emit_team_fog(const PmxEmitParams *p, int mixed, int dtype, hipStream_t st, hipEvent_t ev0, hipEvent_t ev1);
 extern "C" hipError_t pmx_launch_emit_team_belief(const PmxEmitParams *p, int mixed, int dtype, hipStream_t st, hipEvent_t ev0, hipEvent_t ev1);
 extern "C" hipError_t pmx_launch_belief(const PmxBeliefParams *p, int init, hipStream_t st, hipEvent_t ev0, hipEvent_t ev1);
+extern "C" hipError_t pmx_launch_emit_team_weighted(const PmxEmitParams *p, int mixed, int dtype, hipStream_t st, hipEvent_t ev0, hipEvent_t ev1);
+extern "C" hipError_t pmx_launch_belief_weights(const PmxBeliefWeightsParams *p, int init, hipStream_t st, hipEvent_t ev0, hipEvent_t ev1);
 extern "C" hipError_t pmx_launch_expand(const PmxExpandParams *p, int dtype, hipStream_t st, hipEvent_t ev0, hipEvent_t ev1);
 extern "C" hipError_t pmx_launch_maze(const PmxLayoutDev *lay_dev, const int16_t *cell_index_dev, int n_cells,
                                       const int8_t *cells_dev, uint8_t *dist_dev, hipStream_t st);
@@ -630,6 +632,92 @@ int pmx_belief_init(pmx_env *env, int32_t first, int32_t count, int32_t kind, ui
     b.kind = kind;
     HIP_TRY(pmx_launch_belief(&b, 1, as_stream(stream), nullptr, nullptr));
     return PMX_OK;
+}
+
+// The weighted tracker (include/pmx.h, "Belief weights"): the set tracker's checks and parameter block, plus the two buffers.
+int pmx_belief_weights_update(pmx_env *env, int team_red, const uint8_t *team_red_dev, int32_t first, int32_t count, int32_t sight_range,
+                              const uint8_t *reset_dev, uint32_t *belief_dev, int8_t *sonar_dev, uint16_t *weights_dev, uint8_t *levels_dev,
+                              void *stream)
+{
+    PmxBeliefWeightsParams w;
+    std::memset(&w, 0, sizeof(w));
+    const int rc = fill_belief_params(env, "pmx_belief_weights_update", first, count, belief_dev, w.b);
+    if (rc != PMX_OK) return rc;
+    if (!weights_dev || !levels_dev) return fail(PMX_ERR_INVALID, "pmx_belief_weights_update: null argument");
+    if (sight_range < 0 || sight_range > PMX_SIGHT_RANGE_MAX)
+        return fail(PMX_ERR_INVALID, "pmx_belief_weights_update: sight_range %d outside 0 .. %d", sight_range, PMX_SIGHT_RANGE_MAX);
+    if (count == 0) return PMX_OK;
+    w.b.red = team_red ? 1 : 0;
+    w.b.team_red = team_red_dev;
+    w.b.sight = sight_range;
+    w.b.reset = reset_dev;
+    w.b.sonar = sonar_dev;
+    w.weights = weights_dev;
+    w.levels = levels_dev;
+    hipEvent_t *ev = prof_pair(env, false);          // recorded with the rule launches, as pmx_belief_update is
+    HIP_TRY(pmx_launch_belief_weights(&w, 0, as_stream(stream), ev ? ev[0] : nullptr, ev ? ev[1] : nullptr));
+    return PMX_OK;
+}
+
+int pmx_belief_weights_init(pmx_env *env, int32_t first, int32_t count, int32_t kind, uint32_t *belief_dev, uint16_t *weights_dev,
+                            uint8_t *levels_dev, void *stream)
+{
+    PmxBeliefWeightsParams w;
+    std::memset(&w, 0, sizeof(w));
+    const int rc = fill_belief_params(env, "pmx_belief_weights_init", first, count, belief_dev, w.b);
+    if (rc != PMX_OK) return rc;
+    if (!weights_dev || !levels_dev) return fail(PMX_ERR_INVALID, "pmx_belief_weights_init: null argument");
+    if (kind != 0 && kind != 1) return fail(PMX_ERR_INVALID, "pmx_belief_weights_init: kind %d is neither 0 (start cells) nor 1 (open cells)", kind);
+    if (count == 0) return PMX_OK;
+    w.b.kind = kind;
+    w.weights = weights_dev;
+    w.levels = levels_dev;
+    HIP_TRY(pmx_launch_belief_weights(&w, 1, as_stream(stream), nullptr, nullptr));
+    return PMX_OK;
+}
+
+namespace {
+// what the weighted emission pair shares: the plain pair's parameter block with the levels; mixed: team_red_dev and the range
+int emit_weighted(pmx_env *env, const char *who, int mixed, int team_red, const uint8_t *team_red_dev, int32_t first, int32_t count,
+                  const uint8_t *levels_dev, void *team_obs_dev, void *merged_dev, void *stream)
+{
+    if (!env || !team_obs_dev || !levels_dev || (mixed && !team_red_dev)) return fail(PMX_ERR_INVALID, "%s: null argument", who);
+    if (mixed && (first < 0 || count < 0 || (int64_t)first + count > env->cfg.n_envs))
+        return fail(PMX_ERR_INVALID, "%s: envs %d .. %lld of %d", who, first, (long long)first + count - 1, env->cfg.n_envs);
+    if (env->open_agent != 0) return fail(PMX_ERR_INVALID, "%s: a tick opened with pmx_step_agent is unfinished", who);
+    if (mixed && count == 0) return PMX_OK;
+    PmxEmitParams x;
+    std::memset(&x, 0, sizeof(x));
+    const size_t snap_sz = (size_t)PMX_SNAP_WORDS(env->lay.H) * env->cfg.n_envs;
+    for (int a = 0; a < 4; ++a) x.snap[a] = (env->snaps_valid && a < 3) ? env->snap_dev + a * snap_sz : env->state_dev;
+    x.lay = env->lay_dev;
+    x.layout_idx = env->layout_idx_dev;
+    x.team_obs = team_obs_dev;
+    x.merged = merged_dev;
+    x.N = env->cfg.n_envs;
+    x.lay_H = env->lay.H, x.lay_W = env->lay.W;
+    if (mixed) {
+        x.team_red = team_red_dev;
+        x.first = first, x.count = count;
+    } else {
+        x.red = team_red ? 1 : 0;
+    }
+    x.levels = levels_dev;
+    hipEvent_t *ev = prof_pair(env, true);           // recorded with the expansion launches, as pmx_emit_team_obs is
+    HIP_TRY(pmx_launch_emit_team_weighted(&x, mixed, env->cfg.obs_dtype, as_stream(stream), ev ? ev[0] : nullptr, ev ? ev[1] : nullptr));
+    return PMX_OK;
+}
+}  // namespace
+
+int pmx_emit_team_obs_weighted(pmx_env *env, int team_red, const uint8_t *levels_dev, void *team_obs_dev, void *merged_dev, void *stream)
+{
+    return emit_weighted(env, "pmx_emit_team_obs_weighted", 0, team_red, nullptr, 0, 0, levels_dev, team_obs_dev, merged_dev, stream);
+}
+
+int pmx_emit_team_obs_mixed_weighted(pmx_env *env, const uint8_t *team_red_dev, int32_t first, int32_t count, const uint8_t *levels_dev,
+                                     void *team_obs_dev, void *merged_dev, void *stream)
+{
+    return emit_weighted(env, "pmx_emit_team_obs_mixed_weighted", 1, 0, team_red_dev, first, count, levels_dev, team_obs_dev, merged_dev, stream);
 }
 
 int pmx_step_agent(pmx_env *env, int agent, const int8_t *actions_dev, const pmx_step_out *out, void *stream)

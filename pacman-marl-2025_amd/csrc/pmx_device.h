@@ -126,6 +126,10 @@ struct PmxEmitParams {
     // pmx_emit_team_obs_belief / _mixed_belief only (pmx_emit_team_kernel<DT, MIXED, false, true>; NULL and unread otherwise): the
     // tracker's sets, [rows][2 slots][2 enemies][32] row words; learner slot j's plane 5 is the OR of its two sets
     const uint32_t *belief;
+    // pmx_emit_team_obs_weighted / _mixed_weighted only (pmx_emit_team_kernel<DT, MIXED, false, false, true>; NULL and unread
+    // otherwise): the weighted tracker's levels, uint8 [rows][2 slots][HW], cell y * W + x raw; learner slot j's plane 5 is
+    // levels[row][j] as numbers
+    const uint8_t *levels;
 };
 
 // pmx_belief_update / pmx_belief_init: the possibilistic tracker of the hidden enemies (include/pmx.h, "Belief sets")
@@ -142,6 +146,14 @@ struct PmxBeliefParams {
     int32_t lay_H, lay_W;
     uint32_t seed;
     int32_t kind;                // pmx_belief_init only: 0 = start cells, 1 = every open cell
+};
+
+// pmx_belief_weights_update / pmx_belief_weights_init (include/pmx.h, "Belief weights"): the set tracker's block, unchanged, and
+// the two buffers of the weighted filter.  A block of its own, so that pmx_belief_kernel's argument is the one it was.
+struct PmxBeliefWeightsParams {
+    PmxBeliefParams b;
+    uint16_t *weights;           // [count][2 slots][2 enemies][HW]
+    uint8_t *levels;             // [count][2 slots][HW]
 };
 
 // Host-side launch tuning, changed through pmx_set_tuning: -1 = the built-in choice.

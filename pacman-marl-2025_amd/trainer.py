@@ -133,7 +133,7 @@ class VecMAPPOTrainer:
                  device="cuda:0", seed=0, rank=0, world_size=1, process_group=None, total_updates=2000, length=300,
                  use_autocast=True, opponent="random", use_graph=False, algorithm="mappo", paired_minibatches=True, curriculum_scale=1.0,
                  env=None, redraw_layouts=False, force_collectives=False, hard_bots=("baseline",), mask_illegal=False,
-                 mix_opponents=False, fog_of_war=False, sight_range=SIGHT_RANGE, belief=False):
+                 mix_opponents=False, fog_of_war=False, sight_range=SIGHT_RANGE, belief=False, belief_weights=False):
         self.device = torch.device(device)
         # fog_of_war: every policy input of the rollout (the learners', the self / pool opponent networks', the bootstrap
         # observation) comes from the fog entry points -- an enemy shows only within sight_range of one of the team's agents, the
@@ -153,6 +153,13 @@ class VecMAPPOTrainer:
         self.belief = bool(belief)
         if self.belief and not self.fog_of_war:
             raise ValueError("belief=True needs fog_of_war=True: without the sight rule no enemy is hidden and there is nothing to track")
+        # belief_weights (needs fog_of_war and belief): beside every set the env keeps a weight per cell, the exact Bayes filter of
+        # include/pmx.h "Belief weights", and plane 5 shows its levels 0 .. 16 in place of the sets' 0 / 1.  Every tracker call and
+        # every belief emission of the rollout is then the weighted form (pmx_belief_weights_update / _init, pmx_emit_team_obs_weighted);
+        # the two extra tensors ride along with each belief buffer and are not saved either.  Off: none of the new calls is made
+        self.belief_weights = bool(belief_weights)
+        if self.belief_weights and not (self.fog_of_war and self.belief):
+            raise ValueError("belief_weights=True needs fog_of_war=True and belief=True: the weights refine the sets of the hidden enemies")
         self.rank, self.world_size = rank, world_size
         # hard_bots: the in-kernel teams the curriculum draws its "hard" opponent from (the reference's hard teams are
         # baselineTeam, AstarTeam and approxQTeam, pacman_mappo_resnet.py:40-47); the default keeps the draws of earlier versions
@@ -290,11 +297,35 @@ class VecMAPPOTrainer:
 
     # ---- belief buffers: [tensor, colour] with colour a host array [N]: 0 / 1 = the row tracks the enemies of a blue / red team,
     # -1 = start cells of the reset the constructor made, -2 = every open cell (both sound for either colour), 2 = the row missed
-    # the last rollout's updates and is re-initialised before it is used again
+    # the last rollout's updates and is re-initialised before it is used again.  Under belief_weights the tensor is the triple
+    # (sets, weights, levels), sliced and initialised together
     def _new_belief(self):
         b = self.env.new_belief()
-        self.env.belief_init(b, 0)
+        if self.belief_weights:
+            b = (b,) + tuple(self.env.new_belief_weights())
+        self._belief_init(b, 0)
         return [b, np.full(self.N, -1, np.int8)]
+
+    def _belief_init(self, t, kind, lo=0, hi=None):
+        """(re-)initialise the rows lo .. hi - 1 (None: all) of a buffer's tensor(s) for the envs of the same indices"""
+        if hi is None:
+            kw = {}
+        else:
+            kw = {"first": lo, "count": hi - lo}
+        if self.belief_weights:
+            self.env.belief_weights_init(*(x if hi is None else x[lo:hi] for x in t), kind, **kw)
+        else:
+            self.env.belief_init(t if hi is None else t[lo:hi], kind, **kw)
+
+    def _belief_kw(self, view):
+        """the emission keyword that shows a buffer (rows 0 .. n - 1 as _belief_for returned them)"""
+        return {"levels": view[2]} if self.belief_weights else {"belief": view}
+
+    def _belief_update(self, red, view, done, **rows):
+        if self.belief_weights:
+            self.env.belief_weights_update(red, view[0], view[1], view[2], self.sight_range, reset=done, **rows)
+        else:
+            self.env.belief_update(red, view, self.sight_range, reset=done, **rows)
 
     def _belief_for(self, buf, want, n=None):
         """The buffer's tensor for a rollout whose rows 0 .. n - 1 (None: all) track the enemies of a team of colour want[row]:
@@ -306,10 +337,10 @@ class VecMAPPOTrainer:
         if len(bad):
             cuts = np.nonzero(np.diff(bad) != 1)[0] + 1
             for run in np.split(bad, cuts):
-                self.env.belief_init(t[int(run[0]):int(run[-1]) + 1], 1, first=int(run[0]), count=len(run))
+                self._belief_init(t, 1, int(run[0]), int(run[-1]) + 1)
         colour[:n] = want
         colour[n:] = np.where(colour[n:] == -2, -2, 2)
-        return t[:n]
+        return tuple(x[:n] for x in t) if self.belief_weights else t[:n]
 
     def _hard_bot(self):
         """The hard in-kernel team of this rollout: one extra draw, made only when there is a choice."""
@@ -374,10 +405,10 @@ class VecMAPPOTrainer:
         if self.belief:
             net = mode in ("self", "pool")
             bel = self._belief_for(self._belief, int(red))
-            kw = {"belief": bel}
+            kw = self._belief_kw(bel)
             if self._belief_opp is not None:
                 obel = self._belief_for(self._belief_opp, int(not red), None if net else 0)
-                okw = {"belief": obel}
+                okw = self._belief_kw(obel)
         for t in range(T):
             env.emit_team_obs(red, self.obs_buf[t], self.merged_buf[t] if mappo_alg else None, **kw)
             if masks:
@@ -401,9 +432,9 @@ class VecMAPPOTrainer:
                 acts[:, opp_ids] = mappo.canonicalize_action(oa, not red).to(torch.int8)
             _, rew, done, info = env.step(acts, want_obs=False)
             if self.belief:
-                env.belief_update(red, bel, self.sight_range, reset=done)
+                self._belief_update(red, bel, done)
                 if net:
-                    env.belief_update(not red, obel, self.sight_range, reset=done)
+                    self._belief_update(not red, obel, done)
             cur_agent = info["agent"]
             shp = shaping_from_agent_words(self.prev_agent[:, learner_ids], cur_agent[:, learner_ids])   # [N,2] f64
             team_reward = rew[:, team] + rew[:, team]                # sum over the two learners' (identical) rewards
@@ -469,10 +500,10 @@ class VecMAPPOTrainer:
         kw = okw = self._fog                                         # keywords of the learners' / the opponent networks' emissions
         if self.belief:
             bel = self._belief_for(self._belief, red_host)
-            kw = {"belief": bel}
+            kw = self._belief_kw(bel)
             if self._belief_opp is not None:
                 obel = self._belief_for(self._belief_opp, 1 - red_host, n_net)
-                okw = {"belief": obel}
+                okw = self._belief_kw(obel)
         for t in range(T):
             env.emit_team_obs_mixed(red_u8, self.obs_buf[t], self.merged_buf[t] if mappo_alg else None, **kw)
             if masks:
@@ -496,9 +527,9 @@ class VecMAPPOTrainer:
                         mappo.set_team_columns(acts[lo:hi], red_u8[lo:hi], mappo.canonicalize_action(oa, inv_u8[lo:hi]), opponents=True)
             _, rew, done, info = env.step(acts, want_obs=False)
             if self.belief:
-                env.belief_update(red_u8, bel, self.sight_range, reset=done)
+                self._belief_update(red_u8, bel, done)
                 if n_net:
-                    env.belief_update(inv_u8, obel, self.sight_range, reset=done, first=0, count=n_net)
+                    self._belief_update(inv_u8, obel, done, first=0, count=n_net)
             cur_agent = info["agent"]
             shp = shaping_from_agent_words(mappo.team_columns(self.prev_agent, red_u8), mappo.team_columns(cur_agent, red_u8))   # [N,2] f64
             own = torch.where(red_b, rew[:, 0], rew[:, 1])
@@ -624,6 +655,8 @@ class VecMAPPOTrainer:
             extra["mix_opponents"] = 1
         if self.fog_of_war:                                              # (likewise)
             extra["fog_of_war"], extra["sight_range"] = 1, int(self.sight_range)
+        if self.belief_weights:                                          # (likewise: the policy was trained on levels, not on 0 / 1)
+            extra["belief_weights"] = 1
         torch.save({**extra, "data": self.learner.bucket.data, "ema": self.learner.ema, "exp_avg": self.learner.exp_avg,
                     "exp_avg_sq": self.learner.exp_avg_sq, "step": int(self.learner.step_count), "update": int(self.update_idx),
                     "total_updates": int(self.total_updates), "pool": list(self.opponent_pool), "gen": self.gen.get_state(),
@@ -648,6 +681,9 @@ class VecMAPPOTrainer:
             raise ValueError(f"checkpoint was written with fog_of_war={ck_fog[0]}" + (f", sight_range={ck_fog[1]}" if ck_fog[0] else "") +
                              f", this trainer has fog_of_war={self.fog_of_war}" + (f", sight_range={self.sight_range}" if self.fog_of_war else "") +
                              ": a policy trained on fogged planes is fed fogged planes")
+        if bool(ck.get("belief_weights", 0)) != self.belief_weights:      # (no key: written with the flag off)
+            raise ValueError(f"checkpoint was written with belief_weights={bool(ck.get('belief_weights', 0))}, this trainer has "
+                             f"belief_weights={self.belief_weights}: a policy trained on the levels 0 .. 16 in plane 5 is fed levels")
         if int(ck["total_updates"]) != int(self.total_updates):
             raise ValueError(f"checkpoint was written for a schedule of {ck['total_updates']} updates, this trainer has {self.total_updates}")
         self.learner.restore(ck)                                         # (weights, Adam moments, EMA and step count: the same keys)
@@ -663,16 +699,19 @@ class VecMAPPOTrainer:
         if self.belief:                                                  # the sets are not saved: a resumed run knows the board only
             for buf in (self._belief, self._belief_opp):
                 if buf is not None:
-                    self.env.belief_init(buf[0], 1)
+                    self._belief_init(buf[0], 1)
                     buf[1][:] = -2
 
 
 def evaluate_vs_bots(model, num_episodes=20, layout_file="bloxCapture", teams=("baselineTeam", "randomTeam"), length=300,
-                     device="cuda:0", fog_of_war=False, sight_range=SIGHT_RANGE, belief=False):
+                     device="cuda:0", fog_of_war=False, sight_range=SIGHT_RANGE, belief=False, belief_weights=False):
     """evaluate_vs_bots (pacman_mappo_resnet.py:293-337): a fresh env per episode against host CaptureAgent bots (red),
     the learner plays blue with argmax actions; returns (mean return, std, win rate), a win being final score < 0.
     The reference cycles through its A*/approx-Q/baseline/MCTS teams; here through the team files this build ships.
     fog_of_war: the learner's planes go through fog_obs (the host bots keep the full state the env gives them)."""
+    if belief_weights:
+        raise ValueError("evaluate_vs_bots has no belief tracker (no emission kernel runs on the host-bot path): evaluate a policy "
+                         "trained with belief_weights=True with evaluate_vectorized(belief_weights=True)")
     if belief:
         raise ValueError("evaluate_vs_bots has no belief tracker (no emission kernel runs on the host-bot path): evaluate a policy "
                          "trained with belief=True with evaluate_vectorized(belief=True)")
@@ -705,7 +744,7 @@ def evaluate_vs_bots(model, num_episodes=20, layout_file="bloxCapture", teams=("
 
 @torch.no_grad()
 def evaluate_vectorized(model, layout="bloxCapture", n_envs=1024, opponent="baseline", length=300, device="cuda:0", seed=0,
-                        autocast=True, mask_illegal=False, side="blue", fog_of_war=False, sight_range=SIGHT_RANGE, belief=False):
+                        autocast=True, mask_illegal=False, side="blue", fog_of_war=False, sight_range=SIGHT_RANGE, belief=False, belief_weights=False):
     """evaluate_vs_bots (pacman_mappo_resnet.py:293-337) for n_envs episodes at once: the learner plays blue with argmax
     actions against the in-kernel randomTeam / baselineTeam / approxQTeam (opponent "random" / "baseline" / "approxq"), one episode per env (an env stops counting at its first done).
     Returns (mean episode return of the learner team as the reference sums it, std, win rate = share with final score < 0).
@@ -715,14 +754,18 @@ def evaluate_vectorized(model, layout="bloxCapture", n_envs=1024, opponent="base
     fog_of_war: the policy sees an enemy only within sight_range of one of its two agents (pmx_emit_team_obs_mixed_fog); every
     side, blue included, then runs the emission-based loop.  The in-kernel bots keep the full state.
     belief (needs fog_of_war): plane 5 shows the tracker's sets (pmx_belief_update after every step, pmx_emit_team_obs_mixed_belief),
-    the inputs of a policy trained with the trainer's belief=True."""
+    the inputs of a policy trained with the trainer's belief=True.
+    belief_weights (needs fog_of_war and belief): plane 5 shows the weighted tracker's levels (pmx_belief_weights_update,
+    pmx_emit_team_obs_mixed_weighted), the inputs of a policy trained with the trainer's belief_weights=True."""
     if side not in ("blue", "red", "both"):
         raise ValueError(f"side must be blue, red or both, got {side!r}")
     if belief and not fog_of_war:
         raise ValueError("belief=True needs fog_of_war=True")
+    if belief_weights and not (fog_of_war and belief):
+        raise ValueError("belief_weights=True needs fog_of_war=True and belief=True")
     if side != "blue" or fog_of_war:
         return _evaluate_sides(model, layout, n_envs, opponent, length, device, seed, autocast, mask_illegal, side,
-                               int(sight_range) if fog_of_war else None, **({"belief": True} if belief else {}))
+                               int(sight_range) if fog_of_war else None, **({"belief": True} if belief else {}), **({"belief_weights": True} if belief_weights else {}))
     dev = torch.device(device)
     env = PmxVecEnv(layout, n_envs, length=length, auto_reset=True, obs_dtype="bfloat16" if autocast else "float32", device=dev,
                     seed=seed, bots=opponent in BOT_TEAMS)
@@ -759,10 +802,12 @@ def evaluate_vectorized(model, layout="bloxCapture", n_envs=1024, opponent="base
     return float(ret.mean()), float(ret.std()), float((final < 0).double().mean())
 
 
-def _evaluate_sides(model, layout, n_envs, opponent, length, device, seed, autocast, mask_illegal, side, sight_range=None, belief=False):
+def _evaluate_sides(model, layout, n_envs, opponent, length, device, seed, autocast, mask_illegal, side, sight_range=None, belief=False,
+                    belief_weights=False):
     """evaluate_vectorized with the learner's colour chosen per env: observations from pmx_emit_team_obs_mixed (canonical, so the
     policy sees a red game as it was trained to), actions and masks through the per-env frame helpers.  sight_range (an int): the
-    fog form of the emission; with belief the belief form, the sets advanced after every step."""
+    fog form of the emission; with belief the belief form, the sets advanced after every step; with belief_weights the weighted
+    forms of both."""
     dev = torch.device(device)
     env = PmxVecEnv(layout, n_envs, length=length, auto_reset=True, obs_dtype="bfloat16" if autocast else "float32", device=dev,
                     seed=seed, bots=opponent in BOT_TEAMS)
@@ -781,7 +826,10 @@ def _evaluate_sides(model, layout, n_envs, opponent, length, device, seed, autoc
     team_obs = torch.empty((n_envs, 2) + env.obs_shape, dtype=env.obs_torch_dtype, device=dev)
     ctx = torch.autocast(device_type=dev.type, dtype=torch.bfloat16) if autocast else _NullCtx()
     kw = {} if sight_range is None else {"sight_range": sight_range}
-    if belief:
+    if belief_weights:
+        bel, wts, lev = env.belief_weights_init(env.new_belief(), *env.new_belief_weights(), 0)
+        kw = {"levels": lev}
+    elif belief:
         bel = env.belief_init(env.new_belief(), 0)
         kw = {"belief": bel}
     for _ in range(length + 1):
@@ -795,7 +843,9 @@ def _evaluate_sides(model, layout, n_envs, opponent, length, device, seed, autoc
                 a = model.get_deterministic_action(lo).view(n_envs, 2)
         mappo.set_team_columns(acts, red, mappo.canonicalize_action(a, red))
         _, rew, done, info = env.step(acts, want_obs=False)
-        if belief:
+        if belief_weights:
+            env.belief_weights_update(red, bel, wts, lev, sight_range, reset=done)
+        elif belief:
             env.belief_update(red, bel, sight_range, reset=done)
         own = torch.where(red_b, rew[:, 0], rew[:, 1])
         ret += torch.where(alive, own + own, torch.zeros_like(ret))                 # sum over both learners' rewards (:328)

@@ -188,18 +188,26 @@ class PmxVecEnv:
                       _lib.stream(self.device))
         return self.obs, self.legal
 
-    def emit_team_obs(self, team_red, team_obs, merged=None, sight_range=None, belief=None):
+    def emit_team_obs(self, team_red, team_obs, merged=None, sight_range=None, belief=None, levels=None):
         """The two observations of one team for the CURRENT tick (canonicalised for red) into team_obs [N,2,8,H,W] and, if
         given, the merged critic input into merged [N,8,H,W] (pmx_emit_team_obs; pacman_mappo_resnet.py:215-229, :267-274).
         sight_range (an int): the contest's fog of war on the two learners' planes (pmx_emit_team_obs_fog; capture.py:268-292),
         an enemy shows only within that Manhattan distance of one of the team's agents; merged stays full-information.
         belief (a new_belief() tensor, in place of sight_range): plane 5 of slot j is the OR of the tracker's two sets of that
-        slot (pmx_emit_team_obs_belief); the tensor is only read."""
+        slot (pmx_emit_team_obs_belief); the tensor is only read.
+        levels (the levels tensor of new_belief_weights(), in place of both): plane 5 of slot j is levels[:, j] as numbers 0 .. 16
+        (pmx_emit_team_obs_weighted); only read."""
         N = self.n_envs
         assert team_obs.shape == (N, 2) + self.obs_shape and team_obs.dtype == self.obs_torch_dtype and team_obs.is_contiguous()
         if merged is not None:
             assert merged.shape == (N,) + self.obs_shape and merged.dtype == self.obs_torch_dtype and merged.is_contiguous()
         with torch.cuda.device(self.device):
+            if levels is not None:
+                assert sight_range is None and belief is None, "the weighted emission replaces the fog and the belief emission: pass one of the three"
+                self._check_levels(levels, N)
+                _lib.call("pmx_emit_team_obs_weighted", self.handle, int(bool(team_red)), levels.data_ptr(), team_obs.data_ptr(),
+                          merged.data_ptr() if merged is not None else None, _lib.stream(self.device))
+                return team_obs, merged
             if belief is not None:
                 assert sight_range is None, "the belief emission applies no sight rule of its own: pass one of the two"
                 self._check_belief(belief, N)
@@ -214,12 +222,12 @@ class PmxVecEnv:
                       merged.data_ptr() if merged is not None else None, _lib.stream(self.device))
         return team_obs, merged
 
-    def emit_team_obs_mixed(self, team_red, team_obs, merged=None, first=0, count=None, sight_range=None, belief=None):
+    def emit_team_obs_mixed(self, team_red, team_obs, merged=None, first=0, count=None, sight_range=None, belief=None, levels=None):
         """emit_team_obs with the learners' colour chosen per env (pmx_emit_team_obs_mixed): team_red uint8 [N], non-zero = that
         env's learners are red.  Writes rows for the envs first .. first + count - 1 (count None: up to the last env), row j for
         env first + j, into team_obs [count,2,8,H,W] and, if given, merged [count,8,H,W].  sight_range as in emit_team_obs
         (pmx_emit_team_obs_mixed_fog); belief as there too, a [count,2,2,32] tensor whose row j belongs to env first + j
-        (pmx_emit_team_obs_mixed_belief)."""
+        (pmx_emit_team_obs_mixed_belief); levels likewise, [count,2,HW] (pmx_emit_team_obs_mixed_weighted)."""
         N = self.n_envs
         first = int(first)
         count = N - first if count is None else int(count)
@@ -230,6 +238,12 @@ class PmxVecEnv:
         if count == 0:                                   # (an empty tensor has no address to pass)
             return team_obs, merged
         with torch.cuda.device(self.device):
+            if levels is not None:
+                assert sight_range is None and belief is None, "the weighted emission replaces the fog and the belief emission: pass one of the three"
+                self._check_levels(levels, count)
+                _lib.call("pmx_emit_team_obs_mixed_weighted", self.handle, team_red.data_ptr(), first, count, levels.data_ptr(),
+                          team_obs.data_ptr(), merged.data_ptr() if merged is not None else None, _lib.stream(self.device))
+                return team_obs, merged
             if belief is not None:
                 assert sight_range is None, "the belief emission applies no sight rule of its own: pass one of the two"
                 self._check_belief(belief, count)
@@ -288,6 +302,61 @@ class PmxVecEnv:
                       reset.data_ptr() if reset is not None else None, belief.data_ptr(), sonar.data_ptr() if sonar is not None else None,
                       _lib.stream(self.device))
         return belief
+
+    # -- belief weights: the exact filter that refines the sets (include/pmx.h, "Belief weights") ---------------------
+    def new_belief_weights(self, count=None):
+        """(weights, levels) for `count` envs (None: all), zeroed: weights int16 [count, 2 slots, 2 enemies, H * W] holding the
+        kernel's uint16 values bit for bit (torch has no uint16 in this binding, as belief is int32), levels uint8 [count, 2, H * W].
+        Cell y * W + x, raw coordinates.  Call belief_weights_init before the first use."""
+        n, hw = self.n_envs if count is None else int(count), self.layout.height * self.layout.width
+        return (torch.zeros((n, 2, 2, hw), dtype=torch.int16, device=self.device), torch.zeros((n, 2, hw), dtype=torch.uint8, device=self.device))
+
+    def _check_levels(self, levels, count):
+        hw = self.layout.height * self.layout.width
+        assert levels.shape == (count, 2, hw) and levels.dtype == torch.uint8 and levels.is_contiguous() and levels.device == self.device
+
+    def _check_weights(self, weights, count):
+        hw = self.layout.height * self.layout.width
+        assert weights.shape == (count, 2, 2, hw) and weights.dtype == torch.int16 and weights.is_contiguous() and weights.device == self.device
+
+    def belief_weights_init(self, belief, weights, levels, kind=0, first=0, count=None):
+        """pmx_belief_weights_init: belief_init on `belief`, the weights 65535 on the cells of each set and the levels to match."""
+        first = int(first)
+        count = self.n_envs - first if count is None else int(count)
+        if count == 0:
+            return belief, weights, levels
+        self._check_belief(belief, count)
+        self._check_weights(weights, count)
+        self._check_levels(levels, count)
+        with torch.cuda.device(self.device):
+            _lib.call("pmx_belief_weights_init", self.handle, first, count, int(kind), belief.data_ptr(), weights.data_ptr(), levels.data_ptr(),
+                      _lib.stream(self.device))
+        return belief, weights, levels
+
+    def belief_weights_update(self, team_red, belief, weights, levels, sight_range, reset=None, first=0, count=None, sonar=None):
+        """pmx_belief_weights_update, once after each step() IN PLACE OF belief_update: advances the sets exactly as belief_update
+        does and, beside them, the weights (random-walk motion, respawn prior, sight and sonar) and the levels.  Arguments as
+        belief_update."""
+        first = int(first)
+        count = self.n_envs - first if count is None else int(count)
+        if count == 0:
+            return belief, weights, levels
+        self._check_belief(belief, count)
+        self._check_weights(weights, count)
+        self._check_levels(levels, count)
+        red_dev = None
+        if isinstance(team_red, torch.Tensor):
+            assert team_red.shape == (self.n_envs,) and team_red.dtype == torch.uint8 and team_red.is_contiguous() and team_red.device == self.device
+            red_dev, team_red = team_red.data_ptr(), 0
+        if reset is not None:
+            assert reset.shape == (self.n_envs,) and reset.dtype == torch.uint8 and reset.is_contiguous() and reset.device == self.device
+        if sonar is not None:
+            assert sonar.shape == (count, 2, 2) and sonar.dtype == torch.int8 and sonar.is_contiguous() and sonar.device == self.device
+        with torch.cuda.device(self.device):
+            _lib.call("pmx_belief_weights_update", self.handle, int(bool(team_red)), red_dev, first, count, int(sight_range),
+                      reset.data_ptr() if reset is not None else None, belief.data_ptr(), sonar.data_ptr() if sonar is not None else None,
+                      weights.data_ptr(), levels.data_ptr(), _lib.stream(self.device))
+        return belief, weights, levels
 
     # -- measurement ---------------------------------------------------------------------------------------------
     def profile_begin(self, max_launches):

@@ -1,14 +1,18 @@
-"""Measurements of the belief sets (profiles/belief/README.md).
+"""Measurements of the belief sets (profiles/belief/README.md) and of the belief weights (profiles/belief_weights/README.md).
 
   times      the kernels' own durations (the start / stop events pmx_profile_begin attaches to each dispatch) of pmx_belief_update,
              pmx_emit_team_obs_belief and pmx_emit_team_obs_fog on byte planes, interleaved launch by launch in one process after a
              warm-up, and the budget a reviewer would hold the belief emission to: the fog emission's time plus the time of 512
-             more bytes per env at the fog emission's own bandwidth
+             more bytes per env at the fog emission's own bandwidth; also pmx_belief_weights_update and
+             pmx_emit_team_obs_weighted in the same rotation, with their budgets: the set update plus 10 HW more bytes per env,
+             the belief emission plus 2 HW more bytes per env, both at the fog emission's bandwidth
   tightness  over a game of in-kernel baselineTeam bots on both sides: the mean size of a hidden enemy's set and the share of
              hidden cases whose set still holds the enemy's start cell while the enemy is more than 6 cells from it (the price of
-             the respawn rule), for blue learners' second slot, whose snapshot is the end-of-tick state pmx_get_state returns
+             the respawn rule), for blue learners' second slot, whose snapshot is the end-of-tick state pmx_get_state returns;
+             and, from the weights, the mean share of a hidden enemy's total weight on its true cell against 1 / |set|, and the
+             share of the weight on the start cell in the "start cell kept, enemy more than 6 away" cases
   eval       greedy win rate of an EMA checkpoint (tools/train.py --save) against the in-kernel baselineTeam under fog, with or
-             without the belief sets (--belief)
+             without the belief sets (--belief) or with the belief weights (--belief-weights)
 """
 import argparse
 import json
@@ -30,13 +34,16 @@ def times(args):
     g = torch.Generator(device="cuda").manual_seed(2)
     n_slots = 4                                                 # rotate the outputs and the buffers
     bel = [env.belief_init(env.new_belief(), 0) for _ in range(n_slots)]
+    wb = [env.belief_weights_init(env.new_belief(), *env.new_belief_weights(), 0) for _ in range(n_slots)]
     for _ in range(8):                                          # a few ticks: valid snapshots, agents off their starts, sets of many cells
         env.step(torch.randint(0, 5, (N, 4), generator=g, device="cuda", dtype=torch.int8), want_obs=False)
         for b in bel:
             env.belief_update(False, b, s, reset=env.done)
+        for b in wb:
+            env.belief_weights_update(False, *b, s, reset=env.done)
     team = [torch.empty((N, 2) + env.obs_shape, dtype=torch.uint8, device="cuda") for _ in range(n_slots)]
     merged = [torch.empty((N,) + env.obs_shape, dtype=torch.uint8, device="cuda") for _ in range(n_slots)]
-    t = {"update": [], "emit_belief": [], "emit_fog": []}
+    t = {"update": [], "emit_belief": [], "emit_fog": [], "update_weights": [], "emit_weighted": []}
     for k in range(args.warmup + args.launches):
         i = k % n_slots
         env.profile_begin(4)
@@ -46,7 +53,13 @@ def times(args):
         env.profile_begin(4)
         env.emit_team_obs(False, team[i], merged[i], sight_range=s)
         b = env.profile_end()
+        env.profile_begin(4)
+        env.belief_weights_update(False, *wb[i], s)
+        env.emit_team_obs(False, team[i], merged[i], levels=wb[i][2])
+        c = env.profile_end()
         if k >= args.warmup:
+            t["update_weights"].append(c["rule_ms"] * 1e3)
+            t["emit_weighted"].append(c["expand_ms"] * 1e3)
             t["update"].append(a["rule_ms"] * 1e3)
             t["emit_belief"].append(a["expand_ms"] * 1e3)
             t["emit_fog"].append(b["expand_ms"] * 1e3)
@@ -63,6 +76,12 @@ def times(args):
     out["fog_emission_GBps"] = round(N * stored / (fog * 1e-6) / 1e9, 1)
     out["belief_emission_budget_us"] = round(fog * (1 + 512 / stored), 3)
     out["belief_emission_excess_us"] = round(belief - out["belief_emission_budget_us"], 3)
+    wupd, wemit = out["update_weights_us"]["mean"], out["emit_weighted_us"]["mean"]
+    per_byte = fog / stored                                     # us per byte and env at the fog emission's bandwidth
+    out["weights_update_budget_us"] = round(upd + 10 * H * W * per_byte, 3)        # reads 2 * 2 * HW, writes 4 * 2 * HW + 2 * HW more bytes
+    out["weights_update_excess_us"] = round(wupd - out["weights_update_budget_us"], 3)
+    out["weighted_emission_budget_us"] = round(belief + 2 * H * W * per_byte, 3)
+    out["weighted_emission_excess_us"] = round(wemit - out["weighted_emission_budget_us"], 3)
     print(json.dumps(out))
 
 
@@ -73,15 +92,19 @@ def tightness(args):
     lay = env.layout
     starts = lay.starts.astype(np.int64)
     codes = torch.tensor([-3, -3, -4, -4], dtype=torch.int8, device="cuda")[None].expand(N, 4).contiguous()
-    bel = env.belief_init(env.new_belief(), 0)
+    bel, wts, lev = env.belief_weights_init(env.new_belief(), *env.new_belief_weights(), 0)
     hidden = cells = with_start = 0
+    H, W = lay.height, lay.width
+    true_share = uniform_share = start_share = 0.0
     for _ in range(T):
         env.step(codes, want_obs=False)
-        env.belief_update(False, bel, s, reset=env.done)
+        env.belief_weights_update(False, bel, wts, lev, s, reset=env.done)       # (the sets come out as pmx_belief_update leaves them)
         st = env.get_state()
         pos = np.array([[[p.pos[i][0], p.pos[i][1]] for i in range(4)] for p in st], np.int64)
         live = ~env.done.cpu().numpy().astype(bool)
         words = bel[:, 1].cpu().numpy().view(np.uint32)         # blue learners' second slot: the end-of-tick state
+        q = wts[:, 1].cpu().numpy().view(np.uint16).astype(np.float64).reshape(N, 2, H, W)
+        ar = np.arange(N)
         for k, e in enumerate((0, 2)):
             d = np.minimum(np.abs(pos[:, e] - pos[:, 1]).sum(1), np.abs(pos[:, e] - pos[:, 3]).sum(1))
             h = live & (d > s)
@@ -92,19 +115,27 @@ def tightness(args):
             has = ((words[:, k, sy] >> np.uint32(sx)) & 1).astype(bool)
             away = np.abs(pos[:, e] - starts[e]).sum(1) > 6
             with_start += int((h & has & away).sum())
+            total = np.maximum(q[:, k].sum((1, 2)), 1.0)
+            true_share += float((q[ar, k, pos[:, e, 1], pos[:, e, 0]] / total)[h].sum())
+            uniform_share += float((1.0 / np.maximum((q[:, k] > 0).sum((1, 2)), 1))[h].sum())
+            start_share += float((q[:, k, sy, sx] / total)[h & has & away].sum())
     print(json.dumps({"layout": args.layout, "envs": N, "ticks": T, "sight_range": s, "hidden_cases": hidden,
                       "mean_set_cells": round(cells / max(hidden, 1), 2),
-                      "start_cell_kept_while_far_share": round(with_start / max(hidden, 1), 4)}))
+                      "start_cell_kept_while_far_share": round(with_start / max(hidden, 1), 4),
+                      "weight_share_on_true_cell": round(true_share / max(hidden, 1), 4),
+                      "uniform_share_one_over_set": round(uniform_share / max(hidden, 1), 4),
+                      "weight_share_on_start_cell_while_far": round(start_share / max(with_start, 1), 4)}))
 
 
 def evaluate(args):
     lay = pmx.get_layout(args.layout)
     model = mappo.MAPPOAgent((8, lay.height, lay.width), 5, 2).cuda()
     model.load_state_dict(torch.load(args.checkpoint, map_location="cuda", weights_only=True))
-    kw = dict(fog_of_war=True, sight_range=args.sight_range, **({"belief": True} if args.belief else {}))
+    kw = dict(fog_of_war=True, sight_range=args.sight_range, **({"belief": True} if args.belief or args.belief_weights else {}),
+              **({"belief_weights": True} if args.belief_weights else {}))
     mean, std, rate = trainer.evaluate_vectorized(model, args.layout, args.episodes, "baseline", seed=args.seed, **kw)
     print(json.dumps({"checkpoint": os.path.basename(args.checkpoint), "layout": args.layout, "episodes": args.episodes, "opponent": "baseline",
-                      "sight_range": args.sight_range, "belief": bool(args.belief), "win_rate": rate, "return_mean": round(mean, 3),
+                      "sight_range": args.sight_range, "belief": bool(args.belief or args.belief_weights), "belief_weights": bool(args.belief_weights), "win_rate": rate, "return_mean": round(mean, 3),
                       "return_std": round(std, 3)}))
 
 
@@ -119,6 +150,7 @@ if __name__ == "__main__":
     ap.add_argument("--sight-range", type=int, default=5)
     ap.add_argument("--checkpoint", default="")
     ap.add_argument("--belief", action="store_true")
+    ap.add_argument("--belief-weights", action="store_true")
     ap.add_argument("--episodes", type=int, default=1024)
     ap.add_argument("--seed", type=int, default=0)
     a = ap.parse_args()

@@ -57,6 +57,8 @@ def parser():
                                                               "team's two agents (the critic's merged input stays full); the evaluation runs under the same rule")
     ap.add_argument("--belief", action="store_true", help="with --fog-of-war: track, per hidden enemy, the set of cells it can be on (sight rule, noisy sonar "
                     "distances, motion) on the device and show the sets in plane 5 of every policy input, in training and in the evaluations")
+    ap.add_argument("--belief-weights", action="store_true", help="with --fog-of-war --belief: refine the sets by an exact Bayes filter on the device (random-walk "
+                    "motion, respawn prior, sight rule, sonar) and show its levels 0 .. 16 in plane 5 in place of the sets' 0 / 1")
     ap.add_argument("--sight-range", type=int, default=5, help="with --fog-of-war: Manhattan cells (the contest's SIGHT_RANGE is 5)")
     ap.add_argument("--graph", action="store_true", help="replay the optimizer step from a hipGraph (launch-bound minibatches, e.g. 512)")
     return ap
@@ -99,6 +101,8 @@ def main():
     fog = {"fog_of_war": True, "sight_range": args.sight_range} if args.fog_of_war else {}
     if args.belief:
         fog["belief"] = True                                    # (without --fog-of-war the trainer rejects it)
+    if args.belief_weights:
+        fog["belief_weights"] = True                            # (without --belief the trainer rejects it)
     tr = trainer.VecMAPPOTrainer(layout, args.envs, horizon=args.horizon, minibatch=args.minibatch, epochs=args.epochs, redraw_layouts=args.redraw,
                                  obs_dtype=args.obs, device=f"cuda:{local}", seed=args.seed, rank=rank, world_size=world,
                                  total_updates=args.total_updates, opponent=args.opponent, algorithm=args.algorithm, use_graph=args.graph, paired_minibatches=not args.unpaired, curriculum_scale=args.curriculum_scale,
