@@ -328,6 +328,60 @@ int pmx_emit_team_obs_weighted(pmx_env *env, int team_red, const uint8_t *levels
 int pmx_emit_team_obs_mixed_weighted(pmx_env *env, const uint8_t *team_red_dev, int32_t first, int32_t count, const uint8_t *levels_dev,
                                      void *team_obs_dev, void *merged_dev, void *stream);
 
+/* ---- Belief evidence: the public facts the observation leaves on a hidden enemy ---------------------------------------------------
+ * makeObservation (capture.py:268-292) blanks only the `configuration` of a hidden enemy: both food grids, every agent's isPacman
+ * and the team's own positions stay in what every contest agent gets.  The evidence forms of the two updates use them.  Opt-in:
+ * pmx_belief_update / pmx_belief_weights_update are unchanged, and these calls REPLACE them (same arguments plus `rules` and the
+ * evidence buffer).  All integer and exact.
+ *
+ *   rule (bit of `rules`)        fact                                          effect on enemy e_k's set in slot j
+ *   PMX_EVIDENCE_SIDE     1      isPacman of a hidden enemy (capture.py:492)   only the columns of the half it is on stay
+ *   PMX_EVIDENCE_FOOD     2      a pellet left the defended half               the mover stands where the pellet was
+ *   PMX_EVIDENCE_CONTACT  4      a death is a collision with a team agent      the start cell joins only a set that touches one
+ *
+ * Evidence buffer (caller-owned): uint32_t evidence[rows][PMX_EVIDENCE_WORDS], 144 bytes per env, row = env - first.  Words 0 .. 31:
+ * the food row words of the slot-1 snapshot at the last update (both halves; rows >= H are 0).  Word 32 / 33: P[first] / P[second]
+ * in that snapshot as x | y << 8.  Word 34: 1 if words 0 .. 33 are valid, else 0.  Word 35: 0.  pmx_belief_evidence_init zeroes
+ * the rows (valid = 0); call it wherever pmx_belief_init / pmx_belief_weights_init is called on those rows.
+ *
+ * Notation as in "Belief sets", and: half, lo_mask (columns x < half), hi_mask from the layout; mine = lo_mask for a red team (it
+ * defends x < half), hi_mask for a blue one.  The previous snapshot of slot 1 is slot 0's snapshot of this call; that of slot 0 is
+ * the evidence row, and when word 34 is 0 slot 0 has none.  F_prev, F: the food rows of the previous snapshot and of slot j's;
+ * P_prev[first], P_prev[second]: the team's two cells in the previous snapshot.
+ *
+ * The steps of the set table that change, per slot j and enemy k:
+ *   2a. food     (rules & 2, a previous snapshot exists, e_k is the enemy that moved)  E = F_prev & ~F & mine over all rows.  If E
+ *                has exactly one bit c, manhattan(c, P_prev[a_j]) > 1 and manhattan(c, start cell of a_j) > 1: after the dilation,
+ *                S &= E.  Sound because only a mover standing on a pellet removes it (capture.py:514-560) and the window holds
+ *                exactly two movers, e_k and then a_j; a returning agent can eat food on its own half (quirk Q1, SURVEY.md appendix
+ *                A), so a_j is excluded by where it can have been: one step from its previous cell, or from its start if it was
+ *                killed in between.  E with more than one bit cannot arise from play; the rule is skipped then (a hand-set state).
+ *   3. respawn   without rules & 4, or without a previous snapshot: S |= start bit, as before.  Otherwise K = the cells within
+ *                Manhattan distance 1 of P_prev[first], P_prev[second] and the start cells of first and second, and S |= start bit
+ *                only if S & K is not empty: every death is a same-cell collision with one of the team's agents (capture.py:
+ *                670-728); the stationary agent is on its previous cell, the learner one step from its previous cell or its start.
+ *   4. side      (rules & 1, hidden enemies only, after the sight and sonar cuts)  S &= ((x of P[e_k] < half) == red) ? mine : the
+ *                other half's columns.  The flag is taken from the position, not from bit 24 of the agent word, so that a state
+ *                set from outside with an inconsistent flag cannot make the set unsound.
+ *   5. store     after slot 1 the evidence row is written from slot 1's snapshot with valid = 1.  Reset rows (reset_dev[env] != 0)
+ *                get sets and readings as before; their evidence row is written from the current slot-1 snapshot too, which under
+ *                auto_reset holds the fresh game, with valid = 1.
+ * rules == 0 leaves belief and sonar_dev bit for bit as pmx_belief_update leaves them; the evidence row is still maintained.
+ * pmx_belief_weights_update_evidence applies this set rule and then the table of "Belief weights" unchanged with S' this set; the
+ * mass its step 3 puts on a start cell outside S' is dropped by its step 4.
+ * Errors as the parent call, and PMX_ERR_INVALID for rules outside 0 .. 7 or a NULL evidence_dev. */
+#define PMX_EVIDENCE_SIDE    1
+#define PMX_EVIDENCE_FOOD    2
+#define PMX_EVIDENCE_CONTACT 4
+#define PMX_EVIDENCE_WORDS   36
+int pmx_belief_evidence_init(pmx_env *env, int32_t first, int32_t count, uint32_t *evidence_dev, void *stream);
+int pmx_belief_update_evidence(pmx_env *env, int team_red, const uint8_t *team_red_dev, int32_t first, int32_t count, int32_t sight_range,
+                               int32_t rules, const uint8_t *reset_dev, uint32_t *belief_dev, int8_t *sonar_dev, uint32_t *evidence_dev,
+                               void *stream);
+int pmx_belief_weights_update_evidence(pmx_env *env, int team_red, const uint8_t *team_red_dev, int32_t first, int32_t count,
+                                       int32_t sight_range, int32_t rules, const uint8_t *reset_dev, uint32_t *belief_dev, int8_t *sonar_dev,
+                                       uint16_t *weights_dev, uint8_t *levels_dev, uint32_t *evidence_dev, void *stream);
+
 /* The layout each env is currently on (host output [n_envs]; all zeros for a single-layout handle).  Synchronises the stream. */
 int pmx_get_layout_index(pmx_env *env, int32_t *index_out, void *stream);
 

@@ -18,6 +18,7 @@ SIGHT_RANGE_MAX = 64                             # PMX_SIGHT_RANGE_MAX
 SALT_SONAR = 0x534F4E41                          # PMX_SALT_SONAR: the sonar's noise draw (pmx_belief_update)
 BELIEF_START_CELLS, BELIEF_OPEN_CELLS = 0, 1     # pmx_belief_init kinds
 BELIEF_RESPAWN_SHIFT, BELIEF_LEVELS = 7, 16      # PMX_BELIEF_RESPAWN_SHIFT, PMX_BELIEF_LEVELS (pmx_belief_weights_update)
+EVIDENCE_SIDE, EVIDENCE_FOOD, EVIDENCE_CONTACT, EVIDENCE_WORDS = 1, 2, 4, 36      # PMX_EVIDENCE_* (pmx_belief_update_evidence)
 COLSUM_BLOCKS = 512
 LN32_PARTIAL_ROWS = 2048
 ACTOR_PACK_BYTES = 297984
@@ -91,6 +92,9 @@ PROTOTYPES = [
     ("pmx_emit_team_obs_mixed_belief", C.c_int, [_VP, _VP, _I32, _I32, _VP, _VP, _VP, _VP]),
     ("pmx_belief_weights_update", C.c_int, [_VP, C.c_int, _VP, _I32, _I32, _I32, _VP, _VP, _VP, _VP, _VP, _VP]),
     ("pmx_belief_weights_init", C.c_int, [_VP, _I32, _I32, _I32, _VP, _VP, _VP, _VP]),
+    ("pmx_belief_evidence_init", C.c_int, [_VP, _I32, _I32, _VP, _VP]),
+    ("pmx_belief_update_evidence", C.c_int, [_VP, C.c_int, _VP, _I32, _I32, _I32, _I32, _VP, _VP, _VP, _VP, _VP]),
+    ("pmx_belief_weights_update_evidence", C.c_int, [_VP, C.c_int, _VP, _I32, _I32, _I32, _I32, _VP, _VP, _VP, _VP, _VP, _VP, _VP]),
     ("pmx_emit_team_obs_weighted", C.c_int, [_VP, C.c_int, _VP, _VP, _VP, _VP]),
     ("pmx_emit_team_obs_mixed_weighted", C.c_int, [_VP, _VP, _I32, _I32, _VP, _VP, _VP, _VP]),
     ("pmx_get_layout_index", C.c_int, [_VP, C.POINTER(_I32), _VP]),

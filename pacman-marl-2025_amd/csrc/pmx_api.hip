@@ -23,6 +23,8 @@ extern "C" hipError_t pmx_launch_emit_team_belief(const PmxEmitParams *p, int mi
 extern "C" hipError_t pmx_launch_belief(const PmxBeliefParams *p, int init, hipStream_t st, hipEvent_t ev0, hipEvent_t ev1);
 extern "C" hipError_t pmx_launch_emit_team_weighted(const PmxEmitParams *p, int mixed, int dtype, hipStream_t st, hipEvent_t ev0, hipEvent_t ev1);
 extern "C" hipError_t pmx_launch_belief_weights(const PmxBeliefWeightsParams *p, int init, hipStream_t st, hipEvent_t ev0, hipEvent_t ev1);
+extern "C" hipError_t pmx_launch_belief_evidence(const PmxBeliefWeightsParams *p, const PmxBeliefEvidenceParams *e, int weighted, hipStream_t st,
+                                                 hipEvent_t ev0, hipEvent_t ev1);
 extern "C" hipError_t pmx_launch_expand(const PmxExpandParams *p, int dtype, hipStream_t st, hipEvent_t ev0, hipEvent_t ev1);
 extern "C" hipError_t pmx_launch_maze(const PmxLayoutDev *lay_dev, const int16_t *cell_index_dev, int n_cells,
                                       const int8_t *cells_dev, uint8_t *dist_dev, hipStream_t st);
@@ -674,6 +676,65 @@ int pmx_belief_weights_init(pmx_env *env, int32_t first, int32_t count, int32_t 
     w.levels = levels_dev;
     HIP_TRY(pmx_launch_belief_weights(&w, 1, as_stream(stream), nullptr, nullptr));
     return PMX_OK;
+}
+
+// Belief evidence (include/pmx.h, "Belief evidence"): the parents' checks and parameter blocks, plus the evidence rows and the rules.
+int pmx_belief_evidence_init(pmx_env *env, int32_t first, int32_t count, uint32_t *evidence_dev, void *stream)
+{
+    if (!env || !evidence_dev) return fail(PMX_ERR_INVALID, "pmx_belief_evidence_init: null argument");
+    if (first < 0 || count < 0 || (int64_t)first + count > env->cfg.n_envs)
+        return fail(PMX_ERR_INVALID, "pmx_belief_evidence_init: envs %d .. %lld of %d", first, (long long)first + count - 1, env->cfg.n_envs);
+    if (count == 0) return PMX_OK;
+    HIP_TRY(hipMemsetAsync(evidence_dev, 0, (size_t)count * PMX_EVIDENCE_WORDS * sizeof(uint32_t), as_stream(stream)));   // valid = 0
+    return PMX_OK;
+}
+
+namespace {
+// what the two evidence updates share; weighted == 0: the set form, weights_dev and levels_dev unread
+int belief_update_evidence(pmx_env *env, const char *who, int weighted, int team_red, const uint8_t *team_red_dev, int32_t first, int32_t count,
+                           int32_t sight_range, int32_t rules, const uint8_t *reset_dev, uint32_t *belief_dev, int8_t *sonar_dev,
+                           uint16_t *weights_dev, uint8_t *levels_dev, uint32_t *evidence_dev, void *stream)
+{
+    PmxBeliefWeightsParams w;
+    std::memset(&w, 0, sizeof(w));
+    const int rc = fill_belief_params(env, who, first, count, belief_dev, w.b);
+    if (rc != PMX_OK) return rc;
+    if (!evidence_dev || (weighted && (!weights_dev || !levels_dev))) return fail(PMX_ERR_INVALID, "%s: null argument", who);
+    if (sight_range < 0 || sight_range > PMX_SIGHT_RANGE_MAX)
+        return fail(PMX_ERR_INVALID, "%s: sight_range %d outside 0 .. %d", who, sight_range, PMX_SIGHT_RANGE_MAX);
+    if (rules < 0 || rules > (PMX_EVIDENCE_SIDE | PMX_EVIDENCE_FOOD | PMX_EVIDENCE_CONTACT))
+        return fail(PMX_ERR_INVALID, "%s: rules %d outside 0 .. 7", who, rules);
+    if (count == 0) return PMX_OK;
+    w.b.red = team_red ? 1 : 0;
+    w.b.team_red = team_red_dev;
+    w.b.sight = sight_range;
+    w.b.reset = reset_dev;
+    w.b.sonar = sonar_dev;
+    w.weights = weights_dev;
+    w.levels = levels_dev;
+    PmxBeliefEvidenceParams e;
+    e.evidence = evidence_dev;
+    e.rules = rules;
+    hipEvent_t *ev = prof_pair(env, false);          // recorded with the rule launches, as the parents are
+    HIP_TRY(pmx_launch_belief_evidence(&w, &e, weighted, as_stream(stream), ev ? ev[0] : nullptr, ev ? ev[1] : nullptr));
+    return PMX_OK;
+}
+}  // namespace
+
+int pmx_belief_update_evidence(pmx_env *env, int team_red, const uint8_t *team_red_dev, int32_t first, int32_t count, int32_t sight_range,
+                               int32_t rules, const uint8_t *reset_dev, uint32_t *belief_dev, int8_t *sonar_dev, uint32_t *evidence_dev,
+                               void *stream)
+{
+    return belief_update_evidence(env, "pmx_belief_update_evidence", 0, team_red, team_red_dev, first, count, sight_range, rules, reset_dev,
+                                  belief_dev, sonar_dev, nullptr, nullptr, evidence_dev, stream);
+}
+
+int pmx_belief_weights_update_evidence(pmx_env *env, int team_red, const uint8_t *team_red_dev, int32_t first, int32_t count,
+                                       int32_t sight_range, int32_t rules, const uint8_t *reset_dev, uint32_t *belief_dev, int8_t *sonar_dev,
+                                       uint16_t *weights_dev, uint8_t *levels_dev, uint32_t *evidence_dev, void *stream)
+{
+    return belief_update_evidence(env, "pmx_belief_weights_update_evidence", 1, team_red, team_red_dev, first, count, sight_range, rules,
+                                  reset_dev, belief_dev, sonar_dev, weights_dev, levels_dev, evidence_dev, stream);
 }
 
 namespace {

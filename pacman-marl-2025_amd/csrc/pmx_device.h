@@ -156,6 +156,13 @@ struct PmxBeliefWeightsParams {
     uint8_t *levels;             // [count][2 slots][HW]
 };
 
+// pmx_belief_update_evidence / pmx_belief_weights_update_evidence (include/pmx.h, "Belief evidence"): the evidence kernels
+// take the parents' block, unchanged, and this one as a second argument, so that the parents' argument is the one it was
+struct PmxBeliefEvidenceParams {
+    uint32_t *evidence;          // [count][36]: food rows 0 .. 31, P[first], P[second], valid, 0 of the last update's slot-1 snapshot
+    int32_t rules;               // PMX_EVIDENCE_* bits
+};
+
 // Host-side launch tuning, changed through pmx_set_tuning: -1 = the built-in choice.
 struct PmxExpandTuning {
     int32_t alt = -1;            // alternate the sweep direction from tick to tick (0: always the same direction)

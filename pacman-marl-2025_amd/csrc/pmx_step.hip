@@ -21,6 +21,7 @@
 #include <hip/hip_ext.h>
 
 #include "pmx_device.h"
+#include "pmx_belief.h"
 
 #define PMX_MAX_H_LDS 32   // per-lane wall columns (multi-layout handles) start after room for 32 food rows
 
@@ -272,12 +273,7 @@ __device__ __forceinline__ int substep_core(Env &e, const Ctx &c, int action, bo
 #define PMX_SALT_EXPLORE 0xA511E9B3u    // approxQTeam's epsilon test
 #define PMX_BOT_HOME 1                  // flag bits returned beside the action (action | flags << 8)
 #define PMX_BOT_EXPLORED 2
-__device__ __forceinline__ uint32_t bot_hash(uint32_t key, uint32_t ticks, int agent, uint32_t salt)
-{
-    uint32_t x = key ^ (ticks * 0x85EBCA77u) ^ ((uint32_t)agent * 0xC2B2AE3Du) ^ salt;
-    x ^= x >> 16; x *= 0x7FEB352Du; x ^= x >> 15; x *= 0x846CA68Bu; x ^= x >> 16;
-    return x;
-}
+// (bot_hash, the generator itself, is in pmx_belief.h: the sonar's draw uses it too)
 // floor(x * n / 2^32)-th set action of `mask` in the reference's list order N,S,E,W,Stop
 __device__ __forceinline__ int pick_in_order(int mask, uint32_t x)
 {
@@ -1920,343 +1916,25 @@ extern "C" hipError_t pmx_launch_emit_team_weighted(const PmxEmitParams *p, int 
 }
 
 // ---------------------------------------------------------------------------------------------------------------
-// Belief sets of the hidden enemies (include/pmx.h, "Belief sets"): per learner slot and enemy the set of cells the enemy can be
-// on, one row word per board row -- the bit-board form of the tick.  One wavefront per ENV, four envs per block; lane = enemy *
-// 32 + row, so a lane owns one row word of one enemy's set and both enemies advance side by side.  The agent words of the two
-// learners' snapshots are read once (lanes 0-3 and 4-7) and broadcast as scalars; the vertical neighbours of the motion step come
-// from width-32 shuffles (row 0 takes 0 from below, row 31 0 from above; rows >= H hold 0); the sight discs and the sonar annulus
-// of a row are spans of bits around the observer's column whose half-width follows from |y - oy|, so no cell is visited.  The wave
-// reads the previous call's slot-1 sets (the 256 bytes of the env's 512-byte block that the rule uses) and writes both halves of
-// the block, 256 contiguous bytes per instruction; no LDS.
+// Belief sets and weights of the hidden enemies: the kernels are in pmx_belief.h; here the launchers of the forms without evidence
 // ---------------------------------------------------------------------------------------------------------------
-#define PMX_SALT_SONAR 0x534F4E41u      // the sonar's noise draw (include/pmx.h)
-
-// bits ox - w .. ox + w of a row, clipped to the word; none when w < 0
-__device__ __forceinline__ uint32_t belief_span(int ox, int w)
-{
-    if (w < 0) return 0u;
-    const int lo = ox - w > 0 ? ox - w : 0, hi = ox + w < 31 ? ox + w : 31;
-    return (0xFFFFFFFFu >> (31 - hi)) & (0xFFFFFFFFu << lo);
-}
-
-__device__ __forceinline__ int belief_manhattan(uint32_t a, uint32_t b)
-{
-    return abs((int)(a & 0xFF) - (int)(b & 0xFF)) + abs((int)((a >> 8) & 0xFF) - (int)((b >> 8) & 0xFF));
-}
-
-template <bool INIT>
-__global__ __launch_bounds__(PMX_BLOCK) void pmx_belief_kernel(PmxBeliefParams p)
-{
-    const int wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
-    const int lane = threadIdx.x & 63;
-    const int k = lane >> 5, y = lane & 31;
-    const long row = (long)blockIdx.x * 4 + wave;
-    if (row >= p.count) return;
-    const long env = row + p.first;
-    const int W = p.lay_W, H = p.lay_H;
-    const size_t N = (size_t)p.N;
-    const PmxLayoutDev *L = p.lay + (p.layout_idx ? p.layout_idx[env] : 0);
-    uint32_t *B = p.belief + (size_t)row * 128 + lane;          // [slot][enemy][row]: word slot * 64 + lane
-    const uint32_t open = y < H ? ~L->walls[y] & (W == 32 ? 0xFFFFFFFFu : (1u << W) - 1u) : 0u;
-    if constexpr (INIT) {
-        // kind 1: every open cell (the state was set from outside, or the colour changed).  kind 0: the start cells of agents 2 k
-        // and 2 k + 1, enemy k of a blue and of a red team -- the call takes no colour
-        const uint32_t s = p.kind != 0 ? open : ((y == L->starty[2 * k] ? 1u << L->startx[2 * k] : 0u) |
-                                                 (y == L->starty[2 * k + 1] ? 1u << L->startx[2 * k + 1] : 0u));
-        B[0] = s;
-        B[64] = s;
-        return;
-    }
-    const int red_v = p.team_red ? __builtin_amdgcn_readfirstlane((int)p.team_red[env]) : p.red;
-    const int first = red_v ? 0 : 1, second = first + 2;
-    const int e_k = (1 - first) + 2 * k;
-    const uint32_t start_bit = y == L->starty[e_k] ? 1u << L->startx[e_k] : 0u;
-    if (p.reset && __builtin_amdgcn_readfirstlane((int)p.reset[env]) != 0) {
-        B[0] = start_bit;
-        B[64] = start_bit;
-        if (p.sonar && y < 2) p.sonar[(size_t)row * 4 + y * 2 + k] = 0;       // no reading is taken at a reset
-        return;
-    }
-    if constexpr (!INIT) {
-        uint32_t S = B[64];                                     // the previous call's slot 1
-        uint32_t aw = 0;                                        // lanes 0-3: slot 0's snapshot, lanes 4-7: slot 1's
-        if (lane < 8) aw = (p.snap[lane < 4 ? first : second] + env)[(size_t)PMX_W_AGENT_A(H, lane & 3) * N] & 0xFFFFu;
-        const uint32_t ticks = p.state[(size_t)PMX_W_TICKS(H) * N + env];
-        const uint32_t key = p.seed ^ ((uint32_t)env * 0x9E3779B1u);
-#pragma unroll
-        for (int j = 0; j < 2; ++j) {
-            const int a_j = first + 2 * j;
-            // the team's two agents and the two enemies in slot j's snapshot (wave-uniform)
-            const uint32_t p0 = (uint32_t)__builtin_amdgcn_readlane((int)aw, 4 * j + 0), p1 = (uint32_t)__builtin_amdgcn_readlane((int)aw, 4 * j + 1);
-            const uint32_t p2 = (uint32_t)__builtin_amdgcn_readlane((int)aw, 4 * j + 2), p3 = (uint32_t)__builtin_amdgcn_readlane((int)aw, 4 * j + 3);
-            const uint32_t pf = first ? p1 : p0, ps = first ? p3 : p2;
-            const uint32_t pa = j ? ps : pf, pe = first ? (k ? p2 : p0) : (k ? p3 : p1);
-            // motion: the enemy whose sub-step lies between the two snapshots (Stop included).  Every lane runs the shuffles
-            const uint32_t up = __shfl_down(S, 1, 32), dn = __shfl_up(S, 1, 32);
-            if (e_k == ((a_j + 3) & 3)) S = (S | (S << 1) | (S >> 1) | (y < 31 ? up : 0u) | (y > 0 ? dn : 0u)) & open;
-            S |= start_bit;                                     // every death returns an agent to its start
-            const uint32_t h = bot_hash(key, ticks, 4 * a_j + e_k, PMX_SALT_SONAR);
-            const int r = belief_manhattan(pa, pe) + (int)(((uint64_t)h * 13u) >> 32) - 6;
-            const int df = belief_manhattan(pe, pf), ds = belief_manhattan(pe, ps);
-            if ((df < ds ? df : ds) <= p.sight) {
-                S = y == (int)(pe >> 8) ? 1u << (pe & 0xFF) : 0u;
-            } else {
-                const int dyf = abs(y - (int)(pf >> 8)), dys = abs(y - (int)(ps >> 8)), dya = abs(y - (int)(pa >> 8));
-                S &= ~(belief_span((int)(pf & 0xFF), p.sight - dyf) | belief_span((int)(ps & 0xFF), p.sight - dys));
-                S &= belief_span((int)(pa & 0xFF), r + 6 - dya) & ~belief_span((int)(pa & 0xFF), r - 7 - dya);
-            }
-            B[64 * j] = S;
-            if (p.sonar && y == 0) p.sonar[(size_t)row * 4 + j * 2 + k] = (int8_t)r;
-        }
-    }
-}
-
 // count > 0 rows, one wave each; ev0 / ev1 as in pmx_launch_emit_team (the update kernel only)
 extern "C" hipError_t pmx_launch_belief(const PmxBeliefParams *p, int init, hipStream_t st, hipEvent_t ev0, hipEvent_t ev1)
 {
     const unsigned blocks = (unsigned)(((long)p->count + 3) / 4);
-    if (init) hipLaunchKernelGGL(pmx_belief_kernel<true>, dim3(blocks), dim3(PMX_BLOCK), 0, st, *p);
-    else if (ev0) hipExtLaunchKernelGGL(pmx_belief_kernel<false>, dim3(blocks), dim3(PMX_BLOCK), 0, st, ev0, ev1, 0, *p);
-    else hipLaunchKernelGGL(pmx_belief_kernel<false>, dim3(blocks), dim3(PMX_BLOCK), 0, st, *p);
+    if (init) hipLaunchKernelGGL(pmx_belief_kernel<true>, dim3(blocks), dim3(PMX_BLOCK), 0, st, *p, BeliefEvidenceArg<false>{});
+    else if (ev0) hipExtLaunchKernelGGL(pmx_belief_kernel<false>, dim3(blocks), dim3(PMX_BLOCK), 0, st, ev0, ev1, 0, *p, BeliefEvidenceArg<false>{});
+    else hipLaunchKernelGGL(pmx_belief_kernel<false>, dim3(blocks), dim3(PMX_BLOCK), 0, st, *p, BeliefEvidenceArg<false>{});
     return hipGetLastError();
-}
-
-// ---------------------------------------------------------------------------------------------------------------
-// Belief weights (include/pmx.h, "Belief weights"): the exact Bayes filter that refines the sets -- a uint16 weight per learner
-// slot, enemy and cell, and the uint8 levels the weighted emission shows.  A kernel of its own beside pmx_belief_kernel, whose code
-// stays what it is; the two share belief_span, belief_manhattan, bot_hash and the snapshot / readlane set-up, and this one runs the
-// set rule word for word, so belief and sonar come out as pmx_belief_update leaves them.
-// One wavefront per env, four per block.  The SET part keeps the set kernel's shape (lane = enemy * 32 + row, one row word per
-// lane).  The WEIGHT part deals the cells of an enemy's board to the 32 lanes of its half, cell c = c0 + (lane & 31): global loads
-// and stores of a half are 64 / 32 consecutive bytes and an 18 x 11 board takes 7 rounds instead of 20 walks along a row with two
-// thirds of the lanes idle.  y = c / W is a multiplication by ceil(65536 / W), exact for c < 1055 and W <= 32.  A cell's open bit,
-// its four neighbours' and its bit of S' come from width-32 shuffles of the row words the set part holds, so no distance is
-// evaluated per cell.  (Keeping column, row and open bits per cell as a 16-bit word in LDS instead of recomputing them in every
-// round measured no faster: 57.4 against 54.2 us at 16 384 smallCapture envs.)  Per slot, three rounds over the cells, all lanes of the wave in step (exactly one of the two enemies moved,
-// so nothing is gained by branching on it):
-//   A  a[c] = moved ? (open ? (q[c] * R[deg(c)]) >> 16 : 0) : q[c]  into LDS (uint16 [enemy][1024], 4 KB per wave).  q is read
-//      from global: the previous call's slot 1, then the slot 0 this lane itself has just stored (same lane, same address);
-//   B  t[c] = moved ? a[c] + the a of c's open neighbours (0 on walls) : a[c];  T = sum t,  m0 = max over S' minus the start cell
-//      of max(t, 1),  t at the start cell: three reductions within the 32-lane half.  Then add = 1 + (T >> RESPAWN_SHIFT),
-//      m = max(m0, t[start] + add if the start cell is in S'), b = 32 - clz(m);
-//   C  t again (five LDS reads are cheaper than keeping 19-bit values), u, q' by the shift; q' to global, the level to the
-//      other half by one xor-32 shuffle, the larger one stored by half 0.
-// LDS operations of one wavefront execute in order; the wave fences between the rounds keep the compiler from moving them.
-// No atomics, no floating point, vector stores only.
-// ---------------------------------------------------------------------------------------------------------------
-#define PMX_BELIEF_RESPAWN_SHIFT 7      // include/pmx.h
-
-struct BeliefCell { int x, y; uint32_t me, l, r, u, d; };    // a cell's column and row, its own open bit and its neighbours'
-
-__device__ __forceinline__ BeliefCell belief_cell(int c, int W, int inv, uint32_t open)
-{
-    BeliefCell g;
-    const int yr = (c * inv) >> 16;
-    g.x = c - yr * W;                   // 0 .. W - 1 for every c < 1055
-    g.y = yr & 31;                      // (lanes past the board compute a row of no meaning; their results are not used)
-    const uint32_t om = __shfl(open, g.y, 32), ou = __shfl(open, (g.y + 31) & 31, 32), od = __shfl(open, (g.y + 1) & 31, 32);
-    g.me = (om >> g.x) & 1u;
-    g.l = g.x > 0 ? (om >> (g.x - 1)) & 1u : 0u;
-    g.r = g.x < 31 ? (om >> (g.x + 1)) & 1u : 0u;
-    g.u = g.y > 0 ? (ou >> g.x) & 1u : 0u;
-    g.d = g.y < 31 ? (od >> g.x) & 1u : 0u;
-    return g;
-}
-
-__device__ __forceinline__ uint32_t belief_half_sum(uint32_t v)
-{
-#pragma unroll
-    for (int o = 16; o > 0; o >>= 1) v += __shfl_xor(v, o, 32);
-    return v;
-}
-
-__device__ __forceinline__ uint32_t belief_half_max(uint32_t v)
-{
-#pragma unroll
-    for (int o = 16; o > 0; o >>= 1) {
-        const uint32_t w = __shfl_xor(v, o, 32);
-        v = w > v ? w : v;
-    }
-    return v;
-}
-
-template <bool INIT>
-__global__ __launch_bounds__(PMX_BLOCK) void pmx_belief_weights_kernel(PmxBeliefWeightsParams pw)
-{
-    __shared__ uint16_t contrib[4][2][1024];                    // [wave][enemy][cell]: round A's a[c]
-    const PmxBeliefParams &p = pw.b;
-    const int wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
-    const int lane = threadIdx.x & 63;
-    const int k = lane >> 5, y = lane & 31;
-    const long row = (long)blockIdx.x * 4 + wave;
-    if (row >= p.count) return;
-    const long env = row + p.first;
-    const int W = p.lay_W, H = p.lay_H, HW = H * W;
-    const int inv = (65536 + W - 1) / W;
-    const size_t N = (size_t)p.N;
-    const PmxLayoutDev *L = p.lay + (p.layout_idx ? p.layout_idx[env] : 0);
-    uint32_t *B = p.belief + (size_t)row * 128 + lane;          // [slot][enemy][row]: word slot * 64 + lane
-    uint16_t *Wt = pw.weights + ((size_t)row * 4 + k) * HW;     // [slot][enemy][cell]: slot j at + j * 2 * HW
-    uint8_t *Lv = pw.levels + (size_t)row * 2 * HW;             // [slot][cell]
-    const uint32_t open = y < H ? ~L->walls[y] & (W == 32 ? 0xFFFFFFFFu : (1u << W) - 1u) : 0u;
-
-    // both slots of both enemies: 65535 on the cells of the set S (a row word per lane), 0 elsewhere, and the levels to match
-    auto store_set = [&](uint32_t S) {
-        for (int c0 = 0; c0 < HW; c0 += 32) {
-            const int c = c0 + y;
-            const int yr = (c * inv) >> 16, xc = c - yr * W;
-            const uint32_t on = c < HW ? (__shfl(S, yr & 31, 32) >> xc) & 1u : 0u;
-            const uint32_t other = __shfl_xor(on, 32);
-            if (c < HW) {
-                Wt[c] = on ? 65535 : 0;
-                Wt[2 * HW + c] = on ? 65535 : 0;
-                if (k == 0) {
-                    Lv[c] = (on | other) ? 16 : 0;
-                    Lv[HW + c] = (on | other) ? 16 : 0;
-                }
-            }
-        }
-    };
-
-    if constexpr (INIT) {
-        const uint32_t s = p.kind != 0 ? open : ((y == L->starty[2 * k] ? 1u << L->startx[2 * k] : 0u) |
-                                                 (y == L->starty[2 * k + 1] ? 1u << L->startx[2 * k + 1] : 0u));
-        B[0] = s;
-        B[64] = s;
-        store_set(s);
-        return;
-    }
-    const int red_v = p.team_red ? __builtin_amdgcn_readfirstlane((int)p.team_red[env]) : p.red;
-    const int first = red_v ? 0 : 1, second = first + 2;
-    const int e_k = (1 - first) + 2 * k;
-    const uint32_t start_bit = y == L->starty[e_k] ? 1u << L->startx[e_k] : 0u;
-    const int start_c = L->starty[e_k] * W + L->startx[e_k];
-    if (p.reset && __builtin_amdgcn_readfirstlane((int)p.reset[env]) != 0) {
-        B[0] = start_bit;
-        B[64] = start_bit;
-        if (p.sonar && y < 2) p.sonar[(size_t)row * 4 + y * 2 + k] = 0;
-        store_set(start_bit);
-        return;
-    }
-    if constexpr (!INIT) {
-        uint16_t *A = contrib[wave][k];
-        uint32_t S = B[64];                                     // the previous call's slot 1
-        uint32_t aw = 0;                                        // lanes 0-3: slot 0's snapshot, lanes 4-7: slot 1's
-        if (lane < 8) aw = (p.snap[lane < 4 ? first : second] + env)[(size_t)PMX_W_AGENT_A(H, lane & 3) * N] & 0xFFFFu;
-        const uint32_t ticks = p.state[(size_t)PMX_W_TICKS(H) * N + env];
-        const uint32_t key = p.seed ^ ((uint32_t)env * 0x9E3779B1u);
-#pragma unroll
-        for (int j = 0; j < 2; ++j) {
-            // ---- the set rule, as in pmx_belief_kernel ----
-            const int a_j = first + 2 * j;
-            const uint32_t p0 = (uint32_t)__builtin_amdgcn_readlane((int)aw, 4 * j + 0), p1 = (uint32_t)__builtin_amdgcn_readlane((int)aw, 4 * j + 1);
-            const uint32_t p2 = (uint32_t)__builtin_amdgcn_readlane((int)aw, 4 * j + 2), p3 = (uint32_t)__builtin_amdgcn_readlane((int)aw, 4 * j + 3);
-            const uint32_t pf = first ? p1 : p0, ps = first ? p3 : p2;
-            const uint32_t pa = j ? ps : pf, pe = first ? (k ? p2 : p0) : (k ? p3 : p1);
-            const bool moved = e_k == ((a_j + 3) & 3);
-            const uint32_t up = __shfl_down(S, 1, 32), dn = __shfl_up(S, 1, 32);
-            if (moved) S = (S | (S << 1) | (S >> 1) | (y < 31 ? up : 0u) | (y > 0 ? dn : 0u)) & open;
-            S |= start_bit;
-            const uint32_t h = bot_hash(key, ticks, 4 * a_j + e_k, PMX_SALT_SONAR);
-            const int r = belief_manhattan(pa, pe) + (int)(((uint64_t)h * 13u) >> 32) - 6;
-            const int df = belief_manhattan(pe, pf), ds = belief_manhattan(pe, ps);
-            const bool seen = (df < ds ? df : ds) <= p.sight;
-            if (seen) {
-                S = y == (int)(pe >> 8) ? 1u << (pe & 0xFF) : 0u;
-            } else {
-                const int dyf = abs(y - (int)(pf >> 8)), dys = abs(y - (int)(ps >> 8)), dya = abs(y - (int)(pa >> 8));
-                S &= ~(belief_span((int)(pf & 0xFF), p.sight - dyf) | belief_span((int)(ps & 0xFF), p.sight - dys));
-                S &= belief_span((int)(pa & 0xFF), r + 6 - dya) & ~belief_span((int)(pa & 0xFF), r - 7 - dya);
-            }
-            B[64 * j] = S;
-            if (p.sonar && y == 0) p.sonar[(size_t)row * 4 + j * 2 + k] = (int8_t)r;
-
-            // ---- the weights of slot j: q = slot 1 of the previous call (j == 0) or the slot 0 just stored (j == 1) ----
-            const uint16_t *Qg = Wt + (1 - j) * 2 * HW;
-            uint16_t *Og = Wt + j * 2 * HW;
-            const int pe_c = (int)(pe >> 8) * W + (int)(pe & 0xFF);
-            // t[c] of the motion step from round A's a[]; called with c < HW only
-            auto t_of = [&](int c, const BeliefCell &g) -> uint32_t {
-                uint32_t t = A[c];
-                if (moved) {
-                    if (g.l) t += A[c - 1];
-                    if (g.r) t += A[c + 1];
-                    if (g.u) t += A[c - W];
-                    if (g.d) t += A[c + W];
-                    if (!g.me) t = 0;
-                }
-                return t;
-            };
-            __builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "wavefront");      // slot 0's round C has read a[] for the last time
-            __builtin_amdgcn_wave_barrier();
-            for (int c0 = 0; c0 < HW; c0 += 32) {                       // round A
-                const int c = c0 + y;
-                const BeliefCell g = belief_cell(c, W, inv, open);
-                if (c < HW) {
-                    const uint32_t q = Qg[c];
-                    const int deg = 1 + (int)(g.l + g.r + g.u + g.d);
-                    const uint32_t R = deg == 1 ? 65536u : (deg == 2 ? 32768u : (deg == 3 ? 21845u : (deg == 4 ? 16384u : 13107u)));
-                    A[c] = (uint16_t)(moved ? (g.me ? (q * R) >> 16 : 0u) : q);     // q <= 65535, R <= 65536: the product is below 2^32
-                }
-            }
-            __builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "wavefront");
-            __builtin_amdgcn_wave_barrier();
-            uint32_t T = 0, m0 = 0, t_start = 0;
-            for (int c0 = 0; c0 < HW; c0 += 32) {                       // round B
-                const int c = c0 + y;
-                const BeliefCell g = belief_cell(c, W, inv, open);
-                const uint32_t in_set = (__shfl(S, g.y, 32) >> g.x) & 1u;
-                if (c < HW) {
-                    const uint32_t t = t_of(c, g);                       // <= 5 * 65535
-                    T += t;                                              // <= 1024 * 5 * 65535 < 2^32
-                    if (c == start_c) t_start = t;
-                    else if (in_set) m0 = m0 > t ? m0 : (t > 1u ? t : 1u);
-                }
-            }
-            T = belief_half_sum(T);
-            m0 = belief_half_max(m0);
-            t_start = belief_half_max(t_start);
-            const uint32_t start_in = belief_half_max((S & start_bit) != 0u ? 1u : 0u);
-            const uint32_t add = 1u + (T >> PMX_BELIEF_RESPAWN_SHIFT);
-            const uint32_t u_start = start_in ? t_start + add : 0u;     // < 2^22
-            const uint32_t m = m0 > u_start ? m0 : u_start;
-            const int b = 32 - __clz((int)m);                           // 0 for an empty set
-            for (int c0 = 0; c0 < HW; c0 += 32) {                       // round C
-                const int c = c0 + y;
-                const BeliefCell g = belief_cell(c, W, inv, open);
-                const uint32_t in_set = (__shfl(S, g.y, 32) >> g.x) & 1u;
-                uint32_t lev = 0;
-                if (c < HW) {
-                    uint32_t q = 0;
-                    if (seen) {
-                        q = c == pe_c ? 65535u : 0u;
-                    } else if (in_set) {
-                        const uint32_t t = t_of(c, g);
-                        const uint32_t u = c == start_c ? t + add : (t > 1u ? t : 1u);
-                        if (b > 16) {
-                            q = u >> (b - 16);
-                            q = q > 1u ? q : 1u;
-                        } else {
-                            q = u << (16 - b);
-                        }
-                    }
-                    Og[c] = (uint16_t)q;
-                    lev = q ? 1u + (q >> 12) : 0u;
-                }
-                const uint32_t lev_o = __shfl_xor(lev, 32);
-                if (c < HW && k == 0) Lv[j * HW + c] = (uint8_t)(lev > lev_o ? lev : lev_o);
-            }
-        }
-    }
 }
 
 // count > 0 rows, one wave each; ev0 / ev1 as in pmx_launch_belief (the update kernel only)
 extern "C" hipError_t pmx_launch_belief_weights(const PmxBeliefWeightsParams *p, int init, hipStream_t st, hipEvent_t ev0, hipEvent_t ev1)
 {
     const unsigned blocks = (unsigned)(((long)p->b.count + 3) / 4);
-    if (init) hipLaunchKernelGGL(pmx_belief_weights_kernel<true>, dim3(blocks), dim3(PMX_BLOCK), 0, st, *p);
-    else if (ev0) hipExtLaunchKernelGGL(pmx_belief_weights_kernel<false>, dim3(blocks), dim3(PMX_BLOCK), 0, st, ev0, ev1, 0, *p);
-    else hipLaunchKernelGGL(pmx_belief_weights_kernel<false>, dim3(blocks), dim3(PMX_BLOCK), 0, st, *p);
+    if (init) hipLaunchKernelGGL(pmx_belief_weights_kernel<true>, dim3(blocks), dim3(PMX_BLOCK), 0, st, *p, BeliefEvidenceArg<false>{});
+    else if (ev0) hipExtLaunchKernelGGL(pmx_belief_weights_kernel<false>, dim3(blocks), dim3(PMX_BLOCK), 0, st, ev0, ev1, 0, *p, BeliefEvidenceArg<false>{});
+    else hipLaunchKernelGGL(pmx_belief_weights_kernel<false>, dim3(blocks), dim3(PMX_BLOCK), 0, st, *p, BeliefEvidenceArg<false>{});
     return hipGetLastError();
 }
 

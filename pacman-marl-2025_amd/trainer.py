@@ -133,7 +133,7 @@ class VecMAPPOTrainer:
                  device="cuda:0", seed=0, rank=0, world_size=1, process_group=None, total_updates=2000, length=300,
                  use_autocast=True, opponent="random", use_graph=False, algorithm="mappo", paired_minibatches=True, curriculum_scale=1.0,
                  env=None, redraw_layouts=False, force_collectives=False, hard_bots=("baseline",), mask_illegal=False,
-                 mix_opponents=False, fog_of_war=False, sight_range=SIGHT_RANGE, belief=False, belief_weights=False):
+                 mix_opponents=False, fog_of_war=False, sight_range=SIGHT_RANGE, belief=False, belief_weights=False, belief_evidence=False):
         self.device = torch.device(device)
         # fog_of_war: every policy input of the rollout (the learners', the self / pool opponent networks', the bootstrap
         # observation) comes from the fog entry points -- an enemy shows only within sight_range of one of the team's agents, the
@@ -160,6 +160,13 @@ class VecMAPPOTrainer:
         self.belief_weights = bool(belief_weights)
         if self.belief_weights and not (self.fog_of_war and self.belief):
             raise ValueError("belief_weights=True needs fog_of_war=True and belief=True: the weights refine the sets of the hidden enemies")
+        # belief_evidence (needs fog_of_war and belief; with or without belief_weights): every update also uses what the observation
+        # leaves public on a hidden enemy -- its side, a pellet it ate, and that it can only have died next to one of the team's
+        # agents (pmx_belief_update_evidence / pmx_belief_weights_update_evidence).  Each belief buffer gets an evidence tensor,
+        # initialised wherever the buffer is.  Plane 5 means what it meant, so nothing is saved and no flag is recorded
+        self.belief_evidence = bool(belief_evidence)
+        if self.belief_evidence and not (self.fog_of_war and self.belief):
+            raise ValueError("belief_evidence=True needs fog_of_war=True and belief=True: the evidence narrows the sets of the hidden enemies")
         self.rank, self.world_size = rank, world_size
         # hard_bots: the in-kernel teams the curriculum draws its "hard" opponent from (the reference's hard teams are
         # baselineTeam, AstarTeam and approxQTeam, pacman_mappo_resnet.py:40-47); the default keeps the draws of earlier versions
@@ -295,19 +302,21 @@ class VecMAPPOTrainer:
             v = model.value(self._net_in(merged)).float() if want_value else None
         return a.view(-1, 2), lp.view(-1, 2), v
 
-    # ---- belief buffers: [tensor, colour] with colour a host array [N]: 0 / 1 = the row tracks the enemies of a blue / red team,
+    # ---- belief buffers: [tensor, colour, evidence] with colour a host array [N]: 0 / 1 = the row tracks the enemies of a blue / red team,
     # -1 = start cells of the reset the constructor made, -2 = every open cell (both sound for either colour), 2 = the row missed
     # the last rollout's updates and is re-initialised before it is used again.  Under belief_weights the tensor is the triple
-    # (sets, weights, levels), sliced and initialised together
+    # (sets, weights, levels), sliced and initialised together.  evidence: the env's evidence rows under belief_evidence, else None
     def _new_belief(self):
         b = self.env.new_belief()
         if self.belief_weights:
             b = (b,) + tuple(self.env.new_belief_weights())
-        self._belief_init(b, 0)
-        return [b, np.full(self.N, -1, np.int8)]
+        ev = self.env.new_belief_evidence() if self.belief_evidence else None
+        self._belief_init(b, 0, evidence=ev)
+        return [b, np.full(self.N, -1, np.int8), ev]
 
-    def _belief_init(self, t, kind, lo=0, hi=None):
-        """(re-)initialise the rows lo .. hi - 1 (None: all) of a buffer's tensor(s) for the envs of the same indices"""
+    def _belief_init(self, t, kind, lo=0, hi=None, evidence=None):
+        """(re-)initialise the rows lo .. hi - 1 (None: all) of a buffer's tensor(s), and of its evidence, for the envs of the same
+        indices"""
         if hi is None:
             kw = {}
         else:
@@ -316,12 +325,20 @@ class VecMAPPOTrainer:
             self.env.belief_weights_init(*(x if hi is None else x[lo:hi] for x in t), kind, **kw)
         else:
             self.env.belief_init(t if hi is None else t[lo:hi], kind, **kw)
+        if evidence is not None:
+            self.env.belief_evidence_init(evidence if hi is None else evidence[lo:hi], **kw)
 
     def _belief_kw(self, view):
         """the emission keyword that shows a buffer (rows 0 .. n - 1 as _belief_for returned them)"""
         return {"levels": view[2]} if self.belief_weights else {"belief": view}
 
-    def _belief_update(self, red, view, done, **rows):
+    def _evidence_of(self, buf, n=None):
+        """the evidence rows that go with the rows 0 .. n - 1 of a buffer (None without belief_evidence)"""
+        return None if buf[2] is None else buf[2][:n]
+
+    def _belief_update(self, red, view, done, evidence=None, **rows):
+        if evidence is not None:
+            rows["evidence"] = evidence
         if self.belief_weights:
             self.env.belief_weights_update(red, view[0], view[1], view[2], self.sight_range, reset=done, **rows)
         else:
@@ -331,13 +348,13 @@ class VecMAPPOTrainer:
         """The buffer's tensor for a rollout whose rows 0 .. n - 1 (None: all) track the enemies of a team of colour want[row]:
         rows that tracked the other colour (or none, last rollout) are re-initialised to every open cell, run by run."""
         n = self.N if n is None else n
-        t, colour = buf
+        t, colour, evidence = buf
         want = np.broadcast_to(np.asarray(want, np.int8), (self.N,))[:n]
         bad = np.nonzero((colour[:n] >= 0) & (colour[:n] != want))[0]
         if len(bad):
             cuts = np.nonzero(np.diff(bad) != 1)[0] + 1
             for run in np.split(bad, cuts):
-                self._belief_init(t, 1, int(run[0]), int(run[-1]) + 1)
+                self._belief_init(t, 1, int(run[0]), int(run[-1]) + 1, evidence)
         colour[:n] = want
         colour[n:] = np.where(colour[n:] == -2, -2, 2)
         return tuple(x[:n] for x in t) if self.belief_weights else t[:n]
@@ -404,10 +421,10 @@ class VecMAPPOTrainer:
         kw = okw = self._fog                                         # keywords of the learners' / the opponent network's emissions
         if self.belief:
             net = mode in ("self", "pool")
-            bel = self._belief_for(self._belief, int(red))
+            bel, ev = self._belief_for(self._belief, int(red)), self._evidence_of(self._belief)
             kw = self._belief_kw(bel)
             if self._belief_opp is not None:
-                obel = self._belief_for(self._belief_opp, int(not red), None if net else 0)
+                obel, oev = self._belief_for(self._belief_opp, int(not red), None if net else 0), self._evidence_of(self._belief_opp, None if net else 0)
                 okw = self._belief_kw(obel)
         for t in range(T):
             env.emit_team_obs(red, self.obs_buf[t], self.merged_buf[t] if mappo_alg else None, **kw)
@@ -432,9 +449,9 @@ class VecMAPPOTrainer:
                 acts[:, opp_ids] = mappo.canonicalize_action(oa, not red).to(torch.int8)
             _, rew, done, info = env.step(acts, want_obs=False)
             if self.belief:
-                self._belief_update(red, bel, done)
+                self._belief_update(red, bel, done, ev)
                 if net:
-                    self._belief_update(not red, obel, done)
+                    self._belief_update(not red, obel, done, oev)
             cur_agent = info["agent"]
             shp = shaping_from_agent_words(self.prev_agent[:, learner_ids], cur_agent[:, learner_ids])   # [N,2] f64
             team_reward = rew[:, team] + rew[:, team]                # sum over the two learners' (identical) rewards
@@ -499,10 +516,10 @@ class VecMAPPOTrainer:
         lg = None
         kw = okw = self._fog                                         # keywords of the learners' / the opponent networks' emissions
         if self.belief:
-            bel = self._belief_for(self._belief, red_host)
+            bel, ev = self._belief_for(self._belief, red_host), self._evidence_of(self._belief)
             kw = self._belief_kw(bel)
             if self._belief_opp is not None:
-                obel = self._belief_for(self._belief_opp, 1 - red_host, n_net)
+                obel, oev = self._belief_for(self._belief_opp, 1 - red_host, n_net), self._evidence_of(self._belief_opp, n_net)
                 okw = self._belief_kw(obel)
         for t in range(T):
             env.emit_team_obs_mixed(red_u8, self.obs_buf[t], self.merged_buf[t] if mappo_alg else None, **kw)
@@ -527,9 +544,9 @@ class VecMAPPOTrainer:
                         mappo.set_team_columns(acts[lo:hi], red_u8[lo:hi], mappo.canonicalize_action(oa, inv_u8[lo:hi]), opponents=True)
             _, rew, done, info = env.step(acts, want_obs=False)
             if self.belief:
-                self._belief_update(red_u8, bel, done)
+                self._belief_update(red_u8, bel, done, ev)
                 if n_net:
-                    self._belief_update(inv_u8, obel, done, first=0, count=n_net)
+                    self._belief_update(inv_u8, obel, done, oev, first=0, count=n_net)
             cur_agent = info["agent"]
             shp = shaping_from_agent_words(mappo.team_columns(self.prev_agent, red_u8), mappo.team_columns(cur_agent, red_u8))   # [N,2] f64
             own = torch.where(red_b, rew[:, 0], rew[:, 1])
@@ -699,7 +716,7 @@ class VecMAPPOTrainer:
         if self.belief:                                                  # the sets are not saved: a resumed run knows the board only
             for buf in (self._belief, self._belief_opp):
                 if buf is not None:
-                    self._belief_init(buf[0], 1)
+                    self._belief_init(buf[0], 1, evidence=buf[2])
                     buf[1][:] = -2
 
 
@@ -744,7 +761,8 @@ def evaluate_vs_bots(model, num_episodes=20, layout_file="bloxCapture", teams=("
 
 @torch.no_grad()
 def evaluate_vectorized(model, layout="bloxCapture", n_envs=1024, opponent="baseline", length=300, device="cuda:0", seed=0,
-                        autocast=True, mask_illegal=False, side="blue", fog_of_war=False, sight_range=SIGHT_RANGE, belief=False, belief_weights=False):
+                        autocast=True, mask_illegal=False, side="blue", fog_of_war=False, sight_range=SIGHT_RANGE, belief=False, belief_weights=False,
+                        belief_evidence=False):
     """evaluate_vs_bots (pacman_mappo_resnet.py:293-337) for n_envs episodes at once: the learner plays blue with argmax
     actions against the in-kernel randomTeam / baselineTeam / approxQTeam (opponent "random" / "baseline" / "approxq"), one episode per env (an env stops counting at its first done).
     Returns (mean episode return of the learner team as the reference sums it, std, win rate = share with final score < 0).
@@ -756,16 +774,20 @@ def evaluate_vectorized(model, layout="bloxCapture", n_envs=1024, opponent="base
     belief (needs fog_of_war): plane 5 shows the tracker's sets (pmx_belief_update after every step, pmx_emit_team_obs_mixed_belief),
     the inputs of a policy trained with the trainer's belief=True.
     belief_weights (needs fog_of_war and belief): plane 5 shows the weighted tracker's levels (pmx_belief_weights_update,
-    pmx_emit_team_obs_mixed_weighted), the inputs of a policy trained with the trainer's belief_weights=True."""
+    pmx_emit_team_obs_mixed_weighted), the inputs of a policy trained with the trainer's belief_weights=True.
+    belief_evidence (needs fog_of_war and belief): the updates are the evidence forms, as under the trainer's belief_evidence=True."""
     if side not in ("blue", "red", "both"):
         raise ValueError(f"side must be blue, red or both, got {side!r}")
     if belief and not fog_of_war:
         raise ValueError("belief=True needs fog_of_war=True")
     if belief_weights and not (fog_of_war and belief):
         raise ValueError("belief_weights=True needs fog_of_war=True and belief=True")
+    if belief_evidence and not (fog_of_war and belief):
+        raise ValueError("belief_evidence=True needs fog_of_war=True and belief=True")
     if side != "blue" or fog_of_war:
         return _evaluate_sides(model, layout, n_envs, opponent, length, device, seed, autocast, mask_illegal, side,
-                               int(sight_range) if fog_of_war else None, **({"belief": True} if belief else {}), **({"belief_weights": True} if belief_weights else {}))
+                               int(sight_range) if fog_of_war else None, **({"belief": True} if belief else {}), **({"belief_weights": True} if belief_weights else {}),
+                               **({"belief_evidence": True} if belief_evidence else {}))
     dev = torch.device(device)
     env = PmxVecEnv(layout, n_envs, length=length, auto_reset=True, obs_dtype="bfloat16" if autocast else "float32", device=dev,
                     seed=seed, bots=opponent in BOT_TEAMS)
@@ -803,11 +825,11 @@ def evaluate_vectorized(model, layout="bloxCapture", n_envs=1024, opponent="base
 
 
 def _evaluate_sides(model, layout, n_envs, opponent, length, device, seed, autocast, mask_illegal, side, sight_range=None, belief=False,
-                    belief_weights=False):
+                    belief_weights=False, belief_evidence=False):
     """evaluate_vectorized with the learner's colour chosen per env: observations from pmx_emit_team_obs_mixed (canonical, so the
     policy sees a red game as it was trained to), actions and masks through the per-env frame helpers.  sight_range (an int): the
     fog form of the emission; with belief the belief form, the sets advanced after every step; with belief_weights the weighted
-    forms of both."""
+    forms of both; with belief_evidence the updates are the evidence forms."""
     dev = torch.device(device)
     env = PmxVecEnv(layout, n_envs, length=length, auto_reset=True, obs_dtype="bfloat16" if autocast else "float32", device=dev,
                     seed=seed, bots=opponent in BOT_TEAMS)
@@ -832,6 +854,7 @@ def _evaluate_sides(model, layout, n_envs, opponent, length, device, seed, autoc
     elif belief:
         bel = env.belief_init(env.new_belief(), 0)
         kw = {"belief": bel}
+    ekw = {"evidence": env.belief_evidence_init(env.new_belief_evidence())} if belief_evidence else {}
     for _ in range(length + 1):
         env.emit_team_obs_mixed(red, team_obs, **kw)
         lo = team_obs.view((-1,) + env.obs_shape)
@@ -844,9 +867,9 @@ def _evaluate_sides(model, layout, n_envs, opponent, length, device, seed, autoc
         mappo.set_team_columns(acts, red, mappo.canonicalize_action(a, red))
         _, rew, done, info = env.step(acts, want_obs=False)
         if belief_weights:
-            env.belief_weights_update(red, bel, wts, lev, sight_range, reset=done)
+            env.belief_weights_update(red, bel, wts, lev, sight_range, reset=done, **ekw)
         elif belief:
-            env.belief_update(red, bel, sight_range, reset=done)
+            env.belief_update(red, bel, sight_range, reset=done, **ekw)
         own = torch.where(red_b, rew[:, 0], rew[:, 1])
         ret += torch.where(alive, own + own, torch.zeros_like(ret))                 # sum over both learners' rewards (:328)
         d = done.to(torch.bool) & alive

@@ -279,11 +279,13 @@ class PmxVecEnv:
             _lib.call("pmx_belief_init", self.handle, first, count, int(kind), belief.data_ptr(), _lib.stream(self.device))
         return belief
 
-    def belief_update(self, team_red, belief, sight_range, reset=None, first=0, count=None, sonar=None):
+    def belief_update(self, team_red, belief, sight_range, reset=None, first=0, count=None, sonar=None, evidence=None, rules=7):
         """pmx_belief_update, once after each step(): advances the sets of the envs first .. first + count - 1 (row j of `belief`
         for env first + j) by the enemy's motion, the respawn rule, the sight rule and this tick's sonar readings.  team_red: a
         bool, or a uint8 [N] tensor (per env).  reset: uint8 [N], non-zero = that env was reset (pass step()'s done under
-        auto_reset): its sets go back to the start cells.  sonar: optional int8 [count, 2, 2] output of the readings."""
+        auto_reset): its sets go back to the start cells.  sonar: optional int8 [count, 2, 2] output of the readings.
+        evidence (a new_belief_evidence() tensor of `count` rows): pmx_belief_update_evidence instead, with the rule bits `rules`
+        (_lib.EVIDENCE_SIDE | EVIDENCE_FOOD | EVIDENCE_CONTACT); None makes the call made before."""
         first = int(first)
         count = self.n_envs - first if count is None else int(count)
         if count == 0:
@@ -298,6 +300,12 @@ class PmxVecEnv:
         if sonar is not None:
             assert sonar.shape == (count, 2, 2) and sonar.dtype == torch.int8 and sonar.is_contiguous() and sonar.device == self.device
         with torch.cuda.device(self.device):
+            if evidence is not None:
+                self._check_evidence(evidence, count)
+                _lib.call("pmx_belief_update_evidence", self.handle, int(bool(team_red)), red_dev, first, count, int(sight_range), int(rules),
+                          reset.data_ptr() if reset is not None else None, belief.data_ptr(), sonar.data_ptr() if sonar is not None else None,
+                          evidence.data_ptr(), _lib.stream(self.device))
+                return belief
             _lib.call("pmx_belief_update", self.handle, int(bool(team_red)), red_dev, first, count, int(sight_range),
                       reset.data_ptr() if reset is not None else None, belief.data_ptr(), sonar.data_ptr() if sonar is not None else None,
                       _lib.stream(self.device))
@@ -333,10 +341,11 @@ class PmxVecEnv:
                       _lib.stream(self.device))
         return belief, weights, levels
 
-    def belief_weights_update(self, team_red, belief, weights, levels, sight_range, reset=None, first=0, count=None, sonar=None):
+    def belief_weights_update(self, team_red, belief, weights, levels, sight_range, reset=None, first=0, count=None, sonar=None,
+                              evidence=None, rules=7):
         """pmx_belief_weights_update, once after each step() IN PLACE OF belief_update: advances the sets exactly as belief_update
         does and, beside them, the weights (random-walk motion, respawn prior, sight and sonar) and the levels.  Arguments as
-        belief_update."""
+        belief_update; with evidence, pmx_belief_weights_update_evidence."""
         first = int(first)
         count = self.n_envs - first if count is None else int(count)
         if count == 0:
@@ -353,10 +362,39 @@ class PmxVecEnv:
         if sonar is not None:
             assert sonar.shape == (count, 2, 2) and sonar.dtype == torch.int8 and sonar.is_contiguous() and sonar.device == self.device
         with torch.cuda.device(self.device):
+            if evidence is not None:
+                self._check_evidence(evidence, count)
+                _lib.call("pmx_belief_weights_update_evidence", self.handle, int(bool(team_red)), red_dev, first, count, int(sight_range),
+                          int(rules), reset.data_ptr() if reset is not None else None, belief.data_ptr(),
+                          sonar.data_ptr() if sonar is not None else None, weights.data_ptr(), levels.data_ptr(), evidence.data_ptr(),
+                          _lib.stream(self.device))
+                return belief, weights, levels
             _lib.call("pmx_belief_weights_update", self.handle, int(bool(team_red)), red_dev, first, count, int(sight_range),
                       reset.data_ptr() if reset is not None else None, belief.data_ptr(), sonar.data_ptr() if sonar is not None else None,
                       weights.data_ptr(), levels.data_ptr(), _lib.stream(self.device))
         return belief, weights, levels
+
+    # -- belief evidence: side, eaten food, contact-only respawn (include/pmx.h, "Belief evidence") --------------------
+    def new_belief_evidence(self, count=None):
+        """The evidence rows for `count` envs (None: all) that ride beside a belief buffer: int32 [count, 36], zeroed (= not valid,
+        what belief_evidence_init leaves).  Pass them as `evidence` to belief_update / belief_weights_update."""
+        return torch.zeros((self.n_envs if count is None else int(count), _lib.EVIDENCE_WORDS), dtype=torch.int32, device=self.device)
+
+    def _check_evidence(self, evidence, count):
+        assert (evidence.shape == (count, _lib.EVIDENCE_WORDS) and evidence.dtype == torch.int32 and evidence.is_contiguous()
+                and evidence.device == self.device)
+
+    def belief_evidence_init(self, evidence, first=0, count=None):
+        """pmx_belief_evidence_init on rows 0 .. count - 1 of `evidence` for the envs first .. first + count - 1: call it wherever
+        belief_init / belief_weights_init is called on those rows."""
+        first = int(first)
+        count = self.n_envs - first if count is None else int(count)
+        if count == 0:
+            return evidence
+        self._check_evidence(evidence, count)
+        with torch.cuda.device(self.device):
+            _lib.call("pmx_belief_evidence_init", self.handle, first, count, evidence.data_ptr(), _lib.stream(self.device))
+        return evidence
 
     # -- measurement ---------------------------------------------------------------------------------------------
     def profile_begin(self, max_launches):
