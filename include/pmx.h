@@ -542,7 +542,9 @@ int pmx_set_floats(float *dst_dev, const float *values, int32_t n, void *stream)
 /* clip_grad_norm_(max_norm) -> Adam (no weight decay, no amsgrad) -> EMA on flat float32 buffers of n elements, two launches
  * (pacman_mappo_resnet.py:587-595).  scratch_dev: PMX_OPT_PARTIALS doubles.  lr / (1 - beta1^t) and 1 / sqrt(1 - beta2^t) are read
  * from scalars_dev[0..1] when it is not NULL (graph replay), else taken from the host arguments.  grad_dev is left clipped;
- * norm_out_dev (may be NULL) receives the gradient's 2-norm before clipping. */
+ * norm_out_dev (may be NULL) receives the gradient's 2-norm before clipping.  The clip factor is torch.clamp(max_norm / (norm +
+ * 1e-6), max=1), NaN included: one NaN gradient element makes every gradient, moment, weight and EMA element NaN, as
+ * clip_grad_norm_ does; an infinite norm gives the factor 0 and poisons the infinite elements alone. */
 #define PMX_OPT_PARTIALS 1024
 int pmx_clip_adam_ema(float *grad_dev, float *param_dev, float *exp_avg_dev, float *exp_avg_sq_dev, float *ema_dev, int64_t n,
                       double *scratch_dev, const float *scalars_dev, float lr_over_bc1, float rsqrt_bc2, float beta1, float beta2,

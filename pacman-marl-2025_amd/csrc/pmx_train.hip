@@ -1873,6 +1873,8 @@ extern "C" int pmx_set_floats(float *dst_dev, const float *values, int32_t n, vo
 //   g *= min(1, max_norm / (norm + 1e-6));  m = m + (1 - b1)(g - m);  v = b2 v + (1 - b2) g g;
 //   p -= (lr / bc1) * m / (sqrt(v) / sqrt(bc2) + eps);  ema = decay * ema + (1 - decay) * p.
 // lr / bc1 and 1 / sqrt(bc2) come from two device floats when `sc_dev` is given (graph replay), else from the host values.
+// Non-finite gradients follow torch.clamp(max_norm / (norm + 1e-6), max=1): a NaN norm makes the clip factor NaN and with it every
+// gradient, moment, weight and EMA element; an infinite norm makes it 0, which poisons only the infinite elements (inf * 0).
 // ---------------------------------------------------------------------------------------------------------------
 __global__ __launch_bounds__(256) void pmx_sqsum_partial_kernel(const float *__restrict__ g, long n, double *__restrict__ partial)
 {
@@ -1910,7 +1912,8 @@ __global__ __launch_bounds__(256) void pmx_adam_ema_kernel(float *__restrict__ g
     __syncthreads();
     if (threadIdx.x == 0) {
         const float norm = (float)sqrt((red[0] + red[1]) + (red[2] + red[3]));
-        s_scale = fminf(max_norm / (norm + 1e-6f), 1.0f);
+        const float ratio = max_norm / (norm + 1e-6f);
+        s_scale = ratio >= 1.0f ? 1.0f : ratio;            // a NaN ratio passes through (fminf would drop it and return 1)
         if (blockIdx.x == 0 && norm_out) *norm_out = norm;
         if (blockIdx.x == 0 && report_sums6) {             // running sums of the step's reports, for the caller's averages
             if (reports5) {
