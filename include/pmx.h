@@ -76,6 +76,23 @@ enum { PMX_OBS_F32 = 0, PMX_OBS_BF16 = 1, PMX_OBS_U8 = 2 };
  * left (:324) where baselineTeam waits for none. */
 #define PMX_ACTION_APPROXQ_OFFENSE (-5)
 #define PMX_ACTION_APPROXQ_DEFENSE (-6)
+/* Fog-bound bots (pmx_set_bot_sight below).  The reference's bots are written for the contest's observation: under
+ * GameState.makeObservation (capture.py:268-292) getPosition() of a far enemy is None and the team files filter on it.  With a
+ * bot sight set, bot agent I deciding on the mid-tick state e has mate M = (I + 2) % 4 and enemies O = (I + 1) % 4, (I + 3) % 4;
+ *     seen(O) = min(manhattan(P[O], P[I]), manhattan(P[O], P[M])) <= sight_range,
+ * all positions from e and never from a successor (the reference decides visibility once, in makeObservation; a hidden enemy
+ * stays hidden in every successor generated from that observation).  Per action code:
+ *     PMX_ACTION_BASELINE_DEFENSE, PMX_ACTION_APPROXQ_DEFENSE   an enemy counts as an invader of successor t (the -1000 and the
+ *         distance term) iff t.pac[O] && seen(O)     (agents/baselineTeam.py:174, agents/approxQTeam.py:394)
+ *     PMX_ACTION_APPROXQ_OFFENSE   g counts O iff !e.pac[O] && seen(O) and O is within one step of the next cell; eats follows
+ *         g as before     (agents/approxQTeam.py:230)
+ *     PMX_ACTION_BASELINE_OFFENSE, the walk home, PMX_ACTION_RANDOM_LEGAL and every draw (salts, order, count): unchanged.
+ * The successors are the full state's.  A one-move successor can collide only with an enemy on the cell the mover reaches;
+ * that enemy is at Manhattan distance at most 1 from P[I] before the move, hence seen for every sight_range >= 1, so the
+ * transition needs no checkDeath skip (capture.py:681, :707).  That is why the range is 1 .. PMX_SIGHT_RANGE_MAX and 0 is
+ * refused.  pmx_bot_query on such a handle also reports flag bit 2 = seen(the lower-index enemy), bit 3 = seen(the higher-index
+ * enemy) for the codes -3 .. -6. */
+#define PMX_BOT_SIGHT_OFF (-1)
 
 typedef struct pmx_env pmx_env;
 
@@ -189,6 +206,13 @@ int pmx_successor(pmx_env *env, int agent, const int8_t *actions_dev, int32_t *s
  * PMX_ERR_UNSUPPORTED on a handle without enable_bots (except PMX_ACTION_RANDOM_LEGAL), PMX_ERR_INVALID for a bad agent or
  * code. */
 int pmx_bot_query(pmx_env *env, int agent, int code, double *values_dev, int8_t *action_dev, uint8_t *flags_dev, void *stream);
+
+/* Bind the in-kernel bots to the contest's sight rule (the table at PMX_BOT_SIGHT_OFF above).  A host-side field of the
+ * handle, no launch: it applies to every pmx_step, pmx_step_agent and pmx_bot_query enqueued after the call, which then run
+ * separate instantiations of their kernels.  PMX_BOT_SIGHT_OFF, the default, restores the kernels of a handle never set.
+ * sight_range is PMX_BOT_SIGHT_OFF or 1 .. PMX_SIGHT_RANGE_MAX (from 62 on nothing is hidden); PMX_ERR_INVALID for a NULL
+ * handle or any other value, PMX_ERR_UNSUPPORTED for a value other than PMX_BOT_SIGHT_OFF on a handle without enable_bots. */
+int pmx_set_bot_sight(pmx_env *env, int32_t sight_range);
 
 /* Observation planes / legal masks of the CURRENT state for all emitted agents (gymPacMan.get_Observation,
  * gymPacMan.py:195-229; GameState.getLegalActions, capture.py:101-105). */

@@ -14,6 +14,8 @@ ACTION_RANDOM_LEGAL = -2
 ACTION_BASELINE_OFFENSE, ACTION_BASELINE_DEFENSE = -3, -4
 ACTION_APPROXQ_OFFENSE, ACTION_APPROXQ_DEFENSE = -5, -6
 BOT_FLAG_HOME, BOT_FLAG_EXPLORED = 1, 2          # pmx_bot_query flags
+BOT_FLAG_SEEN_LO, BOT_FLAG_SEEN_HI = 4, 8        # ... on a handle with a bot sight: the lower / higher enemy index is seen
+BOT_SIGHT_OFF = -1                               # PMX_BOT_SIGHT_OFF (pmx_set_bot_sight)
 SIGHT_RANGE_MAX = 64                             # PMX_SIGHT_RANGE_MAX
 SALT_SONAR = 0x534F4E41                          # PMX_SALT_SONAR: the sonar's noise draw (pmx_belief_update)
 BELIEF_START_CELLS, BELIEF_OPEN_CELLS = 0, 1     # pmx_belief_init kinds
@@ -81,6 +83,7 @@ PROTOTYPES = [
     ("pmx_step_agent", C.c_int, [_VP, C.c_int, _VP, C.POINTER(StepOut), _VP]),
     ("pmx_successor", C.c_int, [_VP, C.c_int, _VP, _VP, _VP]),
     ("pmx_bot_query", C.c_int, [_VP, C.c_int, C.c_int, _VP, _VP, _VP, _VP]),
+    ("pmx_set_bot_sight", C.c_int, [_VP, _I32]),
     ("pmx_observe", C.c_int, [_VP, _VP, _VP, _VP]),
     ("pmx_emit_team_obs", C.c_int, [_VP, C.c_int, _VP, _VP, _VP]),
     ("pmx_emit_team_obs_mixed", C.c_int, [_VP, _VP, _I32, _I32, _VP, _VP, _VP]),

@@ -41,7 +41,7 @@ class QForager(CaptureAgent):
         x = int(now.pos[self.index][0]) + _STEP[code][0]
         y = int(now.pos[self.index][1]) + _STEP[code][1]
         near = sum(1 for f in self.foes
-                   if not now.pac[f] and abs(int(now.pos[f][0]) - x) + abs(int(now.pos[f][1]) - y) <= 1)
+                   if not now.pac[f] and f not in self.unseen and abs(int(now.pos[f][0]) - x) + abs(int(now.pos[f][1]) - y) <= 1)
         q = 0
         q += (1.0 / 10.0) * _Q_WEIGHTS["bias"]
         q += (near / 10.0) * _Q_WEIGHTS["ghosts"]
@@ -56,6 +56,7 @@ class QForager(CaptureAgent):
         now = gameState._state
         names = gameState.getLegalActions(self.index)                      # reference list order: N, S, E, W, Stop
         prey = set(_cells(now.food, self.height, self.prey_mask))
+        self.unseen = [f for f in self.foes if gameState.getAgentPosition(f) is None]     # hidden by makeObservation, if asked on one
         if len(prey) <= _HOME_AT:
             options = gameState._engine.successors(now, self.index)        # all five successors, one GPU round trip
             best_name, best_d = None, 9999

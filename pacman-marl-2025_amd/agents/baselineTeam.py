@@ -44,12 +44,14 @@ def _forage_score(bot, now, nxt, code):
 
 
 def _guard_score(bot, now, nxt, code):
-    """Stay a ghost (+100), -1000 per invader, close in on the nearest (-10 per step), dislike stopping and turning back."""
+    """Stay a ghost (+100), -1000 per invader the bot can see, close in on the nearest (-10 per step), dislike stopping and
+    turning back.  An enemy the observation hides (bot.unseen, set per turn) is no invader in any successor, as in the reference
+    (agents/baselineTeam.py:174); on a full state nothing is hidden."""
     me = (int(nxt.pos[bot.index][0]), int(nxt.pos[bot.index][1]))
     total = 0 if nxt.pac[bot.index] else 100
     gap = _FAR
     for foe in bot.foes:
-        if nxt.pac[foe]:
+        if nxt.pac[foe] and foe not in bot.unseen:
             total -= 1000
             gap = min(gap, bot.getMazeDistance(me, (int(nxt.pos[foe][0]), int(nxt.pos[foe][1]))))
     if gap != _FAR:
@@ -83,6 +85,7 @@ class ReflexBot(CaptureAgent):
         now = gameState._state
         names = gameState.getLegalActions(self.index)                      # reference list order: N, S, E, W, Stop
         options = gameState._engine.successors(now, self.index)            # all five successors, one GPU round trip
+        self.unseen = [f for f in self.foes if gameState.getAgentPosition(f) is None]     # hidden by makeObservation, if asked on one
         if sum(bin(int(now.food[y]) & self.prey_mask).count("1") for y in range(self.height)) <= self.home_at:
             best_name, best_d = None, 9999
             for name in names:

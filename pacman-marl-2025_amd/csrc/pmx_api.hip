@@ -58,6 +58,7 @@ struct pmx_env {
     bool snaps_valid = false;       // the three sub-step snapshots belong to the current state (set by pmx_step)
     int n_cus = 0;                  // compute units of the device: the default of the fused tick's env threshold
     int last_step_fused = 0;        // the last pmx_step ran pmx_tick_fused_kernel (pmx_last_step_fused)
+    int32_t bot_sight = 0;          // 0: the bots keep the full state; else the sight range of pmx_set_bot_sight
     std::vector<hipEvent_t> ev_rule, ev_expand;
     size_t ev_rule_used, ev_expand_used;
 };
@@ -139,6 +140,7 @@ void fill_tick_params(pmx_env *env, PmxTickParams &p, const int8_t *actions, con
     p.seed = env->cfg.seed;
     p.lay_W = env->lay.W; p.lay_H = env->lay.H; p.lay_half = env->lay.half; p.lay_n_dump = env->lay.n_dump;
     p.lo_mask = env->lay.lo_mask; p.hi_mask = env->lay.hi_mask;
+    p.bot_sight = env->bot_sight;
 }
 
 // when profiling, returns the pair of events to record around the next launch of that kernel (or nullptr)
@@ -818,6 +820,17 @@ int pmx_bot_query(pmx_env *env, int agent, int code, double *values_dev, int8_t 
     PmxTickParams p;
     fill_tick_params(env, p, nullptr, nullptr);
     HIP_TRY(pmx_launch_bot_query(&p, env->lay.H, agent, code, values_dev, action_dev, flags_dev, as_stream(stream)));
+    return PMX_OK;
+}
+
+int pmx_set_bot_sight(pmx_env *env, int32_t sight_range)
+{
+    if (!env) return fail(PMX_ERR_INVALID, "pmx_set_bot_sight: null env");
+    if (sight_range != PMX_BOT_SIGHT_OFF && (sight_range < 1 || sight_range > PMX_SIGHT_RANGE_MAX))
+        return fail(PMX_ERR_INVALID, "pmx_set_bot_sight: sight_range %d is neither PMX_BOT_SIGHT_OFF nor in 1 .. %d", sight_range, PMX_SIGHT_RANGE_MAX);
+    if (sight_range != PMX_BOT_SIGHT_OFF && !env->dist_dev)
+        return fail(PMX_ERR_UNSUPPORTED, "pmx_set_bot_sight: needs a handle created with enable_bots");
+    env->bot_sight = sight_range == PMX_BOT_SIGHT_OFF ? 0 : sight_range;
     return PMX_OK;
 }
 

@@ -78,6 +78,7 @@ struct PmxTickParams {
     float *obs;                  // [N][n_emit][8][H][W], float32 planes only
     int32_t n_emit;
     int32_t rule_blocks;
+    int32_t bot_sight;           // 0: the bots keep the full state; 1 .. PMX_SIGHT_RANGE_MAX: the sight instantiations (pmx_set_bot_sight)
 };
 
 struct PmxExpandParams {

@@ -273,6 +273,8 @@ __device__ __forceinline__ int substep_core(Env &e, const Ctx &c, int action, bo
 #define PMX_SALT_EXPLORE 0xA511E9B3u    // approxQTeam's epsilon test
 #define PMX_BOT_HOME 1                  // flag bits returned beside the action (action | flags << 8)
 #define PMX_BOT_EXPLORED 2
+#define PMX_BOT_SEEN_LO 4               // sight form only: the lower-index / higher-index enemy is seen (bot_seen)
+#define PMX_BOT_SEEN_HI 8
 // (bot_hash, the generator itself, is in pmx_belief.h: the sonar's draw uses it too)
 // floor(x * n / 2^32)-th set action of `mask` in the reference's list order N,S,E,W,Stop
 __device__ __forceinline__ int pick_in_order(int mask, uint32_t x)
@@ -370,6 +372,71 @@ __device__ __noinline__ int bot_action(const Env &e, const Ctx &c, bool defensiv
     return pick_in_order(best_mask, bot_hash(c.rng_key, e.ticks, I, PMX_SALT_BEST));
 }
 
+// bot_action under the sight rule (the handle has a bot sight, pmx_set_bot_sight).  It is bot_action's text once more and not a
+// template both share: as a wrapper around a shared always-inlined body, bot_action<I> -- four calls per env and tick on every
+// bots handle -- came out 16 .. 36 bytes shorter and differently scheduled (profiles/fog_bots/README.md).
+// `seen` bit 0 / 1 = enemy O1 / O2 is within the sight range of the deciding agent or its mate IN THE STATE e; a defender counts an enemy as an invader of a successor only when that bit is set
+// (agents/baselineTeam.py:174, agents/approxQTeam.py:394 filter on getPosition() != None, and GameState.makeObservation,
+// capture.py:268-292, hides a far enemy once, before any successor is generated).  The successors themselves stay the full
+// state's: a one-move successor can collide only with an enemy on the cell the mover reaches, that enemy is at Manhattan
+// distance <= 1 from the mover before the move and hence seen for every sight range >= 1, so substep_core needs no
+// checkDeath skip (capture.py:681, :707) -- which is why sight 0 is refused.  The offensive features read no enemy.
+template <int I>
+__device__ __noinline__ int bot_action_sight(const Env &e, const Ctx &c, bool defensive, int home_at, double *vals, int seen)
+{
+    constexpr bool RED = (I % 2) == 0;
+    constexpr int O1 = RED ? 1 : 0, O2 = O1 + 2;
+    const int legal = legal_mask(c.wl, c.wls, (int)(e.xy[I] & 0xFF), (int)(e.xy[I] >> 8));
+    const uint32_t enemy_mask = RED ? c.hi_mask : c.lo_mask;      // getFood: the other side's pellets
+    int food_left = 0;
+    for (int y = 0; y < c.H; ++y) food_left += __popc(c.fd[y * PMX_RULE_BLOCK] & enemy_mask);
+    int home_act = -1;
+    if (food_left <= home_at) {
+        home_act = bot_home_walk<I>(e, c, legal) | (PMX_BOT_HOME << 8);
+        if (!vals) return home_act;
+    }
+    int best = -(1 << 30), best_mask = 0;
+    const int order[5] = { 0, 2, 1, 3, 4 };
+    const int rev[5] = { 2, 3, 0, 1, 4 };
+    for (int k = 0; k < 5; ++k) {
+        const int a = order[k];
+        if (!((legal >> a) & 1)) continue;
+        Env t = e;
+        for (int y = 0; y < c.H; ++y) c.fd2[y * PMX_RULE_BLOCK] = c.fd[y * PMX_RULE_BLOCK];
+        Ctx c2 = c;
+        c2.fd = c.fd2;
+        bool rl; int dr = 0, db = 0;
+        substep_core<I>(t, c2, a, rl, dr, db);
+        const int my = c.cidx[(t.xy[I] >> 8) * 32 + (t.xy[I] & 0xFF)];
+        const uint8_t *drow = c.dist + (size_t)my * c.n_cells;
+        int val;
+        if (!defensive) {
+            int cnt = 0, mind = 1 << 30;
+            for (int y = 0; y < c.H; ++y) {
+                uint32_t m = c.fd2[y * PMX_RULE_BLOCK] & enemy_mask;
+                cnt += __popc(m);
+                while (m) {
+                    const int x = __ffs(m) - 1;
+                    m &= m - 1;
+                    const int d = drow[c.cidx[y * 32 + x]];
+                    mind = d < mind ? d : mind;
+                }
+            }
+            val = -100 * cnt - (cnt > 0 ? mind : 0);
+        } else {
+            int num_inv = 0, mind = 1 << 30;
+            if (t.pac[O1] && (seen & 1)) { ++num_inv; const int d = drow[c.cidx[(t.xy[O1] >> 8) * 32 + (t.xy[O1] & 0xFF)]]; mind = d < mind ? d : mind; }
+            if (t.pac[O2] && (seen & 2)) { ++num_inv; const int d = drow[c.cidx[(t.xy[O2] >> 8) * 32 + (t.xy[O2] & 0xFF)]]; mind = d < mind ? d : mind; }
+            val = -1000 * num_inv + 100 * (t.pac[I] ? 0 : 1) - (num_inv > 0 ? 10 * mind : 0) - (a == 4 ? 100 : 0) - (a == rev[e.dir[I]] ? 2 : 0);
+        }
+        if (val > best) { best = val; best_mask = 1 << a; }
+        else if (val == best) best_mask |= 1 << a;
+        if (vals) vals[a] = (double)val;
+    }
+    if (home_act >= 0) return home_act;
+    return pick_in_order(best_mask, bot_hash(c.rng_key, e.ticks, I, PMX_SALT_BEST));
+}
+
 // agents/approxQTeam.py:49-110, 194-292 ApproxQLearningOffense evaluated in the kernel (action code -5): a linear Q function
 // of (state, action) with the team file's fixed weights, epsilon-greedy with epsilon 0.1, no learning.  Nothing is generated:
 // the features read the agent's cell plus the action vector.  The Q value is summed in float64 in the insertion order of the
@@ -377,8 +444,10 @@ __device__ __noinline__ int bot_action(const Env &e, const Ctx &c, bool defensiv
 // own, so that it equals the reference's Python float bit for bit.  Three draws (include/pmx.h): explore iff
 // h(PMX_SALT_EXPLORE) < ceil(2^32 / 10); exploring plays random_legal's action; otherwise the best set is drawn from as
 // bot_action draws.  With at most two pellets left the agent walks home (:77-86).  Returns action | flags << 8.
-template <int I>
-__device__ __noinline__ int approxq_action(const Env &e, const Ctx &c, double *vals)
+// SIGHT: a ghost is counted only when its `seen` bit is set (agents/approxQTeam.py:230 filters on getPosition() != None); at
+// a sight range >= 2 a ghost within one step of the next cell is always seen, so the rule bites at sight 1 only.
+template <int I, bool SIGHT>
+__device__ __forceinline__ int approxq_action_impl(const Env &e, const Ctx &c, double *vals, int seen)
 {
     constexpr bool RED = (I % 2) == 0;
     constexpr int O1 = RED ? 1 : 0, O2 = O1 + 2;
@@ -406,8 +475,8 @@ __device__ __noinline__ int approxq_action(const Env &e, const Ctx &c, double *v
         // ghosts one step away: opponents that are not Pacman (scared or not) on the cell or next to it (Actions.getLegalNeighbors
         // of the ghost's cell includes the cell itself; the next cell is open, so no wall test is left)
         int g = 0;
-        if (!e.pac[O1]) g += (abs((int)(e.xy[O1] & 0xFF) - nx) + abs((int)(e.xy[O1] >> 8) - ny)) <= 1;
-        if (!e.pac[O2]) g += (abs((int)(e.xy[O2] & 0xFF) - nx) + abs((int)(e.xy[O2] >> 8) - ny)) <= 1;
+        if (!e.pac[O1] && (!SIGHT || (seen & 1))) g += (abs((int)(e.xy[O1] & 0xFF) - nx) + abs((int)(e.xy[O1] >> 8) - ny)) <= 1;
+        if (!e.pac[O2] && (!SIGHT || (seen & 2))) g += (abs((int)(e.xy[O2] & 0xFF) - nx) + abs((int)(e.xy[O2] >> 8) - ny)) <= 1;
         const bool eats = g == 0 && (((c.fd[ny * PMX_RULE_BLOCK] & enemy_mask) >> nx) & 1u);
         // closestFood's breadth-first search = the smallest entry of the next cell's row of the distance matrix
         const uint8_t *drow = c.dist + (size_t)c.cidx[ny * 32 + nx] * c.n_cells;
@@ -435,12 +504,44 @@ __device__ __noinline__ int approxq_action(const Env &e, const Ctx &c, double *v
         return random_legal(legal, c.rng_key, e.ticks, I) | (PMX_BOT_EXPLORED << 8);
     return pick_in_order(best_mask, bot_hash(c.rng_key, e.ticks, I, PMX_SALT_BEST));
 }
+template <int I>
+__device__ __noinline__ int approxq_action(const Env &e, const Ctx &c, double *vals)
+{
+    return approxq_action_impl<I, false>(e, c, vals, 3);
+}
+template <int I>
+__device__ __noinline__ int approxq_action_sight(const Env &e, const Ctx &c, double *vals, int seen)
+{
+    return approxq_action_impl<I, true>(e, c, vals, seen);
+}
+
+// The contest's sight rule for bot agent I (GameState.makeObservation, capture.py:268-292): enemy O is seen iff it is within
+// `sight` Manhattan cells of I or of I's mate.  Bit 0: enemy O1 (the lower index), bit 1: enemy O2.  Four distances on the
+// state the decision starts from, in registers; a hidden enemy stays hidden in every successor of that decision.
+template <int I>
+__device__ __forceinline__ int bot_seen(const Env &e, int sight)
+{
+    constexpr int O1 = (I % 2) == 0 ? 1 : 0, O2 = O1 + 2, M = (I + 2) % 4;
+    const int xi = (int)(e.xy[I] & 0xFF), yi = (int)(e.xy[I] >> 8), xm = (int)(e.xy[M] & 0xFF), ym = (int)(e.xy[M] >> 8);
+    const int x1 = (int)(e.xy[O1] & 0xFF), y1 = (int)(e.xy[O1] >> 8), x2 = (int)(e.xy[O2] & 0xFF), y2 = (int)(e.xy[O2] >> 8);
+    const int d1 = min(abs(x1 - xi) + abs(y1 - yi), abs(x1 - xm) + abs(y1 - ym));
+    const int d2 = min(abs(x2 - xi) + abs(y2 - yi), abs(x2 - xm) + abs(y2 - ym));
+    return (int)(d1 <= sight) | ((int)(d2 <= sight) << 1);
+}
 
 // what bot `code` (-2 .. -6) plays for agent I in state e, as action | flags << 8; the tick (vals NULL) and pmx_bot_query go
-// through this one function
-template <int I>
-__device__ __forceinline__ int bot_decide(const Env &e, const Ctx &c, int code, double *vals)
+// through this one function.  SIGHT: the sight form, which also reports the two seen bits as flags PMX_BOT_SEEN_LO / _HI.
+template <int I, bool SIGHT = false>
+__device__ __forceinline__ int bot_decide(const Env &e, const Ctx &c, int code, double *vals, int sight = 0)
 {
+    if constexpr (SIGHT) {
+        const int seen = bot_seen<I>(e, sight);
+        int r;
+        if (code == -5) r = approxq_action_sight<I>(e, c, vals, seen);
+        else if (code == -3) r = bot_action<I>(e, c, false, 0, vals);
+        else r = bot_action_sight<I>(e, c, true, code == -6 ? 2 : 0, vals, seen);
+        return r | (seen << 10);
+    }
     if (code == -5) return approxq_action<I>(e, c, vals);
     if (code == -3) return bot_action<I>(e, c, false, 0, vals);
     return bot_action<I>(e, c, true, code == -6 ? 2 : 0, vals);
@@ -448,27 +549,29 @@ __device__ __forceinline__ int bot_decide(const Env &e, const Ctx &c, int code, 
 
 // BOTS: the handle was created with pmx_config.enable_bots; only that kernel variant carries the bot code (action codes
 // -3 .. -6; it costs registers and a stack frame for the agent state: +3 us per tick on 16 k envs even when no bot code is used)
-template <int I, bool BOTS>
-__device__ __forceinline__ int substep(Env &e, const Ctx &c, int action, bool &req_legal, int &d_red, int &d_blue)
+// BOTS == 2: the bots variant with the sight rule (PmxTickParams::bot_sight, a separate instantiation of every kernel that
+// carries bot code, so that handles without a sight run the code they ran before)
+template <int I, int BOTS>
+__device__ __forceinline__ int substep(Env &e, const Ctx &c, int action, bool &req_legal, int &d_red, int &d_blue, int sight = 0)
 {
     if (action == -2) action = random_legal(legal_mask(c.wl, c.wls, (int)(e.xy[I] & 0xFF), (int)(e.xy[I] >> 8)), c.rng_key, e.ticks, I);
     if constexpr (BOTS) {
-        if (action <= -3 && action >= -6 && c.dist) action = bot_decide<I>(e, c, action, nullptr) & 0xFF;
+        if (action <= -3 && action >= -6 && c.dist) action = bot_decide<I, BOTS == 2>(e, c, action, nullptr, sight) & 0xFF;
     }
     return substep_core<I>(e, c, action, req_legal, d_red, d_blue);
 }
 
 // One iteration of the loop gymPacMan.py:149-169 for agent I: shaped reward (from the successor, which is what the
 // reference's shadow successor equals) + the transition itself.
-template <int I, bool BOTS>
-__device__ __forceinline__ void tick_substep(Env &e, Acc &a, const Ctx &c, int action)
+template <int I, int BOTS>
+__device__ __forceinline__ void tick_substep(Env &e, Acc &a, const Ctx &c, int action, int sight = 0)
 {
     constexpr bool RED = (I % 2) == 0;
     constexpr int O1 = RED ? 1 : 0, O2 = O1 + 2;
     const int pac1 = e.pac[O1], pac2 = e.pac[O2];
     bool req_legal;
     int d_red = 0, d_blue = 0;
-    const int sc = substep<I, BOTS>(e, c, action, req_legal, d_red, d_blue);
+    const int sc = substep<I, BOTS>(e, c, action, req_legal, d_red, d_blue, sight);
     double r = RED ? a.red_r : a.blue_r;
     if (RED) {                                                            // gymPacMan.py:233-242
         if (d_red > 0) r += 1.0;
@@ -769,44 +872,57 @@ __device__ __forceinline__ void write_walls(const PmxTickParams &p);    // defin
 // Blocks rule_blocks .. gridDim.x - 1 (present when pmx_step splits the observation, see pmx_launch_rule) do not run the rules:
 // they store the wall plane of the observation, the only plane bytes that do not depend on this tick's rules, while the rule
 // blocks wait on their state loads and HBM would otherwise idle.  The branch is block-uniform; no block waits for another.
+// The body is a macro, not a function the two kernels share: behind a function (by reference or by value, always inlined) the
+// compiler schedules the eight existing instantiations differently (same registers, 40 .. 160 bytes more code each,
+// profiles/fog_bots/README.md); as text in the kernel they keep their instruction streams.
+// BOTS: 0 no bot code, 1 the bots variant, 2 the bots variant under the sight rule (p.bot_sight).
+#define PMX_RULE_KERNEL_BODY(BOTS)                                                                                                  \
+    extern __shared__ uint32_t lds[];                                                                                               \
+    if ((int)blockIdx.x >= p.rule_blocks) {                                                                                         \
+        write_walls(p);                                                                                                             \
+        return;                                                                                                                     \
+    }                                                                                                                               \
+    const int env = blockIdx.x * PMX_RULE_BLOCK + threadIdx.x;                                                                      \
+    const bool live = env < p.N;                                                                                                    \
+    RawEnv raw;                                                                                                                     \
+    uint32_t rows[HB];                                                                                                              \
+    uint32_t av = 0;                                                                                                                \
+    if (live) {                                                                                                                     \
+        load_env_issue<HB>(raw, rows, p.state, p.N, env, p.lay_H);                                                                  \
+        av = reinterpret_cast<const uint32_t *>(p.actions)[env];   /* 4 int8 actions */                                             \
+    }                                                                                                                               \
+    Ctx c = make_ctx(p, lds);                                                                                                       \
+    if (!live) return;                                                                                                              \
+    Env e;                                                                                                                          \
+    load_env_commit<HB>(e, c, raw, rows);                                                                                           \
+    Acc a = { 0.0, 0.0, 0, 0, 0, 0, 0 };                                                                                            \
+    count_food<HB>(a, c, rows);                                                                                                     \
+    const size_t snap_sz = (size_t)PMX_SNAP_WORDS(c.H) * p.N;                                                                       \
+    const bool wide = (p.N & (PMX_RULE_BLOCK - 1)) == 0;   /* every wave is full: the 16-byte store path (store_words_wide) */      \
+    tick_substep<0, BOTS>(e, a, c, (int)(int8_t)(av & 0xFF), p.bot_sight);                                                          \
+    if (wide) store_snapshot_wide<HB>(e, c, p.snap, p.N); else store_snapshot<HB>(e, c, p.snap, p.N, env);                          \
+    tick_substep<1, BOTS>(e, a, c, (int)(int8_t)((av >> 8) & 0xFF), p.bot_sight);                                                   \
+    if (wide) store_snapshot_wide<HB>(e, c, p.snap + snap_sz, p.N); else store_snapshot<HB>(e, c, p.snap + snap_sz, p.N, env);      \
+    tick_substep<2, BOTS>(e, a, c, (int)(int8_t)((av >> 16) & 0xFF), p.bot_sight);                                                  \
+    if (wide) store_snapshot_wide<HB>(e, c, p.snap + 2 * snap_sz, p.N); else store_snapshot<HB>(e, c, p.snap + 2 * snap_sz, p.N, env); \
+    tick_substep<3, BOTS>(e, a, c, (int)(int8_t)((av >> 24) & 0xFF), p.bot_sight);                                                  \
+    tick_finish<HB>(e, a, c, p, env, true);                                                                                         \
+    if (wide) store_env_wide<HB>(e, c, p.state, p.N); else store_env<HB>(e, c, p.state, p.N, env);
+
 template <bool BOTS, int HB>
 __global__ __launch_bounds__(PMX_RULE_BLOCK) void pmx_rule_kernel(PmxTickParams p)
 {
-    extern __shared__ uint32_t lds[];
-    if ((int)blockIdx.x >= p.rule_blocks) {
-        write_walls(p);
-        return;
-    }
-    const int env = blockIdx.x * PMX_RULE_BLOCK + threadIdx.x;
-    const bool live = env < p.N;
-    RawEnv raw;
-    uint32_t rows[HB];
-    uint32_t av = 0;
-    if (live) {
-        load_env_issue<HB>(raw, rows, p.state, p.N, env, p.lay_H);
-        av = reinterpret_cast<const uint32_t *>(p.actions)[env];   // 4 int8 actions
-    }
-    Ctx c = make_ctx(p, lds);
-    if (!live) return;
-    Env e;
-    load_env_commit<HB>(e, c, raw, rows);
-    Acc a = { 0.0, 0.0, 0, 0, 0, 0, 0 };
-    count_food<HB>(a, c, rows);
-    const size_t snap_sz = (size_t)PMX_SNAP_WORDS(c.H) * p.N;
-    const bool wide = (p.N & (PMX_RULE_BLOCK - 1)) == 0;          // every wave is full: the 16-byte store path (store_words_wide)
-    tick_substep<0, BOTS>(e, a, c, (int)(int8_t)(av & 0xFF));
-    if (wide) store_snapshot_wide<HB>(e, c, p.snap, p.N); else store_snapshot<HB>(e, c, p.snap, p.N, env);
-    tick_substep<1, BOTS>(e, a, c, (int)(int8_t)((av >> 8) & 0xFF));
-    if (wide) store_snapshot_wide<HB>(e, c, p.snap + snap_sz, p.N); else store_snapshot<HB>(e, c, p.snap + snap_sz, p.N, env);
-    tick_substep<2, BOTS>(e, a, c, (int)(int8_t)((av >> 16) & 0xFF));
-    if (wide) store_snapshot_wide<HB>(e, c, p.snap + 2 * snap_sz, p.N); else store_snapshot<HB>(e, c, p.snap + 2 * snap_sz, p.N, env);
-    tick_substep<3, BOTS>(e, a, c, (int)(int8_t)((av >> 24) & 0xFF));
-    tick_finish<HB>(e, a, c, p, env, true);
-    if (wide) store_env_wide<HB>(e, c, p.state, p.N); else store_env<HB>(e, c, p.state, p.N, env);
+    PMX_RULE_KERNEL_BODY(BOTS ? 1 : 0)
+}
+// the bots variant under the sight rule (handles with pmx_set_bot_sight)
+template <int HB>
+__global__ __launch_bounds__(PMX_RULE_BLOCK) void pmx_rule_sight_kernel(PmxTickParams p)
+{
+    PMX_RULE_KERNEL_BODY(2)
 }
 
 // pmx_step_agent: one sub-step; the accumulators of the open tick travel through the state words.
-template <int I, bool BOTS>
+template <int I, int BOTS>
 __device__ __forceinline__ void rule_agent_body(const PmxTickParams &p, uint32_t *lds)
 {
     Ctx c = make_ctx(p, lds);
@@ -824,7 +940,7 @@ __device__ __forceinline__ void rule_agent_body(const PmxTickParams &p, uint32_t
 #pragma unroll
     for (int i = 0; i < 4; ++i)   // sub-steps not yet taken report the current state
         e.self_after[i] = e.xy[i] | ((uint32_t)e.carry[i] << 16);
-    tick_substep<I, BOTS>(e, a, c, (int)p.actions[env]);
+    tick_substep<I, BOTS>(e, a, c, (int)p.actions[env], p.bot_sight);
     if (p.agent_out) p.agent_out[4 * (size_t)env + I] = e.self_after[I];
     if (I == 3) {
         tick_finish(e, a, c, p, env, false);
@@ -865,7 +981,7 @@ extern "C" __global__ __launch_bounds__(PMX_RULE_BLOCK) void pmx_successor_kerne
 
 // pmx_bot_query: what bot `code` computes for agent I on the current state and what it would play now; nothing is written back.
 // It calls the very device functions the tick calls (bot_decide, random_legal).
-template <int I>
+template <int I, bool SIGHT>
 __device__ __forceinline__ void bot_query_body(const PmxTickParams &p, uint32_t *lds, int code, double *values, int8_t *action,
                                                uint8_t *flags)
 {
@@ -878,7 +994,7 @@ __device__ __forceinline__ void bot_query_body(const PmxTickParams &p, uint32_t 
     double v[5] = { 0.0, 0.0, 0.0, 0.0, 0.0 };
     int r;
     if (code == -2 || !c.dist) r = random_legal(legal, c.rng_key, e.ticks, I);      // (the host refuses other codes without bots)
-    else r = bot_decide<I>(e, c, code, v);
+    else r = bot_decide<I, SIGHT>(e, c, code, v, p.bot_sight);
     if (values) {
 #pragma unroll
         for (int a = 0; a < 5; ++a) values[5 * (size_t)env + a] = ((legal >> a) & 1) ? v[a] : __longlong_as_double(0x7FF8000000000000LL);
@@ -892,10 +1008,22 @@ extern "C" __global__ __launch_bounds__(PMX_RULE_BLOCK) void pmx_bot_query_kerne
 {
     extern __shared__ uint32_t lds[];
     switch (agent) {   // wave-uniform
-    case 0: bot_query_body<0>(p, lds, code, values, action, flags); break;
-    case 1: bot_query_body<1>(p, lds, code, values, action, flags); break;
-    case 2: bot_query_body<2>(p, lds, code, values, action, flags); break;
-    default: bot_query_body<3>(p, lds, code, values, action, flags); break;
+    case 0: bot_query_body<0, false>(p, lds, code, values, action, flags); break;
+    case 1: bot_query_body<1, false>(p, lds, code, values, action, flags); break;
+    case 2: bot_query_body<2, false>(p, lds, code, values, action, flags); break;
+    default: bot_query_body<3, false>(p, lds, code, values, action, flags); break;
+    }
+}
+// its twin for handles with a bot sight: the flags also carry PMX_BOT_SEEN_LO / _HI
+extern "C" __global__ __launch_bounds__(PMX_RULE_BLOCK) void pmx_bot_query_sight_kernel(PmxTickParams p, int agent, int code, double *values,
+                                                                                        int8_t *action, uint8_t *flags)
+{
+    extern __shared__ uint32_t lds[];
+    switch (agent) {   // wave-uniform
+    case 0: bot_query_body<0, true>(p, lds, code, values, action, flags); break;
+    case 1: bot_query_body<1, true>(p, lds, code, values, action, flags); break;
+    case 2: bot_query_body<2, true>(p, lds, code, values, action, flags); break;
+    default: bot_query_body<3, true>(p, lds, code, values, action, flags); break;
     }
 }
 
@@ -904,10 +1032,20 @@ __global__ __launch_bounds__(PMX_RULE_BLOCK) void pmx_rule_agent_kernel(PmxTickP
 {
     extern __shared__ uint32_t lds[];
     switch (agent) {   // wave-uniform
-    case 0: rule_agent_body<0, BOTS>(p, lds); break;
-    case 1: rule_agent_body<1, BOTS>(p, lds); break;
-    case 2: rule_agent_body<2, BOTS>(p, lds); break;
-    default: rule_agent_body<3, BOTS>(p, lds); break;
+    case 0: rule_agent_body<0, BOTS ? 1 : 0>(p, lds); break;
+    case 1: rule_agent_body<1, BOTS ? 1 : 0>(p, lds); break;
+    case 2: rule_agent_body<2, BOTS ? 1 : 0>(p, lds); break;
+    default: rule_agent_body<3, BOTS ? 1 : 0>(p, lds); break;
+    }
+}
+__global__ __launch_bounds__(PMX_RULE_BLOCK) void pmx_rule_agent_sight_kernel(PmxTickParams p, int agent)
+{
+    extern __shared__ uint32_t lds[];
+    switch (agent) {   // wave-uniform
+    case 0: rule_agent_body<0, 2>(p, lds); break;
+    case 1: rule_agent_body<1, 2>(p, lds); break;
+    case 2: rule_agent_body<2, 2>(p, lds); break;
+    default: rule_agent_body<3, 2>(p, lds); break;
     }
 }
 
@@ -1971,7 +2109,19 @@ extern "C" hipError_t pmx_launch_rule(const PmxTickParams *p, int H, hipStream_t
     case 20: PMX_RULE_LAUNCH(B, 20); break;                                                   \
     default: PMX_RULE_LAUNCH(B, 32); break;                                                   \
     }
-    if (p->dist) { PMX_RULE_PICK(true) } else { PMX_RULE_PICK(false) }
+    if (p->dist && p->bot_sight > 0) {      // the sight form of the bots variant (pmx_set_bot_sight)
+        switch (hb) {
+#define PMX_RULE_SIGHT_LAUNCH(HBV)                                                                                       \
+    do {                                                                                                                \
+        if (ev0) hipExtLaunchKernelGGL((pmx_rule_sight_kernel<HBV>), dim3(blocks), dim3(PMX_RULE_BLOCK), (uint32_t)lds, st, ev0, ev1, 0, q); \
+        else hipLaunchKernelGGL((pmx_rule_sight_kernel<HBV>), dim3(blocks), dim3(PMX_RULE_BLOCK), lds, st, q);            \
+    } while (0)
+        case 12: PMX_RULE_SIGHT_LAUNCH(12); break;
+        case 16: PMX_RULE_SIGHT_LAUNCH(16); break;
+        case 20: PMX_RULE_SIGHT_LAUNCH(20); break;
+        default: PMX_RULE_SIGHT_LAUNCH(32); break;
+        }
+    } else if (p->dist) { PMX_RULE_PICK(true) } else { PMX_RULE_PICK(false) }
     return hipGetLastError();
 }
 
@@ -1996,7 +2146,8 @@ extern "C" hipError_t pmx_launch_rule_agent(const PmxTickParams *p, int H, int a
 {
     const int blocks = (p->N + PMX_RULE_BLOCK - 1) / PMX_RULE_BLOCK;
     const size_t lds = (p->layout_idx ? 32 + (size_t)(3 * PMX_MAX_H_LDS + 32 + 16) * PMX_RULE_BLOCK : 32 + (size_t)(3 * H + 16) * PMX_RULE_BLOCK) * sizeof(uint32_t);
-    if (p->dist) hipLaunchKernelGGL(pmx_rule_agent_kernel<true>, dim3(blocks), dim3(PMX_RULE_BLOCK), lds, st, *p, agent);
+    if (p->dist && p->bot_sight > 0) hipLaunchKernelGGL(pmx_rule_agent_sight_kernel, dim3(blocks), dim3(PMX_RULE_BLOCK), lds, st, *p, agent);
+    else if (p->dist) hipLaunchKernelGGL(pmx_rule_agent_kernel<true>, dim3(blocks), dim3(PMX_RULE_BLOCK), lds, st, *p, agent);
     else hipLaunchKernelGGL(pmx_rule_agent_kernel<false>, dim3(blocks), dim3(PMX_RULE_BLOCK), lds, st, *p, agent);
     return hipGetLastError();
 }
@@ -2014,7 +2165,9 @@ extern "C" hipError_t pmx_launch_bot_query(const PmxTickParams *p, int H, int ag
 {
     const int blocks = (p->N + PMX_RULE_BLOCK - 1) / PMX_RULE_BLOCK;
     const size_t lds = (p->layout_idx ? 32 + (size_t)(3 * PMX_MAX_H_LDS + 32 + 16) * PMX_RULE_BLOCK : 32 + (size_t)(3 * H + 16) * PMX_RULE_BLOCK) * sizeof(uint32_t);
-    hipLaunchKernelGGL(pmx_bot_query_kernel, dim3(blocks), dim3(PMX_RULE_BLOCK), lds, st, *p, agent, code, values, action, flags);
+    if (p->dist && p->bot_sight > 0)
+        hipLaunchKernelGGL(pmx_bot_query_sight_kernel, dim3(blocks), dim3(PMX_RULE_BLOCK), lds, st, *p, agent, code, values, action, flags);
+    else hipLaunchKernelGGL(pmx_bot_query_kernel, dim3(blocks), dim3(PMX_RULE_BLOCK), lds, st, *p, agent, code, values, action, flags);
     return hipGetLastError();
 }
 

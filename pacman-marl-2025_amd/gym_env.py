@@ -37,7 +37,7 @@ class gymPacMan_parallel_env:
 
     def __init__(self, layout_file=os.path.join(_HERE, "layouts", "smallCapture.lay"), display=False, length=299,
                  reward_forLegalAction=True, defenceReward=True, random_layout=False, enemieName="randomTeam",
-                 self_play=False, device="cuda:0"):
+                 self_play=False, device="cuda:0", fog_bots=False):
         if display:
             raise NotImplementedError("graphics display is out of scope of the MI355X env (DESIGN.md section 7)")
         self.device = device
@@ -50,6 +50,10 @@ class gymPacMan_parallel_env:
         self.random_layout = random_layout
         self.enemieName = enemieName
         self.self_play = self_play
+        # fog_bots: a red host bot is asked on its own observation of the mid-tick state (CaptureAgent.observationFunction ->
+        # GameState.makeObservation at the contest's SIGHT_RANGE), as capture.py's game loop asks it; the four sonar draws of
+        # makeObservation then precede the bot's own draw in the global `random` stream
+        self.fog_bots = bool(fog_bots)
         self.display = None
         self.reward_forLegalAction = reward_forLegalAction
         self.defenceReward = defenceReward
@@ -128,7 +132,8 @@ class gymPacMan_parallel_env:
                 a = self.action_mapping[actions[self.agents[i]]]        # KeyError on an unknown action, as in the reference
             else:
                 self._cached_state = None
-                a = self.agents[i].getAction(self._game_state())        # the bot sees the full mid-tick state (:157)
+                gs = self._game_state()                                 # the bot sees the full mid-tick state (:157) unless fog_bots
+                a = self.agents[i].getAction(self.agents[i].observationFunction(gs) if self.fog_bots else gs)
             code = torch.tensor([DIR_CODE[a]], dtype=torch.int8, device=env.device)
             observations[self.agents[i]] = env.step_agent(i, code).clone()[0]
             self._sub = (i + 1) & 3

@@ -133,7 +133,7 @@ class VecMAPPOTrainer:
                  device="cuda:0", seed=0, rank=0, world_size=1, process_group=None, total_updates=2000, length=300,
                  use_autocast=True, opponent="random", use_graph=False, algorithm="mappo", paired_minibatches=True, curriculum_scale=1.0,
                  env=None, redraw_layouts=False, force_collectives=False, hard_bots=("baseline",), mask_illegal=False,
-                 mix_opponents=False, fog_of_war=False, sight_range=SIGHT_RANGE, belief=False, belief_weights=False, belief_evidence=False):
+                 mix_opponents=False, fog_of_war=False, sight_range=SIGHT_RANGE, belief=False, belief_weights=False, belief_evidence=False, fog_bots=False):
         self.device = torch.device(device)
         # fog_of_war: every policy input of the rollout (the learners', the self / pool opponent networks', the bootstrap
         # observation) comes from the fog entry points -- an enemy shows only within sight_range of one of the team's agents, the
@@ -167,6 +167,13 @@ class VecMAPPOTrainer:
         self.belief_evidence = bool(belief_evidence)
         if self.belief_evidence and not (self.fog_of_war and self.belief):
             raise ValueError("belief_evidence=True needs fog_of_war=True and belief=True: the evidence narrows the sets of the hidden enemies")
+        # fog_bots (needs fog_of_war and sight_range >= 1): the in-kernel bots obey the sight rule too (pmx_set_bot_sight at the
+        # trainer's sight_range): a bot counts an enemy only within that range of itself or its mate, as the reference's bots do on
+        # the contest's observation.  Set once, below, on an env created with bots.  No network input changes, so nothing is recorded
+        self.fog_bots = bool(fog_bots)
+        if self.fog_bots and not (self.fog_of_war and self.sight_range >= 1):
+            raise ValueError("fog_bots=True needs fog_of_war=True and sight_range >= 1: the bots' rule is the learners' sight rule, and "
+                             "sight 0 would need the hidden-enemy skip inside the transition itself")
         self.rank, self.world_size = rank, world_size
         # hard_bots: the in-kernel teams the curriculum draws its "hard" opponent from (the reference's hard teams are
         # baselineTeam, AstarTeam and approxQTeam, pacman_mappo_resnet.py:40-47); the default keeps the draws of earlier versions
@@ -183,6 +190,8 @@ class VecMAPPOTrainer:
         self.env = env if env is not None else PmxVecEnv(
             layout, n_envs, length=length, reward_forLegalAction=True, defenceReward=True, auto_reset=True, obs_dtype=obs_dtype,
             device=self.device, seed=seed * 1000003 + rank, bots=opponent in BOT_TEAMS or opponent == "curriculum", redraw_layouts=redraw_layouts)
+        if self.fog_bots and (opponent in BOT_TEAMS or opponent == "curriculum"):
+            self.env.set_bot_sight(self.sight_range)
         self.N, self.T = n_envs, horizon
         self.minibatch, self.epochs = minibatch, epochs
         # "mappo": centralised critic on merge_obs_for_critic of the two learners (the reference).  "ippo": the same network
@@ -721,11 +730,17 @@ class VecMAPPOTrainer:
 
 
 def evaluate_vs_bots(model, num_episodes=20, layout_file="bloxCapture", teams=("baselineTeam", "randomTeam"), length=300,
-                     device="cuda:0", fog_of_war=False, sight_range=SIGHT_RANGE, belief=False, belief_weights=False):
+                     device="cuda:0", fog_of_war=False, sight_range=SIGHT_RANGE, belief=False, belief_weights=False, fog_bots=False):
     """evaluate_vs_bots (pacman_mappo_resnet.py:293-337): a fresh env per episode against host CaptureAgent bots (red),
     the learner plays blue with argmax actions; returns (mean return, std, win rate), a win being final score < 0.
     The reference cycles through its A*/approx-Q/baseline/MCTS teams; here through the team files this build ships.
-    fog_of_war: the learner's planes go through fog_obs (the host bots keep the full state the env gives them)."""
+    fog_of_war: the learner's planes go through fog_obs (the host bots keep the full state the env gives them unless fog_bots).
+    fog_bots (needs fog_of_war and sight_range == 5, the contest's constant the host GameState.makeObservation uses): every host
+    bot is asked on its own observation, gymPacMan_parallel_env(fog_bots=True)."""
+    if fog_bots and not fog_of_war:
+        raise ValueError("fog_bots=True needs fog_of_war=True")
+    if fog_bots and int(sight_range) != SIGHT_RANGE:
+        raise ValueError(f"fog_bots=True on the host-bot path uses the contest's SIGHT_RANGE = {SIGHT_RANGE}, got sight_range={sight_range!r}")
     if belief_weights:
         raise ValueError("evaluate_vs_bots has no belief tracker (no emission kernel runs on the host-bot path): evaluate a policy "
                          "trained with belief_weights=True with evaluate_vectorized(belief_weights=True)")
@@ -739,7 +754,8 @@ def evaluate_vs_bots(model, num_episodes=20, layout_file="bloxCapture", teams=("
     learner_ids = [1, 3]
     for ep in range(num_episodes):
         env = gymPacMan_parallel_env(layout_file=layout_file, display=False, reward_forLegalAction=True, defenceReward=True,
-                                     length=length, enemieName=teams[ep % len(teams)], self_play=False, device=device)
+                                     length=length, enemieName=teams[ep % len(teams)], self_play=False, device=device,
+                                     **({"fog_bots": True} if fog_bots else {}))
         obs_dict, _ = env.reset()
         ep_ret, done = 0.0, False
         while not done:
@@ -762,7 +778,7 @@ def evaluate_vs_bots(model, num_episodes=20, layout_file="bloxCapture", teams=("
 @torch.no_grad()
 def evaluate_vectorized(model, layout="bloxCapture", n_envs=1024, opponent="baseline", length=300, device="cuda:0", seed=0,
                         autocast=True, mask_illegal=False, side="blue", fog_of_war=False, sight_range=SIGHT_RANGE, belief=False, belief_weights=False,
-                        belief_evidence=False):
+                        belief_evidence=False, fog_bots=False):
     """evaluate_vs_bots (pacman_mappo_resnet.py:293-337) for n_envs episodes at once: the learner plays blue with argmax
     actions against the in-kernel randomTeam / baselineTeam / approxQTeam (opponent "random" / "baseline" / "approxq"), one episode per env (an env stops counting at its first done).
     Returns (mean episode return of the learner team as the reference sums it, std, win rate = share with final score < 0).
@@ -770,7 +786,8 @@ def evaluate_vectorized(model, layout="bloxCapture", n_envs=1024, opponent="base
     side: "blue" as above; "red": the learner plays red and the bots blue; "both": red in the first half of the envs, blue in
     the rest (a policy trained with mix_opponents plays both colours).  A red learner's win is a final score > 0.
     fog_of_war: the policy sees an enemy only within sight_range of one of its two agents (pmx_emit_team_obs_mixed_fog); every
-    side, blue included, then runs the emission-based loop.  The in-kernel bots keep the full state.
+    side, blue included, then runs the emission-based loop.  The in-kernel bots keep the full state unless fog_bots.
+    fog_bots (needs fog_of_war and sight_range >= 1): the in-kernel bots obey the same sight rule (pmx_set_bot_sight at sight_range).
     belief (needs fog_of_war): plane 5 shows the tracker's sets (pmx_belief_update after every step, pmx_emit_team_obs_mixed_belief),
     the inputs of a policy trained with the trainer's belief=True.
     belief_weights (needs fog_of_war and belief): plane 5 shows the weighted tracker's levels (pmx_belief_weights_update,
@@ -784,10 +801,12 @@ def evaluate_vectorized(model, layout="bloxCapture", n_envs=1024, opponent="base
         raise ValueError("belief_weights=True needs fog_of_war=True and belief=True")
     if belief_evidence and not (fog_of_war and belief):
         raise ValueError("belief_evidence=True needs fog_of_war=True and belief=True")
+    if fog_bots and not (fog_of_war and int(sight_range) >= 1):
+        raise ValueError("fog_bots=True needs fog_of_war=True and sight_range >= 1")
     if side != "blue" or fog_of_war:
         return _evaluate_sides(model, layout, n_envs, opponent, length, device, seed, autocast, mask_illegal, side,
                                int(sight_range) if fog_of_war else None, **({"belief": True} if belief else {}), **({"belief_weights": True} if belief_weights else {}),
-                               **({"belief_evidence": True} if belief_evidence else {}))
+                               **({"belief_evidence": True} if belief_evidence else {}), **({"fog_bots": True} if fog_bots else {}))
     dev = torch.device(device)
     env = PmxVecEnv(layout, n_envs, length=length, auto_reset=True, obs_dtype="bfloat16" if autocast else "float32", device=dev,
                     seed=seed, bots=opponent in BOT_TEAMS)
@@ -825,14 +844,19 @@ def evaluate_vectorized(model, layout="bloxCapture", n_envs=1024, opponent="base
 
 
 def _evaluate_sides(model, layout, n_envs, opponent, length, device, seed, autocast, mask_illegal, side, sight_range=None, belief=False,
-                    belief_weights=False, belief_evidence=False):
+                    belief_weights=False, belief_evidence=False, fog_bots=False):
     """evaluate_vectorized with the learner's colour chosen per env: observations from pmx_emit_team_obs_mixed (canonical, so the
     policy sees a red game as it was trained to), actions and masks through the per-env frame helpers.  sight_range (an int): the
     fog form of the emission; with belief the belief form, the sets advanced after every step; with belief_weights the weighted
-    forms of both; with belief_evidence the updates are the evidence forms."""
+    forms of both; with belief_evidence the updates are the evidence forms; with fog_bots (needs sight_range >= 1) the in-kernel
+    bots obey the sight rule at sight_range."""
+    if fog_bots and (sight_range is None or int(sight_range) < 1):
+        raise ValueError("fog_bots=True needs fog_of_war=True and sight_range >= 1")
     dev = torch.device(device)
     env = PmxVecEnv(layout, n_envs, length=length, auto_reset=True, obs_dtype="bfloat16" if autocast else "float32", device=dev,
                     seed=seed, bots=opponent in BOT_TEAMS)
+    if fog_bots and opponent in BOT_TEAMS:
+        env.set_bot_sight(int(sight_range))
     env.reset(want_obs=False)
     was_training = model.training
     model.eval()

@@ -171,7 +171,8 @@ class PmxVecEnv:
         """Ask an in-kernel bot for its move (pmx_bot_query): for `agent` of every env, on the current state and without
         changing it, what bot `code` (-2 .. -6) would play if step_agent(agent, code) were called now.  Returns (values [N,5]
         float64 indexed by action code, NaN where illegal -- None unless want_values --, action [N] int8, flags [N] uint8:
-        bit 0 walked home, bit 1 explored); fresh tensors."""
+        bit 0 walked home, bit 1 explored; after set_bot_sight also bit 2 / bit 3: the enemy with the lower / higher index is
+        seen); fresh tensors."""
         N = self.n_envs
         values = torch.empty((N, 5), dtype=torch.float64, device=self.device) if want_values else None
         action = torch.empty((N,), dtype=torch.int8, device=self.device)
@@ -180,6 +181,13 @@ class PmxVecEnv:
             _lib.call("pmx_bot_query", self.handle, int(agent), int(code), values.data_ptr() if want_values else None, action.data_ptr(),
                       flags.data_ptr(), _lib.stream(self.device))
         return values, action, flags
+
+    def set_bot_sight(self, sight_range=None):
+        """Bind the in-kernel bots (codes -3 .. -6) to the contest's sight rule (pmx_set_bot_sight): a bot then counts an enemy
+        only within `sight_range` (1 .. 64) Manhattan cells of itself or its mate, as the reference's bots do under
+        GameState.makeObservation.  None switches the rule off (the default).  Applies to every step, step_agent and bot_query
+        after the call; needs an env created with bots=True."""
+        _lib.call("pmx_set_bot_sight", self.handle, _lib.BOT_SIGHT_OFF if sight_range is None else int(sight_range))
 
     def observe(self, want_obs=True, want_legal=True):
         """get_Observation of the current state for every emitted agent (gymPacMan.py:195-229) and/or the legal masks."""

@@ -61,6 +61,8 @@ def parser():
                     "motion, respawn prior, sight rule, sonar) and show its levels 0 .. 16 in plane 5 in place of the sets' 0 / 1")
     ap.add_argument("--belief-evidence", action="store_true", help="with --fog-of-war --belief: narrow the sets by what stays public about a hidden enemy: "
                     "the half it is on, a pellet it ate, and that it can only have died next to one of the team's agents")
+    ap.add_argument("--fog-bots", action="store_true", help="with --fog-of-war: the in-kernel bot opponents obey the sight rule too (an enemy counts only "
+                    "within --sight-range of the bot or its mate, as the contest hands its bots an observation); training and the evaluations")
     ap.add_argument("--sight-range", type=int, default=5, help="with --fog-of-war: Manhattan cells (the contest's SIGHT_RANGE is 5)")
     ap.add_argument("--graph", action="store_true", help="replay the optimizer step from a hipGraph (launch-bound minibatches, e.g. 512)")
     return ap
@@ -107,6 +109,8 @@ def main():
         fog["belief_weights"] = True                            # (without --belief the trainer rejects it)
     if args.belief_evidence:
         fog["belief_evidence"] = True                           # (likewise)
+    if args.fog_bots:
+        fog["fog_bots"] = True                                  # (without --fog-of-war the trainer rejects it)
     tr = trainer.VecMAPPOTrainer(layout, args.envs, horizon=args.horizon, minibatch=args.minibatch, epochs=args.epochs, redraw_layouts=args.redraw,
                                  obs_dtype=args.obs, device=f"cuda:{local}", seed=args.seed, rank=rank, world_size=world,
                                  total_updates=args.total_updates, opponent=args.opponent, algorithm=args.algorithm, use_graph=args.graph, paired_minibatches=not args.unpaired, curriculum_scale=args.curriculum_scale,
