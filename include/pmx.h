@@ -406,6 +406,52 @@ int pmx_belief_weights_update_evidence(pmx_env *env, int team_red, const uint8_t
                                        int32_t sight_range, int32_t rules, const uint8_t *reset_dev, uint32_t *belief_dev, int8_t *sonar_dev,
                                        uint16_t *weights_dev, uint8_t *levels_dev, uint32_t *evidence_dev, void *stream);
 
+/* ---- Episode statistics (opt-in, no reference counterpart): an exact per-episode event record for every env ------------------
+ * The env reports rewards, done and the score; who ate, who died carrying what and who caught whom is in none of them.  The
+ * sub-step snapshots a tick leaves (the ones the observation and belief kernels read) hold all of it, and this kernel counts it.
+ * stats_dev is caller-owned: int32 [PMX_STATS_WORDS][count], WORD-MAJOR -- word w of row r = env - first is stats_dev[w * count + r],
+ * the state's own structure-of-arrays order, so the lane-per-env kernel reads and writes it coalesced.  Words:
+ *   8 i + c     counter c (PMX_STAT_*) of agent i
+ *   32 TICKS    33 SCORE (data.score after the last counted tick, signed)    34 DONE    35 0
+ *   36..39 / 40..43   agent words A / B of the state after the last counted tick (x | y << 8 | dir << 16 | isPacman << 24 and
+ *                     scaredTimer | numCarrying << 8 | numReturned << 20)
+ *   44, 45      its two capsule words (four 16-bit slots x | y << 8, 0xFFFF = empty)        46, 47   0
+ * pmx_episode_stats_init, after pmx_reset or pmx_set_state and before the first step: zeroes the counters, TICKS, DONE and words 35,
+ * 46, 47 and sets SCORE and words 36..45 from the current state.
+ * pmx_episode_stats_update, once after each pmx_step: a row whose DONE word is not 0 is left untouched, every word of it.  Otherwise
+ * the four sub-step transitions X -> Y of the tick are walked with mover m = 0, 1, 2, 3 over the states: words 36..45, snapshot 0,
+ * snapshot 1, snapshot 2, current state.  pos = (x, y), dist = Manhattan distance, every field from the agent and capsule words:
+ *   death of a non-mover i != m   pos_Y[i] != pos_X[i], or scared_X[i] > 0 && scared_Y[i] == 0, or carry_Y[i] < carry_X[i]  (only the
+ *                                 mover moves, only the mover's timer ticks, and only a death empties another agent's carry)
+ *   death of the mover            dist(pos_Y[m], pos_X[m]) > 1, or carry_Y[m] < carry_X[m] && ret_Y[m] == ret_X[m], or
+ *                                 scared_X[m] >= 2 && scared_Y[m] == 0
+ *   DEATHS[i]       += 1 per death of i
+ *   LOST[i]         += carry_X[i] per death of i
+ *   KILLS[m]        += number of non-movers that died
+ *   EATEN[m]        += max(0, carry_Y[m] - carry_X[m])
+ *   RETURNED[m]     += ret_Y[m] - ret_X[m]
+ *   CAPSULES[m]     += occupied capsule slots of X minus those of Y
+ *   PACMAN_STEPS[m] += isPacman_Y[m]
+ *   STOPS[m]        += 1 if the mover did not die and pos_Y[m] == pos_X[m]  (illegal actions become Stop, capture.py:473-474)
+ * After the four transitions TICKS += 1, SCORE = the state's score word, words 36..45 = the state's, DONE = 1 where done_dev[env]
+ * != 0 (done_dev [n_envs] uint8, indexed by env, may be NULL: DONE is then never set).
+ * Blind spot: a mover with carry == 0 and scared <= 1 that is sent to a start cell within one step of the cell it left is counted
+ * as a move.  In the reference this can only be a scared ghost with one tick of fear left that steps onto an invader beside its
+ * own start.  Non-movers have none: a Pacman never stands on its own start, and a ghost there that is not scared cannot be eaten.
+ * A mover that eats a pellet and dies in the same move (capture.py applies the action before checkDeath) gets EATEN += 0 and LOST
+ * += carry_X, so EATEN - RETURNED - LOST == numCarrying stays exact.
+ * One lane per env, no LDS, no atomics, plain vector stores (csrc/pmx_stats.hip).  An open pmx_profile_begin records the update with
+ * the rule launches, as the belief update's.
+ * Errors: PMX_ERR_INVALID for a NULL handle or buffer, a range outside the handle, an unfinished pmx_step_agent tick and, for the
+ * update, where the snapshots do not describe the last tick (nothing stepped since pmx_reset / pmx_set_state, or the tick was run
+ * with pmx_step_agent or pmx_successor, which leave no snapshots); PMX_ERR_UNSUPPORTED on an auto_reset handle (a finished env's
+ * snapshots and state are overwritten with the fresh game inside the tick, so its terminal tick cannot be read).  count == 0
+ * launches nothing. */
+#define PMX_STATS_WORDS 48
+enum { PMX_STAT_EATEN, PMX_STAT_RETURNED, PMX_STAT_LOST, PMX_STAT_DEATHS, PMX_STAT_KILLS, PMX_STAT_CAPSULES, PMX_STAT_PACMAN_STEPS, PMX_STAT_STOPS };  /* 8 per agent */
+int pmx_episode_stats_init(pmx_env *env, int32_t first, int32_t count, int32_t *stats_dev, void *stream);
+int pmx_episode_stats_update(pmx_env *env, int32_t first, int32_t count, const uint8_t *done_dev, int32_t *stats_dev, void *stream);
+
 /* The layout each env is currently on (host output [n_envs]; all zeros for a single-layout handle).  Synchronises the stream. */
 int pmx_get_layout_index(pmx_env *env, int32_t *index_out, void *stream);
 

@@ -21,6 +21,11 @@ SALT_SONAR = 0x534F4E41                          # PMX_SALT_SONAR: the sonar's n
 BELIEF_START_CELLS, BELIEF_OPEN_CELLS = 0, 1     # pmx_belief_init kinds
 BELIEF_RESPAWN_SHIFT, BELIEF_LEVELS = 7, 16      # PMX_BELIEF_RESPAWN_SHIFT, PMX_BELIEF_LEVELS (pmx_belief_weights_update)
 EVIDENCE_SIDE, EVIDENCE_FOOD, EVIDENCE_CONTACT, EVIDENCE_WORDS = 1, 2, 4, 36      # PMX_EVIDENCE_* (pmx_belief_update_evidence)
+STATS_WORDS = 48                                 # PMX_STATS_WORDS (pmx_episode_stats_update)
+(STAT_EATEN, STAT_RETURNED, STAT_LOST, STAT_DEATHS, STAT_KILLS, STAT_CAPSULES, STAT_PACMAN_STEPS,
+ STAT_STOPS) = range(8)                          # PMX_STAT_*: counter c of agent i is word 8 i + c
+STAT_NAMES = ("eaten", "returned", "lost", "deaths", "kills", "capsules", "pacman_steps", "stops")
+STATS_W_TICKS, STATS_W_SCORE, STATS_W_DONE, STATS_W_STATE = 32, 33, 34, 36
 COLSUM_BLOCKS = 512
 LN32_PARTIAL_ROWS = 2048
 ACTOR_PACK_BYTES = 297984
@@ -98,6 +103,8 @@ PROTOTYPES = [
     ("pmx_belief_evidence_init", C.c_int, [_VP, _I32, _I32, _VP, _VP]),
     ("pmx_belief_update_evidence", C.c_int, [_VP, C.c_int, _VP, _I32, _I32, _I32, _I32, _VP, _VP, _VP, _VP, _VP]),
     ("pmx_belief_weights_update_evidence", C.c_int, [_VP, C.c_int, _VP, _I32, _I32, _I32, _I32, _VP, _VP, _VP, _VP, _VP, _VP, _VP]),
+    ("pmx_episode_stats_init", C.c_int, [_VP, _I32, _I32, _VP, _VP]),
+    ("pmx_episode_stats_update", C.c_int, [_VP, _I32, _I32, _VP, _VP, _VP]),
     ("pmx_emit_team_obs_weighted", C.c_int, [_VP, C.c_int, _VP, _VP, _VP, _VP]),
     ("pmx_emit_team_obs_mixed_weighted", C.c_int, [_VP, _VP, _I32, _I32, _VP, _VP, _VP, _VP]),
     ("pmx_get_layout_index", C.c_int, [_VP, C.POINTER(_I32), _VP]),

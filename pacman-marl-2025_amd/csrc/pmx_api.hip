@@ -25,6 +25,8 @@ extern "C" hipError_t pmx_launch_emit_team_weighted(const PmxEmitParams *p, int 
 extern "C" hipError_t pmx_launch_belief_weights(const PmxBeliefWeightsParams *p, int init, hipStream_t st, hipEvent_t ev0, hipEvent_t ev1);
 extern "C" hipError_t pmx_launch_belief_evidence(const PmxBeliefWeightsParams *p, const PmxBeliefEvidenceParams *e, int weighted, hipStream_t st,
                                                  hipEvent_t ev0, hipEvent_t ev1);
+extern "C" hipError_t pmx_launch_episode_stats(const uint32_t *const *snap, const uint8_t *done, int32_t *stats, int N, int first, int count, int H,
+                                               int init, hipStream_t st, hipEvent_t ev0, hipEvent_t ev1);
 extern "C" hipError_t pmx_launch_expand(const PmxExpandParams *p, int dtype, hipStream_t st, hipEvent_t ev0, hipEvent_t ev1);
 extern "C" hipError_t pmx_launch_maze(const PmxLayoutDev *lay_dev, const int16_t *cell_index_dev, int n_cells,
                                       const int8_t *cells_dev, uint8_t *dist_dev, hipStream_t st);
@@ -737,6 +739,39 @@ int pmx_belief_weights_update_evidence(pmx_env *env, int team_red, const uint8_t
 {
     return belief_update_evidence(env, "pmx_belief_weights_update_evidence", 1, team_red, team_red_dev, first, count, sight_range, rules,
                                   reset_dev, belief_dev, sonar_dev, weights_dev, levels_dev, evidence_dev, stream);
+}
+
+// Episode statistics (include/pmx.h, "Episode statistics")
+namespace {
+int episode_stats(pmx_env *env, const char *who, int init, int32_t first, int32_t count, const uint8_t *done_dev, int32_t *stats_dev, void *stream)
+{
+    if (!env || !stats_dev) return fail(PMX_ERR_INVALID, "%s: null argument", who);
+    if (env->cfg.auto_reset)
+        return fail(PMX_ERR_UNSUPPORTED, "%s: an auto_reset handle overwrites a finished env's snapshots with the fresh game inside the tick", who);
+    if (first < 0 || count < 0 || (int64_t)first + count > env->cfg.n_envs)
+        return fail(PMX_ERR_INVALID, "%s: envs %d .. %lld of %d", who, first, (long long)first + count - 1, env->cfg.n_envs);
+    if (env->open_agent != 0) return fail(PMX_ERR_INVALID, "%s: a tick opened with pmx_step_agent is unfinished", who);
+    if (!init && !env->snaps_valid)
+        return fail(PMX_ERR_INVALID, "%s: the sub-step snapshots do not describe the last tick (call it once after each pmx_step)", who);
+    if (count == 0) return PMX_OK;
+    const size_t snap_sz = (size_t)PMX_SNAP_WORDS(env->lay.H) * env->cfg.n_envs;
+    const uint32_t *snap[4];
+    for (int a = 0; a < 4; ++a) snap[a] = (!init && a < 3) ? env->snap_dev + a * snap_sz : env->state_dev;
+    hipEvent_t *ev = init ? nullptr : prof_pair(env, false);          // recorded with the rule launches, as the belief update is
+    HIP_TRY(pmx_launch_episode_stats(snap, done_dev, stats_dev, env->cfg.n_envs, first, count, env->lay.H, init, as_stream(stream),
+                                     ev ? ev[0] : nullptr, ev ? ev[1] : nullptr));
+    return PMX_OK;
+}
+}  // namespace
+
+int pmx_episode_stats_init(pmx_env *env, int32_t first, int32_t count, int32_t *stats_dev, void *stream)
+{
+    return episode_stats(env, "pmx_episode_stats_init", 1, first, count, nullptr, stats_dev, stream);
+}
+
+int pmx_episode_stats_update(pmx_env *env, int32_t first, int32_t count, const uint8_t *done_dev, int32_t *stats_dev, void *stream)
+{
+    return episode_stats(env, "pmx_episode_stats_update", 0, first, count, done_dev, stats_dev, stream);
 }
 
 namespace {

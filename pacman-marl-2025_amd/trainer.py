@@ -907,6 +907,210 @@ def _evaluate_sides(model, layout, n_envs, opponent, length, device, seed, autoc
     return float(ret.mean()), float(ret.std()), float(torch.where(red_b, final > 0, final < 0).double().mean())
 
 
+# ---- Matches: any two sides against each other, each with its own eyes, with the device episode statistics ------------------------
+MATCH_BOTS = ("random", "baseline", "approxq")
+
+
+class MatchSide:
+    """One side of play_match: a network (`model`, a MAPPOAgent) or an in-kernel team (`bot` out of MATCH_BOTS).  greedy / mask_illegal:
+    how a network picks its actions (argmax in place of a draw; over the legal actions only).  fog_of_war, sight_range, belief,
+    belief_weights, belief_evidence: the observation regime the network was trained under, with evaluate_vectorized's meaning and
+    dependencies.  A bot side takes none of them (play_match's fog_bots binds the bots to the opponent's sight rule)."""
+
+    def __init__(self, model=None, bot=None, greedy=False, mask_illegal=False, fog_of_war=False, sight_range=SIGHT_RANGE, belief=False,
+                 belief_weights=False, belief_evidence=False):
+        if (model is None) == (bot is None):
+            raise ValueError("a MatchSide is either a network (model=...) or an in-kernel team (bot=...), exactly one of the two")
+        if bot is not None and bot not in MATCH_BOTS:
+            raise ValueError(f"bot must be one of {MATCH_BOTS}, got {bot!r}")
+        if bot is not None and (greedy or mask_illegal or fog_of_war or belief or belief_weights or belief_evidence):
+            raise ValueError("a bot side takes no policy or observation flags (fog_bots=True of play_match binds the bots to the sight rule)")
+        if belief and not fog_of_war:
+            raise ValueError("belief=True needs fog_of_war=True")
+        if belief_weights and not (fog_of_war and belief):
+            raise ValueError("belief_weights=True needs fog_of_war=True and belief=True")
+        if belief_evidence and not (fog_of_war and belief):
+            raise ValueError("belief_evidence=True needs fog_of_war=True and belief=True")
+        if fog_of_war and not 0 <= int(sight_range) <= _lib.SIGHT_RANGE_MAX:
+            raise ValueError(f"sight_range must be in 0 .. {_lib.SIGHT_RANGE_MAX}, got {sight_range!r}")
+        self.model, self.bot, self.greedy, self.mask_illegal = model, bot, bool(greedy), bool(mask_illegal)
+        self.fog_of_war, self.sight_range = bool(fog_of_war), int(sight_range)
+        self.belief, self.belief_weights, self.belief_evidence = bool(belief), bool(belief_weights), bool(belief_evidence)
+
+
+def match_side_seed(seed, k):
+    """The seed of side k's action draws (k = 0 for A, 1 for B): 2 * seed + k in 32 bits, so the two sides of one match and the sides
+    of matches with neighbouring seeds all draw from different streams (pmx_policy_sample hashes seed, row and tick together)."""
+    return ((int(seed) << 1) | int(k)) & 0xFFFFFFFF
+
+
+def match_colours(n_envs, colours, device="cpu"):
+    """uint8 [n_envs], non-zero = side A is red in that env: "both" = red in envs [0, n_envs // 2) and blue in the rest (the split
+    of evaluate_vectorized(side="both")), "red" / "blue" = that colour everywhere."""
+    if colours not in ("both", "red", "blue"):
+        raise ValueError(f"colours must be both, red or blue, got {colours!r}")
+    red = torch.zeros(n_envs, dtype=torch.uint8, device=device)
+    red[:{"red": n_envs, "both": n_envs // 2, "blue": 0}[colours]] = 1
+    return red
+
+
+def _check_match(a, b, fog_bots):
+    for s in (a, b):
+        if not isinstance(s, MatchSide):
+            raise ValueError(f"play_match takes two MatchSide objects, got {type(s).__name__}")
+    if a.model is not None and b.model is not None and a.greedy and b.greedy:
+        raise ValueError("two greedy networks and no bot make every game of a colour the same game: let at least one side sample "
+                         "(greedy=False), or this would play n_envs copies of two games")
+    if fog_bots:
+        ranges = [o.sight_range for s, o in ((a, b), (b, a)) if s.bot is not None and o.fog_of_war and o.sight_range >= 1]
+        if not ranges:
+            raise ValueError("fog_bots=True needs a bot side whose opponent has fog_of_war=True and sight_range >= 1")
+        return ranges[0]
+    return None
+
+
+def match_result(red, score, ret_a, ret_b, stats):
+    """play_match's bookkeeping from its raw tensors: red uint8 [n] (A's colour), score int32 [n] (final data.score), ret_a / ret_b
+    float64 [n] (each side's summed team reward), stats int32 [48, n].  -> the result dict (see play_match)."""
+    n = int(red.shape[0])
+    red_b = red.to(torch.bool)
+    margin = torch.where(red_b, score, -score).to(torch.float64)             # A's signed final score
+    per = stats[:32].view(4, 8, n).to(torch.float64)                         # [agent, counter, game]
+
+    def split(mask):
+        g = int(mask.sum())
+        if g == 0:
+            return dict(games=0)
+        m = margin[mask]
+        return dict(games=g, wins_a=int((m > 0).sum()), ties=int((m == 0).sum()), wins_b=int((m < 0).sum()),
+                    win_rate_a=float((m > 0).double().mean()), margin_mean=float(m.mean()),
+                    margin_sem=float(m.std() / g ** 0.5) if g > 1 else 0.0)
+
+    def side(team_red):
+        # the side's two slots, lower agent index first (the offensive bot of an in-kernel team): agents (0, 2) where it is red
+        first = torch.where(team_red, per[0], per[1])
+        second = torch.where(team_red, per[2], per[3])
+        return {name: [float(first[c].mean()), float(second[c].mean())] for c, name in enumerate(_lib.STAT_NAMES)}
+
+    out = split(torch.ones_like(red_b))
+    out.update(as_red=split(red_b), as_blue=split(~red_b), ticks_mean=float(stats[_lib.STATS_W_TICKS].double().mean()),
+               return_a=float(ret_a.mean()), return_b=float(ret_b.mean()), stats_a=side(red_b), stats_b=side(~red_b), red=red, score=score, stats=stats)
+    return out
+
+
+class _MatchEyes:
+    """What one network side of a match owns: its colour vector, observation buffer and belief buffers, and the three calls of a tick."""
+
+    def __init__(self, side, env, red, seed, autocast):
+        self.side, self.env, self.red, self.seed = side, env, red, seed
+        n = env.n_envs
+        dev = red.device
+        self.obs = torch.empty((n, 2) + tuple(env.obs_shape), dtype=env.obs_torch_dtype, device=dev)
+        self.ctx = torch.autocast(device_type=dev.type, dtype=torch.bfloat16) if autocast else _NullCtx()
+        self.kw = {"sight_range": side.sight_range} if side.fog_of_war else {}
+        self.bel = self.wts = self.lev = None
+        if side.belief_weights:
+            self.bel, self.wts, self.lev = env.belief_weights_init(env.new_belief(), *env.new_belief_weights(), 0)
+            self.kw = {"levels": self.lev}
+        elif side.belief:
+            self.bel = env.belief_init(env.new_belief(), 0)
+            self.kw = {"belief": self.bel}
+        self.ekw = {"evidence": env.belief_evidence_init(env.new_belief_evidence())} if side.belief_evidence else {}
+
+    def act(self, tick):
+        """this tick's two actions per env, in the env's frame: int64 [n, 2]"""
+        env, side = self.env, self.side
+        env.emit_team_obs_mixed(self.red, self.obs, **self.kw)
+        lo = self.obs.view((-1,) + tuple(env.obs_shape))
+        lg = mappo.canonicalize_legal(mappo.team_columns(env.legal, self.red), self.red).reshape(-1) if side.mask_illegal else None
+        with self.ctx:
+            if side.greedy:          # the very call evaluate_vectorized makes (torch's argmax without masks, the kernel's with them)
+                a = side.model.get_deterministic_action(lo, **({"legal": lg} if lg is not None else {}))
+            else:
+                a = mappo.sample_actions(side.model.logits(lo), lg, seed=self.seed, counter=tick, greedy=False)[0]
+        return mappo.canonicalize_action(a.view(-1, 2), self.red)
+
+    def after_step(self):
+        if self.side.belief_weights:
+            self.env.belief_weights_update(self.red, self.bel, self.wts, self.lev, self.side.sight_range, **self.ekw)
+        elif self.side.belief:
+            self.env.belief_update(self.red, self.bel, self.side.sight_range, **self.ekw)
+
+
+@torch.no_grad()
+def play_match(a, b, layout="bloxCapture", n_envs=1024, length=300, colours="both", device="cuda:0", seed=0, autocast=True, fog_bots=False,
+               env=None):
+    """n_envs games at once between two MatchSides, each seeing the game its own way, with the device episode statistics
+    (pmx_episode_stats_update) of every game.  colours: see match_colours; B's colours are A's inverted.  Per tick every network side
+    gets one pmx_emit_team_obs_mixed* call of its own regime and colours, runs its own forward, and draws with
+    mappo.sample_actions(seed=match_side_seed(seed, k), counter=tick) -- or, greedy, takes evaluate_vectorized's argmax; a bot side
+    writes its two action codes.  After the step each side's belief buffers advance under its own colours.  The env never resets
+    (auto_reset=False): a game counts up to its first done, and the loop ends when every game is DONE or after length + 1 ticks.
+    fog_bots: the in-kernel bots obey the sight rule at the opposing network's sight_range (pmx_set_bot_sight).
+    Returns a dict: games, wins_a / ties / wins_b, win_rate_a, margin_mean / margin_sem (A's signed final score, +score where A is
+    red), the same under as_red / as_blue, ticks_mean, return_a (mean over games of A's summed team reward, as evaluate_vectorized sums
+    it), stats_a / stats_b (per counter of _lib.STAT_NAMES the per-game means of the side's two slots, lower agent index first), and
+    the raw tensors red [n], score [n], stats [48, n].
+    Two greedy networks are refused (every game of a colour would be the same game).  `env`: a ready env in place of the PmxVecEnv
+    this function creates (tests)."""
+    bot_sight = _check_match(a, b, fog_bots)
+    dev = torch.device(device)
+    red_a = match_colours(n_envs, colours, dev)
+    reds = (red_a, 1 - red_a)
+    if env is None:
+        env = PmxVecEnv(layout, n_envs, length=length, auto_reset=False, obs_dtype="bfloat16" if autocast else "float32", device=dev,
+                        seed=seed, bots=any(s.bot in BOT_TEAMS for s in (a, b)))
+    if bot_sight is not None:
+        env.set_bot_sight(bot_sight)
+    env.reset(want_obs=False)
+    stats = env.episode_stats_init(env.new_episode_stats())
+    models = [s.model for s in (a, b) if s.model is not None]
+    was_training = [m.training for m in models]
+    for m in models:
+        m.eval()
+    acts = torch.empty((n_envs, 4), dtype=torch.int8, device=dev)
+    eyes = []
+    for k, s in enumerate((a, b)):
+        if s.model is not None:
+            eyes.append(_MatchEyes(s, env, reds[k], match_side_seed(seed, k), autocast))
+        else:
+            codes = BOT_TEAMS.get(s.bot, (_lib.ACTION_RANDOM_LEGAL,) * 2)
+            mappo.set_team_columns(acts, reds[k], torch.tensor(codes, dtype=torch.int8, device=dev)[None].expand(n_envs, 2))
+    red_b = red_a.to(torch.bool)
+    alive = torch.ones(n_envs, dtype=torch.bool, device=dev)
+    ret = torch.zeros(n_envs, dtype=torch.float64, device=dev)
+    ret_b = torch.zeros(n_envs, dtype=torch.float64, device=dev)
+    final = torch.zeros(n_envs, dtype=torch.int32, device=dev)
+    for tick in range(length + 1):
+        for e in eyes:
+            mappo.set_team_columns(acts, e.red, e.act(tick))
+        _, rew, done, info = env.step(acts, want_obs=False)
+        for e in eyes:
+            e.after_step()
+        env.episode_stats_update(stats, done)
+        own = torch.where(red_b, rew[:, 0], rew[:, 1])
+        ret += torch.where(alive, own + own, torch.zeros_like(ret))                 # sum over both of A's agents' rewards (:328)
+        other = torch.where(red_b, rew[:, 1], rew[:, 0])
+        ret_b += torch.where(alive, other + other, torch.zeros_like(ret_b))
+        d = done.to(torch.bool) & alive
+        final = torch.where(d, info["score"], final)
+        alive &= ~d
+        if not bool(alive.any()):
+            break
+    env.close()
+    for m, t in zip(models, was_training):
+        if t:
+            m.train()
+    R = stats[8 * 0 + _lib.STAT_RETURNED] + stats[8 * 2 + _lib.STAT_RETURNED] - stats[8 * 1 + _lib.STAT_RETURNED] - stats[8 * 3 + _lib.STAT_RETURNED]
+    if not bool((stats[_lib.STATS_W_DONE] == 1).all()):
+        raise RuntimeError(f"play_match: {int((stats[_lib.STATS_W_DONE] != 1).sum())} games are not DONE after {length + 1} ticks")
+    if not torch.equal(stats[_lib.STATS_W_SCORE], final):
+        raise RuntimeError("play_match: the statistics' SCORE differs from the score the env reported at a game's done")
+    if not torch.equal(R, final):
+        raise RuntimeError("play_match: red RETURNED minus blue RETURNED differs from the final score")
+    return match_result(red_a, final, ret, ret_b, stats)
+
+
 class _NullCtx:
     def __enter__(self):
         return self

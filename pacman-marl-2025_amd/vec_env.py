@@ -404,6 +404,48 @@ class PmxVecEnv:
             _lib.call("pmx_belief_evidence_init", self.handle, first, count, evidence.data_ptr(), _lib.stream(self.device))
         return evidence
 
+    # -- episode statistics: an exact per-episode event record (include/pmx.h, "Episode statistics") -------------------
+    def new_episode_stats(self, count=None):
+        """The statistics buffer for `count` envs (None: all): int32 [48, count], WORD-major (word w of env first + r is
+        stats[w, r]), zeroed.  Call episode_stats_init before the first step.  Needs an env created with auto_reset=False."""
+        return torch.zeros((_lib.STATS_WORDS, self.n_envs if count is None else int(count)), dtype=torch.int32, device=self.device)
+
+    def _check_stats(self, stats, count):
+        assert (stats.shape == (_lib.STATS_WORDS, count) and stats.dtype == torch.int32 and stats.is_contiguous()
+                and stats.device == self.device)
+
+    def _stats_call(self, name, stats, first, count, *mid):
+        first = int(first)
+        count = self.n_envs - first if count is None else int(count)
+        self._check_stats(stats, count)
+        if count == 0:                                   # (an empty tensor has no address to pass)
+            return stats
+        with torch.cuda.device(self.device):
+            _lib.call(name, self.handle, first, count, *mid, stats.data_ptr(), _lib.stream(self.device))
+        return stats
+
+    def episode_stats_init(self, stats, first=0, count=None):
+        """pmx_episode_stats_init, after reset() or set_state() and before the first step(): the counters, TICKS and DONE of the
+        rows 0 .. count - 1 (envs first .. first + count - 1) to zero, SCORE and the state words from the current state."""
+        return self._stats_call("pmx_episode_stats_init", stats, first, count)
+
+    def episode_stats_update(self, stats, done=None, first=0, count=None):
+        """pmx_episode_stats_update, once after each step(): counts the tick's four sub-step transitions into every row that is
+        not DONE.  done: uint8 [N] (step()'s done), non-zero = the row is DONE from now on and keeps every word."""
+        if done is not None:
+            assert done.shape == (self.n_envs,) and done.dtype == torch.uint8 and done.is_contiguous() and done.device == self.device
+        return self._stats_call("pmx_episode_stats_update", stats, first, count, done.data_ptr() if done is not None else None)
+
+    @staticmethod
+    def episode_stats_dict(stats):
+        """Named views of a statistics buffer: every counter of _lib.STAT_NAMES as [count, 4] (agent along the last axis), and
+        ticks / score / done as [count]."""
+        count = stats.shape[1]
+        per = stats[:32].view(4, 8, count)
+        out = {name: per[:, c].t() for c, name in enumerate(_lib.STAT_NAMES)}
+        out.update(ticks=stats[_lib.STATS_W_TICKS], score=stats[_lib.STATS_W_SCORE], done=stats[_lib.STATS_W_DONE])
+        return out
+
     # -- measurement ---------------------------------------------------------------------------------------------
     def profile_begin(self, max_launches):
         _lib.call("pmx_profile_begin", self.handle, int(max_launches))
