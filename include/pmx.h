@@ -452,6 +452,46 @@ enum { PMX_STAT_EATEN, PMX_STAT_RETURNED, PMX_STAT_LOST, PMX_STAT_DEATHS, PMX_ST
 int pmx_episode_stats_init(pmx_env *env, int32_t first, int32_t count, int32_t *stats_dev, void *stream);
 int pmx_episode_stats_update(pmx_env *env, int32_t first, int32_t count, const uint8_t *done_dev, int32_t *stats_dev, void *stream);
 
+/* ---- Sight rule on the four-agent planes (opt-in): the contest's observation on pmx_step / pmx_step_agent / pmx_observe / pmx_reset
+ * gymPacMan's get_Observation hands every agent the full state; the contest hands agent i GameState.makeObservation(i)
+ * (capture.py:268-292): the state with the configuration of every far enemy blanked, and four noisy distances.  The two calls below
+ * put both on the env's own surfaces; the team entry points above (pmx_emit_team_obs_fog, pmx_belief_update) are unchanged.
+ *
+ * pmx_set_obs_sight: a host-side field of the handle, no launch, like pmx_set_bot_sight.  PMX_OBS_SIGHT_OFF (the default) or
+ * 0 .. PMX_SIGHT_RANGE_MAX; PMX_ERR_INVALID for a NULL handle or any other value.  While a range is set, every four-agent observation
+ * the handle writes afterwards -- obs_dev of pmx_step, pmx_step_agent, pmx_observe and pmx_reset, for every obs_agents subset, element
+ * type and per-env layout -- is under this rule, for agent i with mate m = i ^ 2 and enemies o (o ^ i odd):
+ *
+ *   what                         from                                                        reference
+ *   P[0 .. 3]                    the snapshot agent i's planes are encoded from (after its     gymPacMan.py:166-167
+ *                                own sub-step in pmx_step, the current state otherwise)
+ *   seen(o)                      min(manhattan(P[o], P[i]), manhattan(P[o], P[m]))            capture.py:285-291
+ *                                <= sight_range
+ *   plane 5 of agent i           the cell of enemy o is set iff seen(o)                       capture.py:288-290 (configuration = None)
+ *   planes 0 - 4, 6, 7           unchanged: walls, self, capsules, the mate, both food grids   capture.py:268-292 blanks nothing else
+ *
+ * This is the rule of pmx_emit_team_obs_fog applied to agent i's own block.  Every other plane byte and every other output of the
+ * call (reward, done, legal, score change, score, agent words), the state and the snapshots are byte for byte what they are with the
+ * rule off; from 62 on nothing is hidden.  With a range set pmx_step runs the rule launch followed by the sight form of the expansion
+ * kernel: neither the one-launch tick nor the wall split is taken, pmx_last_step_fused reports 0 and an open profile records the
+ * expansion as an expand launch.  uint8 planes of four agents take the wave per (env, agent) kernel.  After PMX_OBS_SIGHT_OFF the
+ * handle takes exactly the paths of a handle never set.
+ *
+ * pmx_agent_distances: the contest's getAgentDistances() (capture.py:210-224 noisyDistance, :272-275) for every env.
+ *   agent == -1       dist_dev int8 [n_envs][4][4], 16-byte aligned: r[a][i] = manhattan(P_a[a], P_a[i]) + n for every target i, a itself
+ *                     and its mate included (as the reference), P_a from the source agent a's planes are encoded from: its snapshot
+ *                     after a pmx_step, the current state otherwise -- what pmx_emit_team_obs reads.
+ *   agent == 0 .. 3   dist_dev int8 [n_envs][4], 4-byte aligned: that agent's four readings on the CURRENT state; the form for use after
+ *                     pmx_step_agent(agent), pmx_observe or pmx_reset.
+ * n = (int)(((uint64_t)h * 13) >> 32) - 6 with h = h(PMX_SALT_SONAR), the generator documented at PMX_ACTION_APPROXQ_OFFENSE with
+ * `agent` = 4 a + i and `ticks` = the env's ticks word at the time of the call.  For an enemy target this is the very draw
+ * pmx_belief_update makes: after the same pmx_step r[a_j][e_k] equals its sonar_dev[row][j][k] on every row that is not reset.
+ * Distribution-equivalent to noisyDistance; a reading may be negative.  The call changes nothing in the handle; an open profile records
+ * the launch with the rule launches.  PMX_ERR_INVALID for a NULL handle or pointer, an agent outside -1 .. 3 or a misaligned dist_dev. */
+#define PMX_OBS_SIGHT_OFF (-1)
+int pmx_set_obs_sight(pmx_env *env, int32_t sight_range);
+int pmx_agent_distances(pmx_env *env, int agent, int8_t *dist_dev, void *stream);
+
 /* The layout each env is currently on (host output [n_envs]; all zeros for a single-layout handle).  Synchronises the stream. */
 int pmx_get_layout_index(pmx_env *env, int32_t *index_out, void *stream);
 

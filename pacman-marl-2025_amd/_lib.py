@@ -16,6 +16,7 @@ ACTION_APPROXQ_OFFENSE, ACTION_APPROXQ_DEFENSE = -5, -6
 BOT_FLAG_HOME, BOT_FLAG_EXPLORED = 1, 2          # pmx_bot_query flags
 BOT_FLAG_SEEN_LO, BOT_FLAG_SEEN_HI = 4, 8        # ... on a handle with a bot sight: the lower / higher enemy index is seen
 BOT_SIGHT_OFF = -1                               # PMX_BOT_SIGHT_OFF (pmx_set_bot_sight)
+OBS_SIGHT_OFF = -1                               # PMX_OBS_SIGHT_OFF (pmx_set_obs_sight)
 SIGHT_RANGE_MAX = 64                             # PMX_SIGHT_RANGE_MAX
 SALT_SONAR = 0x534F4E41                          # PMX_SALT_SONAR: the sonar's noise draw (pmx_belief_update)
 BELIEF_START_CELLS, BELIEF_OPEN_CELLS = 0, 1     # pmx_belief_init kinds
@@ -89,6 +90,8 @@ PROTOTYPES = [
     ("pmx_successor", C.c_int, [_VP, C.c_int, _VP, _VP, _VP]),
     ("pmx_bot_query", C.c_int, [_VP, C.c_int, C.c_int, _VP, _VP, _VP, _VP]),
     ("pmx_set_bot_sight", C.c_int, [_VP, _I32]),
+    ("pmx_set_obs_sight", C.c_int, [_VP, _I32]),
+    ("pmx_agent_distances", C.c_int, [_VP, C.c_int, _VP, _VP]),
     ("pmx_observe", C.c_int, [_VP, _VP, _VP, _VP]),
     ("pmx_emit_team_obs", C.c_int, [_VP, C.c_int, _VP, _VP, _VP]),
     ("pmx_emit_team_obs_mixed", C.c_int, [_VP, _VP, _I32, _I32, _VP, _VP, _VP]),

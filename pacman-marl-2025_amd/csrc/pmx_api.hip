@@ -28,6 +28,9 @@ extern "C" hipError_t pmx_launch_belief_evidence(const PmxBeliefWeightsParams *p
 extern "C" hipError_t pmx_launch_episode_stats(const uint32_t *const *snap, const uint8_t *done, int32_t *stats, int N, int first, int count, int H,
                                                int init, hipStream_t st, hipEvent_t ev0, hipEvent_t ev1);
 extern "C" hipError_t pmx_launch_expand(const PmxExpandParams *p, int dtype, hipStream_t st, hipEvent_t ev0, hipEvent_t ev1);
+extern "C" hipError_t pmx_launch_expand_sight(const PmxExpandParams *p, int dtype, int sight, hipStream_t st, hipEvent_t ev0, hipEvent_t ev1);
+extern "C" hipError_t pmx_launch_agent_distances(const uint32_t *const *snap, const uint32_t *state, int8_t *dist, int N, int H, int agent,
+                                                 uint32_t seed, hipStream_t st, hipEvent_t ev0, hipEvent_t ev1);
 extern "C" hipError_t pmx_launch_maze(const PmxLayoutDev *lay_dev, const int16_t *cell_index_dev, int n_cells,
                                       const int8_t *cells_dev, uint8_t *dist_dev, hipStream_t st);
 
@@ -61,6 +64,7 @@ struct pmx_env {
     int n_cus = 0;                  // compute units of the device: the default of the fused tick's env threshold
     int last_step_fused = 0;        // the last pmx_step ran pmx_tick_fused_kernel (pmx_last_step_fused)
     int32_t bot_sight = 0;          // 0: the bots keep the full state; else the sight range of pmx_set_bot_sight
+    int32_t obs_sight = -1;         // PMX_OBS_SIGHT_OFF: the four-agent planes show every enemy; else the range of pmx_set_obs_sight
     std::vector<hipEvent_t> ev_rule, ev_expand;
     size_t ev_rule_used, ev_expand_used;
 };
@@ -185,7 +189,10 @@ int launch_expand(pmx_env *env, void *obs, bool from_snapshots, int single_agent
         if (env->tune.alt != 0) x.reverse = (int32_t)(env->expand_launches++ & 1);
     }
     hipEvent_t *ev = prof_pair(env, true);       // profiling: the dispatch's own start / stop timestamps
-    HIP_TRY(pmx_launch_expand(&x, env->cfg.obs_dtype, st, ev ? ev[0] : nullptr, ev ? ev[1] : nullptr));
+    if (env->obs_sight >= 0)                     // pmx_set_obs_sight: the sight form, for every caller of this function
+        HIP_TRY(pmx_launch_expand_sight(&x, env->cfg.obs_dtype, env->obs_sight, st, ev ? ev[0] : nullptr, ev ? ev[1] : nullptr));
+    else
+        HIP_TRY(pmx_launch_expand(&x, env->cfg.obs_dtype, st, ev ? ev[0] : nullptr, ev ? ev[1] : nullptr));
     return PMX_OK;
 }
 
@@ -409,10 +416,11 @@ int pmx_step(pmx_env *env, const int8_t *actions_dev, const pmx_step_out *out, v
     // behind it.  float32 planes only, and only while the expansion uses ordinary stores: bfloat16 planes measured slower with
     // the split, uint8 planes go through pmx_expand4_kernel, which writes whole env blocks, and beyond PMX_F32_STREAM_BYTES the
     // split is not measured.  Not with redraw_layouts (an env's walls change at a reset inside the rule kernel) and not under
-    // a profile (pmx_profile_begin: the expansion timed there is the full-plane kernel).
+    // a profile (pmx_profile_begin: the expansion timed there is the full-plane kernel).  Not with pmx_set_obs_sight either: the
+    // sight form is the rule launch followed by the full sight expansion, so the one-launch tick below is not taken with it.
     const size_t plane_bytes = (size_t)env->cfg.n_envs * env->n_emit * 8 * env->lay.H * env->lay.W * sizeof(float);
     const bool split_walls = out && out->obs_dev && env->cfg.obs_dtype == PMX_OBS_F32 && plane_bytes <= PMX_F32_STREAM_BYTES &&
-                             !env->cfg.redraw_layouts && !env->profiling;
+                             !env->cfg.redraw_layouts && !env->profiling && env->obs_sight < 0;
     if (split_walls) {
         p.obs = static_cast<float *>(out->obs_dev);
         p.n_emit = env->n_emit;
@@ -866,6 +874,30 @@ int pmx_set_bot_sight(pmx_env *env, int32_t sight_range)
     if (sight_range != PMX_BOT_SIGHT_OFF && !env->dist_dev)
         return fail(PMX_ERR_UNSUPPORTED, "pmx_set_bot_sight: needs a handle created with enable_bots");
     env->bot_sight = sight_range == PMX_BOT_SIGHT_OFF ? 0 : sight_range;
+    return PMX_OK;
+}
+
+int pmx_set_obs_sight(pmx_env *env, int32_t sight_range)
+{
+    if (!env) return fail(PMX_ERR_INVALID, "pmx_set_obs_sight: null env");
+    if (sight_range != PMX_OBS_SIGHT_OFF && (sight_range < 0 || sight_range > PMX_SIGHT_RANGE_MAX))
+        return fail(PMX_ERR_INVALID, "pmx_set_obs_sight: sight_range %d is neither PMX_OBS_SIGHT_OFF nor in 0 .. %d", sight_range, PMX_SIGHT_RANGE_MAX);
+    env->obs_sight = sight_range;
+    return PMX_OK;
+}
+
+int pmx_agent_distances(pmx_env *env, int agent, int8_t *dist_dev, void *stream)
+{
+    if (!env || !dist_dev) return fail(PMX_ERR_INVALID, "pmx_agent_distances: null argument");
+    if (agent < -1 || agent > 3) return fail(PMX_ERR_INVALID, "pmx_agent_distances: agent %d is neither -1 nor 0 .. 3", agent);
+    if ((uintptr_t)dist_dev % (agent < 0 ? 16 : 4) != 0)
+        return fail(PMX_ERR_INVALID, "pmx_agent_distances: dist_dev is not aligned to a row (%d bytes)", agent < 0 ? 16 : 4);
+    const size_t snap_sz = (size_t)PMX_SNAP_WORDS(env->lay.H) * env->cfg.n_envs;
+    const uint32_t *snap[4];
+    for (int a = 0; a < 4; ++a) snap[a] = (env->snaps_valid && a < 3) ? env->snap_dev + a * snap_sz : env->state_dev;
+    hipEvent_t *ev = prof_pair(env, false);          // an open profile records it with the rule launches, as the belief update
+    HIP_TRY(pmx_launch_agent_distances(snap, env->state_dev, dist_dev, env->cfg.n_envs, env->lay.H, agent, env->cfg.seed, as_stream(stream),
+                                       ev ? ev[0] : nullptr, ev ? ev[1] : nullptr));
     return PMX_OK;
 }
 

@@ -1198,8 +1198,13 @@ __device__ __forceinline__ void stream_or_row(uint32_t *T, uint32_t off, uint32_
 // launch stored, i.e. on a 128-byte line of the block's address; the wall-only vectors from there to the end of plane 0 come
 // out of the stream table like every other vector.  (PmxExpandParams::first_vec > 0 only selects this instantiation.)  A
 // template flag and not a test of first_vec, so that the full-plane instantiations are the code they were without the split.
-template <int DT, bool NT, bool BEHIND = false>
-__global__ __launch_bounds__(PMX_BLOCK) void pmx_expand_kernel(PmxExpandParams p)
+// SIGHT (pmx_set_obs_sight; include/pmx.h, "Sight rule on the four-agent planes"): the contest's sight rule on the block of agent
+// `agent`.  Lanes 0-3 hold the four agent words already; lane l takes P[agent] and P[agent ^ 2] from them by two wave shuffles and,
+// when its agent is an enemy further than `sight` from both, skips its atomicOr into the stream table.  No load, no LDS and no
+// store is added or changed.  Everything is under `if constexpr (SIGHT)`, and the body is shared by two kernels, so that
+// pmx_expand_kernel's instantiations stay the code they were (profiles/obs_sight/resource_usage.txt).
+template <int DT, bool NT, bool BEHIND, bool SIGHT>
+__device__ __forceinline__ void expand_block(const PmxExpandParams &p, [[maybe_unused]] int sight)
 {
     constexpr int VEC = ObsVec<DT>::VEC;
     __shared__ uint32_t tab[4][8 * 32 * 32 / 32 + 8];
@@ -1256,11 +1261,22 @@ __global__ __launch_bounds__(PMX_BLOCK) void pmx_expand_kernel(PmxExpandParams p
         stream_or_row(T, (uint32_t)((6 * H + lane) * W), food & L->hi_mask, W);    // blue food: x >= int(W/2) (capture.py:336)
         stream_or_row(T, (uint32_t)((7 * H + lane) * W), food & L->lo_mask, W);    // red food
     }
+    [[maybe_unused]] uint32_t ps = 0, pm = 0;                                        // SIGHT: word A of the agent and of its mate
+    if constexpr (SIGHT) {                                                          // (every lane of the wave runs the shuffles)
+        ps = (uint32_t)__shfl((int)pt, agent);
+        pm = (uint32_t)__shfl((int)pt, agent ^ 2);
+    }
     if (lane < 4) {
         const int x = pt & 0xFF, y = (pt >> 8) & 0xFF;
         const int plane = lane == agent ? 1 : (((lane ^ agent) == 2) ? 4 : 5);      // gymPacMan.py:205-215
         const uint32_t off = (uint32_t)((plane * H + y) * W + x);
-        atomicOr(&T[off >> 5], 1u << (off & 31));
+        bool shown = true;
+        if constexpr (SIGHT) {                                                          // capture.py:285-291
+            const int da = abs(x - (int)(ps & 0xFF)) + abs(y - (int)((ps >> 8) & 0xFF));
+            const int dm = abs(x - (int)(pm & 0xFF)) + abs(y - (int)((pm >> 8) & 0xFF));
+            shown = plane != 5 || (da < dm ? da : dm) <= sight;
+        }
+        if (shown) atomicOr(&T[off >> 5], 1u << (off & 31));
     } else if (lane < 8) {
         const uint32_t cxy = (pt >> (16 * ((lane - 4) & 1))) & 0xFFFFu;
         if (cxy != 0xFFFFu) {
@@ -1297,6 +1313,19 @@ __global__ __launch_bounds__(PMX_BLOCK) void pmx_expand_kernel(PmxExpandParams p
             out[k] = v;
         }
     }
+}
+
+template <int DT, bool NT, bool BEHIND = false>
+__global__ __launch_bounds__(PMX_BLOCK) void pmx_expand_kernel(PmxExpandParams p)
+{
+    expand_block<DT, NT, BEHIND, false>(p, 0);
+}
+
+// the sight form (handles with pmx_set_obs_sight): always the full block, the wall split is not taken with it
+template <int DT, bool NT>
+__global__ __launch_bounds__(PMX_BLOCK) void pmx_expand_sight_kernel(PmxExpandParams p, int sight)
+{
+    expand_block<DT, NT, false, true>(p, sight);
 }
 
 // ---------------------------------------------------------------------------------------------------------------
@@ -2237,5 +2266,32 @@ extern "C" hipError_t pmx_launch_expand(const PmxExpandParams *p, int dtype, hip
     default: PMX_EXPAND(2, true); break;
     }
 #undef PMX_EXPAND
+    return hipGetLastError();
+}
+
+// The sight form of the expansion (pmx_set_obs_sight): pmx_launch_expand's grid, store policy and occupancy cap, always the wave
+// per (env, agent) kernel (uint8 planes of four agents too) and always the full block (first_vec is refused).
+extern "C" hipError_t pmx_launch_expand_sight(const PmxExpandParams *p, int dtype, int sight, hipStream_t st, hipEvent_t ev0, hipEvent_t ev1)
+{
+    const long waves = (long)p->N * p->n_emit;
+    const unsigned blocks = (unsigned)((waves + 3) / 4);
+    const size_t elem = dtype == 0 ? 4 : (dtype == 1 ? 2 : 1);
+    const size_t bytes = (size_t)waves * 8 * p->lay_H * p->lay_W * elem;
+    const bool nt = elem == 1 || (elem == 2 && bytes > ((size_t)512 << 20)) || (elem == 4 && bytes > PMX_F32_STREAM_BYTES);
+    const size_t lds_pad = (nt && elem == 4) ? 40000 : 0;
+    PmxExpandParams q = *p;
+    if (nt) q.reverse = 0;
+    if (q.first_vec > 0) return hipErrorInvalidValue;
+#define PMX_EXPAND_SIGHT(...)                                                                                           \
+    do {                                                                                                                \
+        if (ev0) hipExtLaunchKernelGGL((pmx_expand_sight_kernel<__VA_ARGS__>), dim3(blocks), dim3(PMX_BLOCK), (uint32_t)lds_pad, st, ev0, ev1, 0, q, sight); \
+        else hipLaunchKernelGGL((pmx_expand_sight_kernel<__VA_ARGS__>), dim3(blocks), dim3(PMX_BLOCK), lds_pad, st, q, sight); \
+    } while (0)
+    switch (dtype) {
+    case 0: if (nt) PMX_EXPAND_SIGHT(0, true); else PMX_EXPAND_SIGHT(0, false); break;
+    case 1: if (nt) PMX_EXPAND_SIGHT(1, true); else PMX_EXPAND_SIGHT(1, false); break;
+    default: PMX_EXPAND_SIGHT(2, true); break;
+    }
+#undef PMX_EXPAND_SIGHT
     return hipGetLastError();
 }

@@ -37,7 +37,7 @@ class gymPacMan_parallel_env:
 
     def __init__(self, layout_file=os.path.join(_HERE, "layouts", "smallCapture.lay"), display=False, length=299,
                  reward_forLegalAction=True, defenceReward=True, random_layout=False, enemieName="randomTeam",
-                 self_play=False, device="cuda:0", fog_bots=False):
+                 self_play=False, device="cuda:0", fog_bots=False, fog_of_war=False, sight_range=5):
         if display:
             raise NotImplementedError("graphics display is out of scope of the MI355X env (DESIGN.md section 7)")
         self.device = device
@@ -54,6 +54,14 @@ class gymPacMan_parallel_env:
         # GameState.makeObservation at the contest's SIGHT_RANGE), as capture.py's game loop asks it; the four sonar draws of
         # makeObservation then precede the bot's own draw in the global `random` stream
         self.fog_bots = bool(fog_bots)
+        # fog_of_war (independent of fog_bots): the dicts of reset() and step() and get_Observation() are under the contest's sight
+        # rule (PmxVecEnv.set_obs_sight; capture.py:268-292) and the infos carry the four noisy distances of getAgentDistances()
+        # (PmxVecEnv.agent_distances; capture.py:210-224), drawn by the env's own generator: no draw of `random` is added or moved.
+        # Off: none of the two calls is made and no key is added
+        self.fog_of_war = bool(fog_of_war)
+        self.sight_range = int(sight_range)
+        if self.fog_of_war and not 0 <= self.sight_range <= 64:
+            raise ValueError(f"sight_range must be 0 .. 64, got {sight_range!r}")
         self.display = None
         self.reward_forLegalAction = reward_forLegalAction
         self.defenceReward = defenceReward
@@ -81,6 +89,8 @@ class gymPacMan_parallel_env:
                 self._engine.env.close()
             self._env = PmxVecEnv(self.layout, 1, length=self.length, reward_forLegalAction=self.reward_forLegalAction,
                                   defenceReward=self.defenceReward, auto_reset=False, obs_dtype="float32", device=self.device)
+            if self.fog_of_war:
+                self._env.set_obs_sight(self.sight_range)
             self._engine = SuccessorEngine(self.layout, self.device)
             self._layout_view = _LayoutView(self.layout)
         random.randint(0, 1)                                            # `starter`, drawn and unused (capture.py:372)
@@ -122,11 +132,15 @@ class gymPacMan_parallel_env:
         self._cached_state = None
         observations = {self.agents[i]: obs[0, i].clone() for i in range(4)}
         lg = legal[0].cpu().tolist()
-        return observations, {"legal_actions": {self.agents[i]: legal_list(lg[i]) for i in range(4)}}
+        info = {"legal_actions": {self.agents[i]: legal_list(lg[i]) for i in range(4)}}
+        if self.fog_of_war:
+            r = self._env.agent_distances()[0].cpu().tolist()
+            info["agent_distances"] = {self.agents[i]: r[i] for i in range(4)}
+        return observations, info
 
     def step(self, actions):                                            # gymPacMan.py:143-193
         env = self._env
-        observations = {}
+        observations, readings = {}, {}
         for i in range(4):
             if i in (1, 3) or self.self_play:
                 a = self.action_mapping[actions[self.agents[i]]]        # KeyError on an unknown action, as in the reference
@@ -136,6 +150,8 @@ class gymPacMan_parallel_env:
                 a = self.agents[i].getAction(self.agents[i].observationFunction(gs) if self.fog_bots else gs)
             code = torch.tensor([DIR_CODE[a]], dtype=torch.int8, device=env.device)
             observations[self.agents[i]] = env.step_agent(i, code).clone()[0]
+            if self.fog_of_war:                                         # agent i's readings on the state its planes show
+                readings[self.agents[i]] = env.agent_distances(i)[0]
             self._sub = (i + 1) & 3
         self._cached_state = None
         rew = env.reward[0].cpu().tolist()
@@ -144,9 +160,11 @@ class gymPacMan_parallel_env:
         terminations = {agent: done for agent in self.agents}
         self.steps += 1
         lg = env.legal[0].cpu().tolist()
-        return observations, rewards, terminations, {
-            "legal_actions": {self.agents[i]: legal_list(lg[i]) for i in range(4)},
-            "score_change": int(env.score_change[0].item())}
+        info = {"legal_actions": {self.agents[i]: legal_list(lg[i]) for i in range(4)},
+                "score_change": int(env.score_change[0].item())}
+        if self.fog_of_war:
+            info["agent_distances"] = {agent: r.cpu().tolist() for agent, r in readings.items()}
+        return observations, rewards, terminations, info
 
     def get_Observation(self, agentIndex):                              # gymPacMan.py:195-229
         obs, _ = self._env.observe(want_obs=True, want_legal=False)

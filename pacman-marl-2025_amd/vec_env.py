@@ -189,6 +189,31 @@ class PmxVecEnv:
         after the call; needs an env created with bots=True."""
         _lib.call("pmx_set_bot_sight", self.handle, _lib.BOT_SIGHT_OFF if sight_range is None else int(sight_range))
 
+    def set_obs_sight(self, sight_range=None):
+        """Put the four-agent observations under the contest's sight rule (pmx_set_obs_sight; GameState.makeObservation,
+        capture.py:268-292): in every observation step(), step_agent(), observe() and reset() write after the call, agent i's
+        plane 5 shows an enemy only within `sight_range` (0 .. 64) Manhattan cells of i or of its mate, positions from the snapshot
+        i's planes are encoded from.  Every other plane and every other output is unchanged.  None switches the rule off (the
+        default): the calls are then the ones of an env never set."""
+        _lib.call("pmx_set_obs_sight", self.handle, _lib.OBS_SIGHT_OFF if sight_range is None else int(sight_range))
+
+    def agent_distances(self, agent=None, out=None):
+        """The contest's getAgentDistances() for every env (pmx_agent_distances; capture.py:210-224): Manhattan distance plus a
+        noise of -6 .. 6 from the env's counter-based generator, the draw belief_update makes for the enemies.  agent None: int8
+        [N, 4, 4], r[a, i] = agent a's reading of agent i (itself and its mate included) on the state a's planes come from -- its
+        sub-step snapshot after step(), the current state otherwise.  agent 0 .. 3: int8 [N, 4], that agent's readings on the
+        current state (after step_agent(agent), observe() or reset()).  out: a tensor of that shape to write into; else a fresh
+        one.  Changes nothing in the env."""
+        if agent is not None and not 0 <= int(agent) <= 3:           # (-1 is the C ABI's code for the [N, 4, 4] form: a larger buffer)
+            raise ValueError(f"agent must be None or 0 .. 3, got {agent!r}")
+        shape = (self.n_envs, 4, 4) if agent is None else (self.n_envs, 4)
+        if out is None:
+            out = torch.empty(shape, dtype=torch.int8, device=self.device)
+        assert out.shape == shape and out.dtype == torch.int8 and out.is_contiguous() and out.device == self.device
+        with torch.cuda.device(self.device):
+            _lib.call("pmx_agent_distances", self.handle, -1 if agent is None else int(agent), out.data_ptr(), _lib.stream(self.device))
+        return out
+
     def observe(self, want_obs=True, want_legal=True):
         """get_Observation of the current state for every emitted agent (gymPacMan.py:195-229) and/or the legal masks."""
         with torch.cuda.device(self.device):
