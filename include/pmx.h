@@ -452,6 +452,52 @@ enum { PMX_STAT_EATEN, PMX_STAT_RETURNED, PMX_STAT_LOST, PMX_STAT_DEATHS, PMX_ST
 int pmx_episode_stats_init(pmx_env *env, int32_t first, int32_t count, int32_t *stats_dev, void *stream);
 int pmx_episode_stats_update(pmx_env *env, int32_t first, int32_t count, const uint8_t *done_dev, int32_t *stats_dev, void *stream);
 
+/* ---- Game records (opt-in): a device log of every sub-step of chosen envs, for replay and text rendering -------------------------
+ * The reference's users have capture.py --record / --replay and textDisplay; a game played on the device, bots deciding inside the
+ * tick kernel, leaves only counters.  The sub-step snapshots hold everything a replay needs, and this kernel keeps them.
+ * Both buffers are caller-owned int32, WORD-MAJOR with the row innermost like stats_dev; row r is env first + r:
+ *   head_dev   [PMX_RECORD_HEAD_WORDS][count]   word w of row r = head_dev[w * count + r]
+ *       0 LEN (ticks recorded)   1 DONE   2 OVERFLOW   3 LAYOUT (the row's layout index at init, 0 on a single-layout handle)   4..7  0
+ *   frames_dev [1 + 4 * max_ticks][FW][count]   word w of frame f of row r = frames_dev[(f * FW + w) * count + r], FW = 12 + height
+ *       (pmx_game_record_words).  Frame 0 is the state at init; frame 1 + 4 t + m the state after sub-step m of recorded tick t:
+ *       snapshot m for m = 0, 1, 2 and the current state for m = 3.
+ * One frame:
+ *   0..3 / 4..7   agent words A / B, the encoding of stats words 36..43      8, 9   the two capsule words (stats words 44, 45)
+ *   10            data.score after the sub-step, signed.  The snapshots carry no score word, and need none: only the mover's
+ *                 returned pellets move the score (capture.py:495-511), so after sub-steps 0 .. 2 it is the previous frame's score
+ *                 + (ret_Y[m] - ret_X[m]) for a red mover, - for a blue one; after sub-step 3 it is the state's own score word.
+ *   11            EVENT (below)                                              12 .. 12 + height - 1   food rows, bit x of row y
+ * EVENT of sub-step m, the transition X -> Y with X the previous frame (EVENT of frame 0 is 0):
+ *   bits 0..2     the move that was made: 0 North, 1 East, 2 South, 3 West, 4 Stop (the env's action codes), 7 undetermined
+ *   bit 3         the mover died
+ *   bits 4..7     mask of the non-movers that died (bit 4 + i: agent i)
+ *   bit 8         the mover ate a pellet (carry_Y[m] > carry_X[m])
+ *   bit 9         a capsule was eaten (occupied capsule slots of X > those of Y)
+ *   bits 10..21   ret_Y[m] - ret_X[m]
+ * Deaths are decided by the table of "Episode statistics".  The move of a mover that did not die is the direction of pos_Y[m] -
+ * pos_X[m], Stop where the two are equal (an illegal request became Stop, capture.py:473-474).  The move of a mover that died is
+ * the unique d of the five for which pos_X[m] + d is the cell of an enemy in X (every death is a same-cell collision, capture.py:
+ * 670-728); 7 where no d or more than one qualifies.
+ * pmx_game_record_init, after pmx_reset or pmx_set_state and before the first step: zeroes the head but LAYOUT and writes frame 0.
+ * pmx_game_record_update, once after each pmx_step: a row whose DONE or OVERFLOW word is not 0 is left untouched, every word of it.
+ * A row with LEN == max_ticks (or a LEN outside 0 .. max_ticks) gets OVERFLOW = 1 and nothing else.  Any other row gets the four
+ * frames 4 LEN + 1 .. 4 LEN + 4, LEN += 1, and DONE = 1 where done_dev[env] != 0 (done_dev [n_envs] uint8, indexed by env, may be
+ * NULL: DONE is then never set).  X of sub-step 0 is read back from the log, frame 4 LEN.  max_ticks must be the value of init.
+ * Blind spot: the stats kernel's own (a scared ghost with one tick of fear left that steps onto an invader beside its own start is
+ * logged as a move, bit 3 clear), plus move code 7: a mover that died with two enemy cells, or none, within one step of the cell
+ * it left.  The frames themselves are exact in either case.
+ * One lane per env, no LDS, no atomics, plain vector stores (csrc/pmx_record.hip); no other kernel changes.  An open
+ * pmx_profile_begin records the update with the rule launches, as the stats update's.
+ * Errors: those of the stats calls (PMX_ERR_INVALID for a NULL handle or buffer, a range outside the handle, an unfinished
+ * pmx_step_agent tick and, for the update, where the snapshots do not describe the last tick; PMX_ERR_UNSUPPORTED on an auto_reset
+ * handle), and PMX_ERR_INVALID for max_ticks < 1.  count == 0 launches nothing. */
+#define PMX_RECORD_HEAD_WORDS 8
+enum { PMX_RECORD_LEN, PMX_RECORD_DONE, PMX_RECORD_OVERFLOW, PMX_RECORD_LAYOUT };
+int pmx_game_record_words(const pmx_env *env, int32_t *frame_words);      /* FW = 12 + H */
+int pmx_game_record_init(pmx_env *env, int32_t first, int32_t count, int32_t max_ticks, int32_t *head_dev, int32_t *frames_dev, void *stream);
+int pmx_game_record_update(pmx_env *env, int32_t first, int32_t count, int32_t max_ticks, const uint8_t *done_dev, int32_t *head_dev,
+                           int32_t *frames_dev, void *stream);
+
 /* ---- Sight rule on the four-agent planes (opt-in): the contest's observation on pmx_step / pmx_step_agent / pmx_observe / pmx_reset
  * gymPacMan's get_Observation hands every agent the full state; the contest hands agent i GameState.makeObservation(i)
  * (capture.py:268-292): the state with the configuration of every far enemy blanked, and four noisy distances.  The two calls below

@@ -27,6 +27,8 @@ STATS_WORDS = 48                                 # PMX_STATS_WORDS (pmx_episode_
  STAT_STOPS) = range(8)                          # PMX_STAT_*: counter c of agent i is word 8 i + c
 STAT_NAMES = ("eaten", "returned", "lost", "deaths", "kills", "capsules", "pacman_steps", "stops")
 STATS_W_TICKS, STATS_W_SCORE, STATS_W_DONE, STATS_W_STATE = 32, 33, 34, 36
+RECORD_HEAD_WORDS = 8                            # PMX_RECORD_HEAD_WORDS (pmx_game_record_update)
+RECORD_LEN, RECORD_DONE, RECORD_OVERFLOW, RECORD_LAYOUT = range(4)      # PMX_RECORD_*: the head words
 COLSUM_BLOCKS = 512
 LN32_PARTIAL_ROWS = 2048
 ACTOR_PACK_BYTES = 297984
@@ -108,6 +110,9 @@ PROTOTYPES = [
     ("pmx_belief_weights_update_evidence", C.c_int, [_VP, C.c_int, _VP, _I32, _I32, _I32, _I32, _VP, _VP, _VP, _VP, _VP, _VP, _VP]),
     ("pmx_episode_stats_init", C.c_int, [_VP, _I32, _I32, _VP, _VP]),
     ("pmx_episode_stats_update", C.c_int, [_VP, _I32, _I32, _VP, _VP, _VP]),
+    ("pmx_game_record_words", C.c_int, [_VP, C.POINTER(_I32)]),
+    ("pmx_game_record_init", C.c_int, [_VP, _I32, _I32, _I32, _VP, _VP, _VP]),
+    ("pmx_game_record_update", C.c_int, [_VP, _I32, _I32, _I32, _VP, _VP, _VP, _VP]),
     ("pmx_emit_team_obs_weighted", C.c_int, [_VP, C.c_int, _VP, _VP, _VP, _VP]),
     ("pmx_emit_team_obs_mixed_weighted", C.c_int, [_VP, _VP, _I32, _I32, _VP, _VP, _VP, _VP]),
     ("pmx_get_layout_index", C.c_int, [_VP, C.POINTER(_I32), _VP]),

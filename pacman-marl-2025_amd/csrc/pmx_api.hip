@@ -27,6 +27,9 @@ extern "C" hipError_t pmx_launch_belief_evidence(const PmxBeliefWeightsParams *p
                                                  hipEvent_t ev0, hipEvent_t ev1);
 extern "C" hipError_t pmx_launch_episode_stats(const uint32_t *const *snap, const uint8_t *done, int32_t *stats, int N, int first, int count, int H,
                                                int init, hipStream_t st, hipEvent_t ev0, hipEvent_t ev1);
+extern "C" hipError_t pmx_launch_game_record(const uint32_t *const *snap, const uint8_t *done, const int32_t *layout_idx, int32_t *head,
+                                             int32_t *frames, int N, int first, int count, int H, int max_ticks, int init, hipStream_t st,
+                                             hipEvent_t ev0, hipEvent_t ev1);
 extern "C" hipError_t pmx_launch_expand(const PmxExpandParams *p, int dtype, hipStream_t st, hipEvent_t ev0, hipEvent_t ev1);
 extern "C" hipError_t pmx_launch_expand_sight(const PmxExpandParams *p, int dtype, int sight, hipStream_t st, hipEvent_t ev0, hipEvent_t ev1);
 extern "C" hipError_t pmx_launch_agent_distances(const uint32_t *const *snap, const uint32_t *state, int8_t *dist, int N, int H, int agent,
@@ -780,6 +783,49 @@ int pmx_episode_stats_init(pmx_env *env, int32_t first, int32_t count, int32_t *
 int pmx_episode_stats_update(pmx_env *env, int32_t first, int32_t count, const uint8_t *done_dev, int32_t *stats_dev, void *stream)
 {
     return episode_stats(env, "pmx_episode_stats_update", 0, first, count, done_dev, stats_dev, stream);
+}
+
+// Game records (include/pmx.h, "Game records")
+int pmx_game_record_words(const pmx_env *env, int32_t *frame_words)
+{
+    if (!env || !frame_words) return fail(PMX_ERR_INVALID, "pmx_game_record_words: null argument");
+    *frame_words = 12 + env->lay.H;
+    return PMX_OK;
+}
+
+namespace {
+int game_record(pmx_env *env, const char *who, int init, int32_t first, int32_t count, int32_t max_ticks, const uint8_t *done_dev,
+                int32_t *head_dev, int32_t *frames_dev, void *stream)
+{
+    if (!env || !head_dev || !frames_dev) return fail(PMX_ERR_INVALID, "%s: null argument", who);
+    if (env->cfg.auto_reset)
+        return fail(PMX_ERR_UNSUPPORTED, "%s: an auto_reset handle overwrites a finished env's snapshots with the fresh game inside the tick", who);
+    if (first < 0 || count < 0 || (int64_t)first + count > env->cfg.n_envs)
+        return fail(PMX_ERR_INVALID, "%s: envs %d .. %lld of %d", who, first, (long long)first + count - 1, env->cfg.n_envs);
+    if (max_ticks < 1) return fail(PMX_ERR_INVALID, "%s: max_ticks %d < 1", who, max_ticks);
+    if (env->open_agent != 0) return fail(PMX_ERR_INVALID, "%s: a tick opened with pmx_step_agent is unfinished", who);
+    if (!init && !env->snaps_valid)
+        return fail(PMX_ERR_INVALID, "%s: the sub-step snapshots do not describe the last tick (call it once after each pmx_step)", who);
+    if (count == 0) return PMX_OK;
+    const size_t snap_sz = (size_t)PMX_SNAP_WORDS(env->lay.H) * env->cfg.n_envs;
+    const uint32_t *snap[4];
+    for (int a = 0; a < 4; ++a) snap[a] = (!init && a < 3) ? env->snap_dev + a * snap_sz : env->state_dev;
+    hipEvent_t *ev = init ? nullptr : prof_pair(env, false);          // recorded with the rule launches, as the stats update is
+    HIP_TRY(pmx_launch_game_record(snap, done_dev, env->layout_idx_dev, head_dev, frames_dev, env->cfg.n_envs, first, count, env->lay.H,
+                                   max_ticks, init, as_stream(stream), ev ? ev[0] : nullptr, ev ? ev[1] : nullptr));
+    return PMX_OK;
+}
+}  // namespace
+
+int pmx_game_record_init(pmx_env *env, int32_t first, int32_t count, int32_t max_ticks, int32_t *head_dev, int32_t *frames_dev, void *stream)
+{
+    return game_record(env, "pmx_game_record_init", 1, first, count, max_ticks, nullptr, head_dev, frames_dev, stream);
+}
+
+int pmx_game_record_update(pmx_env *env, int32_t first, int32_t count, int32_t max_ticks, const uint8_t *done_dev, int32_t *head_dev,
+                           int32_t *frames_dev, void *stream)
+{
+    return game_record(env, "pmx_game_record_update", 0, first, count, max_ticks, done_dev, head_dev, frames_dev, stream);
 }
 
 namespace {

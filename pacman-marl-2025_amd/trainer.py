@@ -1039,7 +1039,7 @@ class _MatchEyes:
 
 @torch.no_grad()
 def play_match(a, b, layout="bloxCapture", n_envs=1024, length=300, colours="both", device="cuda:0", seed=0, autocast=True, fog_bots=False,
-               env=None):
+               env=None, record=0):
     """n_envs games at once between two MatchSides, each seeing the game its own way, with the device episode statistics
     (pmx_episode_stats_update) of every game.  colours: see match_colours; B's colours are A's inverted.  Per tick every network side
     gets one pmx_emit_team_obs_mixed* call of its own regime and colours, runs its own forward, and draws with
@@ -1051,6 +1051,8 @@ def play_match(a, b, layout="bloxCapture", n_envs=1024, length=300, colours="bot
     red), the same under as_red / as_blue, ticks_mean, return_a (mean over games of A's summed team reward, as evaluate_vectorized sums
     it), stats_a / stats_b (per counter of _lib.STAT_NAMES the per-game means of the side's two slots, lower agent index first), and
     the raw tensors red [n], score [n], stats [48, n].
+    record=k: the first min(k, n_envs) games are logged sub-step by sub-step (pmx_game_record_update) and the result's "record" is
+    their game_record.GameRecord (meta: A's colour per game, the sides' names); 0: no log, no extra call, "record" is None.
     Two greedy networks are refused (every game of a colour would be the same game).  `env`: a ready env in place of the PmxVecEnv
     this function creates (tests)."""
     bot_sight = _check_match(a, b, fog_bots)
@@ -1064,6 +1066,8 @@ def play_match(a, b, layout="bloxCapture", n_envs=1024, length=300, colours="bot
         env.set_bot_sight(bot_sight)
     env.reset(want_obs=False)
     stats = env.episode_stats_init(env.new_episode_stats())
+    record = max(0, min(int(record), n_envs))
+    rec = env.game_record_init(env.new_game_record(0, record)) if record else None
     models = [s.model for s in (a, b) if s.model is not None]
     was_training = [m.training for m in models]
     for m in models:
@@ -1088,6 +1092,8 @@ def play_match(a, b, layout="bloxCapture", n_envs=1024, length=300, colours="bot
         for e in eyes:
             e.after_step()
         env.episode_stats_update(stats, done)
+        if rec is not None:
+            env.game_record_update(rec, done)
         own = torch.where(red_b, rew[:, 0], rew[:, 1])
         ret += torch.where(alive, own + own, torch.zeros_like(ret))                 # sum over both of A's agents' rewards (:328)
         other = torch.where(red_b, rew[:, 1], rew[:, 0])
@@ -1108,7 +1114,12 @@ def play_match(a, b, layout="bloxCapture", n_envs=1024, length=300, colours="bot
         raise RuntimeError("play_match: the statistics' SCORE differs from the score the env reported at a game's done")
     if not torch.equal(R, final):
         raise RuntimeError("play_match: red RETURNED minus blue RETURNED differs from the final score")
-    return match_result(red_a, final, ret, ret_b, stats)
+    out = match_result(red_a, final, ret, ret_b, stats)
+    out["record"] = None
+    if rec is not None:
+        names = [s.bot if s.model is None else "network" for s in (a, b)]
+        out["record"] = rec.to_host(a_is_red=[int(v) for v in red_a[:record].tolist()], side_a=str(names[0]), side_b=str(names[1]), seed=int(seed))
+    return out
 
 
 class _NullCtx:

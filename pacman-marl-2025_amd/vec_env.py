@@ -22,6 +22,25 @@ def legal_list(mask):
     return [a for a in LEGAL_LIST_ORDER if (int(mask) >> a) & 1]
 
 
+class DeviceGameRecord:
+    """The two caller-owned buffers of include/pmx.h, "Game records", for `count` envs from `first`: head int32 [8, count] and
+    frames int32 [1 + 4 max_ticks, frame_words, count], zeroed (PmxVecEnv.new_game_record)."""
+
+    def __init__(self, env, first, count, max_ticks, frame_words):
+        self.env, self.first, self.count, self.max_ticks, self.frame_words = env, first, count, max_ticks, frame_words
+        self.head = torch.zeros((_lib.RECORD_HEAD_WORDS, count), dtype=torch.int32, device=env.device)
+        self.frames = torch.zeros((1 + 4 * max_ticks, frame_words, count), dtype=torch.int32, device=env.device)
+
+    def to_host(self, **meta):
+        """-> game_record.GameRecord: the head, the frames up to the longest game, the env's layouts and the metadata (one
+        device-to-host copy of each buffer; synchronises)."""
+        from .game_record import GameRecord
+        head = self.head.cpu().numpy()
+        n = 1 + 4 * min(self.max_ticks, max(0, int(head[_lib.RECORD_LEN].max(initial=0))))
+        meta = dict(dict(first=self.first, max_ticks=self.max_ticks, length=self.env.length), **meta)
+        return GameRecord(head, self.frames[:n].cpu().numpy(), [list(l.text) for l in self.env.layouts], meta)
+
+
 class PmxVecEnv:
     def __init__(self, layout, n_envs, length=299, reward_forLegalAction=True, defenceReward=True, auto_reset=True,
                  obs_dtype="float32", obs_agents=(0, 1, 2, 3), device="cuda:0", seed=0, layout_index=None, bots=False,
@@ -470,6 +489,46 @@ class PmxVecEnv:
         out = {name: per[:, c].t() for c, name in enumerate(_lib.STAT_NAMES)}
         out.update(ticks=stats[_lib.STATS_W_TICKS], score=stats[_lib.STATS_W_SCORE], done=stats[_lib.STATS_W_DONE])
         return out
+
+    # -- game records: a device log of every sub-step (include/pmx.h, "Game records") ------------------------------------
+    def new_game_record(self, first=0, count=None, max_ticks=None):
+        """The log buffers for the envs first .. first + count - 1 (count None: all from `first`) and up to max_ticks ticks (None:
+        length + 1, a whole episode): a DeviceGameRecord.  Call game_record_init before the first step.  Needs an env created
+        with auto_reset=False."""
+        first = int(first)
+        count = self.n_envs - first if count is None else int(count)
+        max_ticks = self.length + 1 if max_ticks is None else int(max_ticks)
+        fw = C.c_int32()
+        _lib.call("pmx_game_record_words", self.handle, C.byref(fw))
+        return DeviceGameRecord(self, first, count, max_ticks, fw.value)
+
+    def _check_record(self, rec):
+        for t, shape in ((rec.head, (_lib.RECORD_HEAD_WORDS, rec.count)), (rec.frames, (1 + 4 * rec.max_ticks, rec.frame_words, rec.count))):
+            assert t.shape == shape and t.dtype == torch.int32 and t.is_contiguous() and t.device == self.device
+
+    def game_record_init(self, rec):
+        """pmx_game_record_init, after reset() or set_state() and before the first step(): LEN, DONE and OVERFLOW of every row
+        to zero, LAYOUT from the env's layout, frame 0 from the current state."""
+        self._check_record(rec)
+        if rec.count == 0:                               # (an empty tensor has no address to pass)
+            return rec
+        with torch.cuda.device(self.device):
+            _lib.call("pmx_game_record_init", self.handle, rec.first, rec.count, rec.max_ticks, rec.head.data_ptr(), rec.frames.data_ptr(),
+                      _lib.stream(self.device))
+        return rec
+
+    def game_record_update(self, rec, done=None):
+        """pmx_game_record_update, once after each step(): the tick's four sub-step states and their EVENT words into every row
+        that is neither DONE nor full.  done: uint8 [N] (step()'s done), non-zero = the row is DONE from now on."""
+        self._check_record(rec)
+        if done is not None:
+            assert done.shape == (self.n_envs,) and done.dtype == torch.uint8 and done.is_contiguous() and done.device == self.device
+        if rec.count == 0:
+            return rec
+        with torch.cuda.device(self.device):
+            _lib.call("pmx_game_record_update", self.handle, rec.first, rec.count, rec.max_ticks, done.data_ptr() if done is not None else None,
+                      rec.head.data_ptr(), rec.frames.data_ptr(), _lib.stream(self.device))
+        return rec
 
     # -- measurement ---------------------------------------------------------------------------------------------
     def profile_begin(self, max_launches):

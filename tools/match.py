@@ -7,6 +7,7 @@ regime it was trained with.
     python tools/match.py fog.pt belief.pt --a-fog-of-war --b-fog-of-war --b-belief --games 1024 --layout smallCapture
     python tools/match.py ckpt.pt baseline --a-greedy
     python tools/match.py approxq baseline
+    python tools/match.py approxq baseline --record games.npz --record-games 8        (then: python tools/replay.py games.npz --events)
 """
 import argparse
 import json
@@ -50,11 +51,18 @@ def main(argv=None):
     ap.add_argument("--seed", type=int, default=0)
     ap.add_argument("--fog-bots", action="store_true", help="a bot side obeys the sight rule of the opposing network (needs that side's fog-of-war)")
     ap.add_argument("--device", default="cuda:0")
+    ap.add_argument("--record", metavar="PATH", help="save a game record (.npz) of the first --record-games games; tools/replay.py prints it")
+    ap.add_argument("--record-games", type=int, default=4, help="with --record: how many games to log")
     args = ap.parse_args(argv)
     sides = [make_side(args, k, what, args.layout, args.device) for k, what in (("a", args.a), ("b", args.b))]
     r = trainer.play_match(sides[0], sides[1], layout=args.layout, n_envs=args.games, length=args.length, colours=args.colours,
-                           device=args.device, seed=args.seed, fog_bots=args.fog_bots)
+                           device=args.device, seed=args.seed, fog_bots=args.fog_bots, record=args.record_games if args.record else 0)
+    record = r.pop("record", None)
     out = {k: v for k, v in r.items() if not isinstance(v, torch.Tensor)}
+    if record is not None:
+        record.meta.update(a=args.a, b=args.b, layout=args.layout)
+        record.save(args.record)
+        out.update(record=args.record, record_games=record.games)
     out.update(a=args.a, b=args.b, layout=args.layout, colours=args.colours, seed=args.seed)
     print(json.dumps(out))
     return out
